@@ -9,6 +9,13 @@ MI355X; with --gpus N the frame's rays are sharded N-way and the rendered tiles 
 One "step" = one full pass of the hot path over one batch = one rendered frame (all rays of the frame,
 or this rank's shard of them).  Inputs (rays, weights, occupancy bitfield) are resident in HBM before the
 timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly the --steps frames once (nothing instrumented) and prints the line.
+--full adds everything else the line used to carry, each from runs of its own after the timed region: the per-kernel
+`roofline` / `kernel_times` (the stream again, repeated to --min-timed-s, field launches timed in place), the one-loop
+latency, `roofline_secondary`, `grid_gather_rate`, `latency_ms_one_frame`, `reference_shaped` and `cpu_baseline`.
+--dump-outputs DIR writes what the last timed loop returned (image, depth of its rays; depth_valid = 0 where depth is NaN, written
+as 0) as DIR/<name>.npy, float32.
 """
 import argparse
 import json
@@ -42,8 +49,8 @@ def parse():
     ap.add_argument("--fp32", action="store_true", help="fp32 field network instead of the -O (fp16) configuration")
     ap.add_argument("--field", default="auto", choices=["auto", "ops", "fused"], help="field network implementation")
     ap.add_argument("--loop", default="auto", choices=["auto", "host", "device"], help="loop driver: per-iteration host sync, or device-driven")
-    ap.add_argument("--time-every", type=int, default=8, help="record the per-launch HIP events of the tracked kernels on every K-th timed step "
-                    "(each event record costs ~5 us of queue time between two dependent launches; K = 1 instruments every step)")
+    ap.add_argument("--time-every", type=int, default=8, help="--full: record the per-launch HIP events of the tracked kernels on every K-th step "
+                    "of the instrumented run (each event record costs ~5 us of queue time between two dependent launches; K = 1 instruments every step)")
     ap.add_argument("--pipeline", type=int, default=2, metavar="DIV",
                     help="device loop: render the timed steps as a stream of frames through --contexts loop contexts; the next frame "
                          "starts when a context is free and the newest frame in flight is down to rays / DIV alive (1 = at once; 2 = behind the newest "
@@ -74,13 +81,19 @@ def parse():
                                                                  "second stream, beside the next step's deformation-MLP forward")
     ap.add_argument("--gather-dtype", default="f32", choices=["f32", "f16", "u8"],
                     help="--gpus N: what the per-frame all-gather moves (fp32 as rendered; fp16; or the 8-bit pixels the reference writes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-side", type=int, default=224, help="side of the CPU-baseline sample of the 800x800 camera (224: ~12 s of CPU work; "
                                                                        "800 = the whole frame SURVEY 8(d) names, ~160 s)")
     ap.add_argument("--min-timed-s", type=float, default=0.25,
-                    help="the K-step stream is repeated inside the timed region until it lasts at least this long (ms_per_step = elapsed / "
-                         "frames rendered; `repeats` in the output; 0 = exactly one pass)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the marcher / grid_encode side measurements (roofline_secondary, grid_gather_rate)")
+                    help="--full: the instrumented run behind `roofline` / `kernel_times` repeats the K-step stream until it lasts at least this "
+                         "long (`repeats` in `roofline`; 0 = exactly one pass).  The headline always times the K steps once")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the side measurements (roofline_secondary, grid_gather_rate, "
+                                                                "latency_ms_one_frame, reference_shaped)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else: per-kernel roofline and kernel times, "
+                                                        "latencies, marcher / grid_encode side figures, the reference-shaped caller, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="render mode: write what the last timed loop returned (image [rays, 3], depth [rays] with NaN written as 0, "
+                         "depth_valid [rays]) as DIR/<name>.npy in float32; above 60 MB a fixed, seeded sample of the rays")
     return ap.parse_args()
 
 
@@ -407,6 +420,8 @@ def self_launch(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.mode != "render":
+        raise SystemExit("--dump-outputs: render mode only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and args.mode == "render":
         self_launch(args)
     # One hardware queue per stream in use (the loop contexts + torch's default stream), set before the HIP runtime starts: with the
@@ -576,10 +591,13 @@ def main():
                     "gather_hidden_frac": 1.0 - min(1.0, exposed / max(gather_ms, 1e-9))}
 
     gather_stats, rank_stats = GatherStats(), {}
+    last_gathered = [None]     # the newest assembled frame(s): [n_rays, 4] or [F, n_rays, 4] (image, depth), for --dump-outputs
 
     def gather_outputs(img, dep):
         """One RCCL all-gather per LOOP (+ local un-permute): a frame, or the frames of a group together."""
-        gather_stats.wrap((lambda: gather(img, dep)) if F == 1 else (lambda: gather.gather_group(img, dep, F)))
+        def run():
+            last_gathered[0] = gather(img, dep) if F == 1 else gather.gather_group(img, dep, F)
+        gather_stats.wrap(run)
 
     def stream_of_frames(k, every=0, reps=1):
         """The first k loops (frames, or frame groups) of the sequence, `reps` times over, through the pipelined driver as ONE stream;
@@ -669,44 +687,63 @@ def main():
     import gc
     gc.collect()
     gc.disable()
-    reps, marked, excl_set = 1, [], set()
     if ploop is not None:
         stream_of_frames(min(n_groups, max(args.contexts, args.warmup)))           # warm every context
-        # The driver's command times K = 20 steps: 13 ms.  The K-step stream is therefore repeated inside the timed region until it
-        # lasts >= --min-timed-s: a first un-instrumented pass of the K steps gives the rate, the timed pass then renders
-        # ceil(min / rate) repetitions as ONE stream; ms_per_step = elapsed / loops rendered.
+    # The headline: the K steps of --steps, rendered once, nothing instrumented; ms_per_step = elapsed / K.
+    gather_stats.reset()
+    if ploop is not None:
+        elapsed, outs, _, _ = stream_of_frames(n_groups)
+        last_out = outs[-1]
+    else:
+        barrier()
+        t0 = time.perf_counter()
+        for i in range(n_groups):
+            out = step(i)
+        barrier()
+        elapsed = time.perf_counter() - t0
+        last_out = (out["image"], out["depth"])
+    head_rank_stats = dict(rank_stats)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received from its last loop, copied before anything else renders into the same buffers
+        if world > 1:
+            g = last_gathered[0].float().reshape(-1, 4)
+            image, depth = g[:, :3].cpu().numpy(), g[:, 3].cpu().numpy()
+        else:
+            image, depth = last_out[0].float().reshape(-1, 3).cpu().numpy(), last_out[1].float().reshape(-1).cpu().numpy()
+        # a ray that misses the box has depth 0 / 0 = NaN (as in the reference): written as 0 with depth_valid = 0, so that two dumps
+        # compare with any tolerance test
+        valid = np.isfinite(depth)
+        dumped = {"image": image, "depth": np.where(valid, depth, 0.0), "depth_valid": valid}
+    reps, marked, excl_set = 1, [], set()
+    latency_ms = None
+    if args.full and ploop is not None:
+        # The per-kernel figures, from a run of their own: the K-step stream repeated until it lasts >= --min-timed-s (the headline pass
+        # gives the rate: ceil(min / rate) repetitions as ONE stream), the field launches of every --time-every-th loop timed in place.
         if args.min_timed_s > 0:
-            probe_s, _, _, _ = stream_of_frames(n_groups)
-            reps = max(1, int(np.ceil(1.15 * args.min_timed_s / max(probe_s, 1e-6))))
+            reps = max(1, int(np.ceil(1.15 * args.min_timed_s / max(elapsed, 1e-6))))
         if world > 1:      # every rank must render the same number of loops
             rt = torch.tensor([reps], dtype=torch.int64, device="cpu" if rehearse else dev)
             dist.all_reduce(rt, op=dist.ReduceOp.MAX)
             reps = int(rt.item())
-        gather_stats.reset()
         every_eff = every if every else 0
         if every_eff and n_groups * reps < 8:
             every_eff = 0
-        elapsed, _, marked, excl_set = stream_of_frames(n_groups, every_eff, reps)
+        _, _, marked, excl_set = stream_of_frames(n_groups, every_eff, reps)
         every = every_eff
-    else:
-        one = None
+    elif args.full:
         if dloop is not None and args.min_timed_s > 0:
-            barrier(); t0 = time.perf_counter(); step(0); barrier()
-            one = time.perf_counter() - t0
-            reps = max(1, int(np.ceil(args.min_timed_s / max(one * n_groups, 1e-6))))
+            reps = max(1, int(np.ceil(args.min_timed_s / max(elapsed, 1e-6))))
         n_instrumented = len(range(0, n_groups * reps, every)) if every else 0
         if dloop is not None:
             dloop.prepare_timing(n_instrumented)  # event pairs for the in-place timing of the fused-field launches, created up front
         barrier()
-        t0 = time.perf_counter()
         for i in range(n_groups * reps):
             step(i % n_groups, timed=bool(every) and (i % every == 0))
         barrier()
-        elapsed = time.perf_counter() - t0
         marked = list(range(0, n_groups * reps, every)) if every else []
     # latency of ONE loop with nothing else in flight (what --pipeline 0 reports as ms_per_step), same sequence, after the timed region
-    latency_ms = None
-    if dloop is not None:
+    if args.full and dloop is not None:
         lat = []
         for g in range(min(n_groups, 8)):
             barrier()
@@ -721,7 +758,7 @@ def main():
         # per-rank device-side spans (render_ms: first launch -> last loop done; gather_ms_*: events on the gather stream; how much of
         # the gather time was hidden under rendering): what the first real N-GPU run should be read by
         all_rank_stats = [None] * world
-        dist.all_gather_object(all_rank_stats, dict(rank_stats, rank=rank, elapsed_ms=elapsed * 1e3))
+        dist.all_gather_object(all_rank_stats, dict(head_rank_stats, rank=rank, elapsed_ms=elapsed * 1e3))
         cdev = "cpu" if rehearse else dev
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -731,8 +768,7 @@ def main():
         n_samples = int(ns.item())
     else:
         n_samples = n_samples_local
-    frames_rendered = K * reps
-    n_samples *= reps
+    frames_rendered = K
     ms_per_step = elapsed / frames_rendered * 1e3
     points_per_s = n_samples / elapsed
     n_rays_frame = n_total if args.emulate_rank_of <= 1 else n_local
@@ -744,10 +780,9 @@ def main():
     result = {
         "metric": METRIC, "value": points_per_s, "unit": "sampled-points/s", "rays_per_s": rays_per_s,
         "n_gpus": world, "steps": K, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "repeats": reps, "frames_rendered": frames_rendered, "timed_region_s": elapsed,
+        "frames_rendered": frames_rendered, "timed_region_s": elapsed,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "f16" if fp16 else "f32", "data": "synthetic",
-        "latency_ms_one_loop_at_a_time": latency_ms,
         "config": {"workload": f"dnerf {args.scene}-like {args.size}x{args.size} full-frame inference render, "
                                f"{'-O (fp16 field network, fp16 grid table)' if fp16 else 'fp32'}, {seq}, "
                                f"T_thresh 1e-2, max_steps 1024, dt_gamma 0",
@@ -758,7 +793,11 @@ def main():
                    "parallelism": (f"ray-tiles x{world}, {F} frames per loop, one all_gather_into_tensor per loop ({args.gather_dtype})" + (" (ONE-GPU REHEARSAL, numbers invalid)" if rehearse else "")) if world > 1
                                   else ("single GPU" + (f" rendering rank 0's shard of a {args.emulate_rank_of}-way ray split (NOT a whole-frame figure)" if args.emulate_rank_of > 1 else ""))},
     }
-    if rank == 0:
+    if world > 1:
+        result["ranks"] = all_rank_stats
+    if rank == 0 and args.full:
+        result["latency_ms_one_loop_at_a_time"] = latency_ms
+
         def loop_samples(g):     # sampled points of loop g of the (repeated) stream
             g = g % n_groups
             return distinct[tuple(frame_cam[g * F:(g + 1) * F])][0]
@@ -774,11 +813,12 @@ def main():
             over_samples = 0
         result["roofline"], result["kernel_times"] = roofline(timers, fp16, excl_samples, over_samples) if every else (None, {})
         if result["roofline"]:
+            result["roofline"]["repeats"] = reps
             result["roofline"]["instrumented_steps"] = (
-                f"{n_instrumented} of {n_groups * reps} timed loops (every {every}th" + (", plus the last" if ploop is not None else "") + ")"
+                f"{n_instrumented} of {n_groups * reps} loops of the instrumented run (every {every}th" + (", plus the last" if ploop is not None else "") + ")"
                 + (f"; {n_excl} of them (the last" + (" and the quarter points" if n_excl > 2 else (" and the midpoint" if n_excl == 2 else "")) + ") rendered with nothing else in flight -- their launches give achieved / frac -- and "
                    f"{n_instrumented - n_excl} overlapped like the uninstrumented ones (the `overlapped` entry)" if ploop is not None else ""))
-            # field FLOPs of the whole timed region over its wall time: a lower bound of the kernel's rate that no overlap can inflate
+            # field FLOPs of the headline's timed region over its wall time: a lower bound of the kernel's rate that no overlap can inflate
             result["roofline"]["whole_job_mfma_frac"] = FIELD_FLOP_PER_POINT * n_samples / elapsed / 1e12 / result["roofline"]["peak"]
         if world == 1 and dloop is not None and not args.no_secondary and args.emulate_rank_of <= 1:
             result["roofline_secondary"] = marcher_roofline(dloop, grp_o, grp_d, grp_t, n_groups, distinct, frame_cam, F)
@@ -792,13 +832,30 @@ def main():
             # --fp32: one frame alone and the reference's caller (no autocast; forward dispatching to the fp32 fused kernel)
             result["latency_ms_one_frame"] = one_frame_latency(sc, field, cam_o, cam_d, cam_t, dev)
             result["reference_shaped"] = reference_shaped(sc, cam_o, cam_d, cam_t, fp32=True)
-        if world > 1:
-            result["ranks"] = all_rank_stats
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(sc, args.cpu_baseline_side)
+    if rank == 0:
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(result))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES_MAX = 60 * 10 ** 6      # --dump-outputs: the arrays' bytes together (below 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: arrays (name -> numpy array whose first axis runs over the same rays) as DIR/<name>.npy in float32.  Above
+    DUMP_BYTES_MAX together, the same fixed, seeded sample of rays (sorted ray indices, seed 0) is kept from every array."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(a.astype(np.float32, copy=False).nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        idx = np.sort(np.random.default_rng(0).choice(n, n * DUMP_BYTES_MAX // total, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def one_frame_latency(sc, field, cam_o, cam_d, cam_t, dev, frames=8):

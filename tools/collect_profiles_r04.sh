@@ -10,16 +10,16 @@ PART=${1:-all}
 want() { [ "$PART" = "all" ] || [ "$PART" = "$1" ]; }
 stats() {  # name, bench args...
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tmp_$name -o p -- python3 bench.py "$@" > $OUT/bench_${name}_under_rocprof.json 2> $OUT/${name}.err || return 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tmp_$name -o p -- python3 bench.py --full "$@" > $OUT/bench_${name}_under_rocprof.json 2> $OUT/${name}.err || return 1
   cp $(find $OUT/tmp_$name -name "*kernel_stats.csv" | head -1) $OUT/${name}_kernel_stats.csv
   rm -rf $OUT/tmp_$name
 }
 if want bench; then
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2>$OUT/bench_driver_cmd.err || exit 1; echo "driver cmd done"
-python3 bench.py > $OUT/bench_default.json 2>/dev/null || exit 1; echo "bench default done"
-python3 bench.py --steps 20 --pipeline 0 --group-frames 1 --no-cpu-baseline > $OUT/bench_sequential.json 2>/dev/null || exit 1
-python3 bench.py --steps 20 --warmup 5 --pipeline 0 --no-cpu-baseline --no-secondary > $OUT/bench_one_loop_at_a_time.json 2>/dev/null || exit 1
-python3 bench.py --fp32 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_fp32.json 2>/dev/null || exit 1
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.json 2>$OUT/bench_driver_cmd.err || exit 1; echo "driver cmd done"
+python3 bench.py --full > $OUT/bench_default.json 2>/dev/null || exit 1; echo "bench default done"
+python3 bench.py --full --steps 20 --pipeline 0 --group-frames 1 --no-cpu-baseline > $OUT/bench_sequential.json 2>/dev/null || exit 1
+python3 bench.py --full --steps 20 --warmup 5 --pipeline 0 --no-cpu-baseline --no-secondary > $OUT/bench_one_loop_at_a_time.json 2>/dev/null || exit 1
+python3 bench.py --full --fp32 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_fp32.json 2>/dev/null || exit 1
 echo "bench lines done"
 fi
 if want stats; then
@@ -30,7 +30,7 @@ stats sequential --steps 20 --warmup 3 --pipeline 0 --group-frames 1 --no-cpu-ba
 echo "stats done"
 fi
 if want pmc; then
-# PMC: the static frame, 4 copies per loop (the default frame-group size), one loop at a time: 1 count + 1 warm-up + 2 timed + 2 latency = 6 loops
+# PMC: the static frame, 4 copies per loop (the default frame-group size), one loop at a time: 1 count + 1 warm-up + 2 timed = 4 loops (a plain run)
 B="python3 bench.py --static-frame --steps 8 --warmup 1 --pipeline 0 --no-cpu-baseline --no-secondary --min-timed-s 0"
 $B > $OUT/bench_pmc_command.json 2>/dev/null || exit 1
 timeout -k 10 1000 python3 tools/pmc_passes.py $OUT/pmc_field $OUT/pmc_field_raw.json \
@@ -41,7 +41,7 @@ timeout -k 10 1000 python3 tools/pmc_passes.py $OUT/pmc_field $OUT/pmc_field_raw
   --set G=TCC_HIT_sum,TCC_MISS_sum,TCC_REQ_sum,TCC_READ_sum --set H=TCP_TOTAL_CACHE_ACCESSES_sum,TCP_TCC_READ_REQ_sum,TCP_TOTAL_ACCESSES_sum,TCP_TA_DATA_STALL_CYCLES_sum \
   --kernel k_field --kernel k_composite_march --kernel k_march_rays \
   --note "static frame x 4 per loop, one loop at a time" -- $B || exit 1
-python3 tools/field_pmc_summary.py $OUT/pmc_field_raw.json $OUT/bench_pmc_command.json 6 $OUT/field_pmc_summary.json || exit 1
+python3 tools/field_pmc_summary.py $OUT/pmc_field_raw.json $OUT/bench_pmc_command.json 4 $OUT/field_pmc_summary.json || exit 1
 echo "pmc done"
 fi
 if want grid; then
@@ -72,7 +72,7 @@ timeout -k 10 900 python3 tools/pmc_passes.py $OUT/pmc_field32 $OUT/pmc_field_f3
 echo "pmc32 done"
 fi
 if want cpu800; then
-python3 bench.py --steps 20 --warmup 5 --no-secondary --cpu-baseline-side 800 > $OUT/bench_cpu_baseline_800.json 2>/dev/null || exit 1
+python3 bench.py --full --steps 20 --warmup 5 --no-secondary --cpu-baseline-side 800 > $OUT/bench_cpu_baseline_800.json 2>/dev/null || exit 1
 echo "cpu 800 done"
 fi
 if want modes; then
@@ -81,7 +81,7 @@ SDN_DETERMINISTIC=1 python3 bench.py --mode train --steps 300 --warmup 10 > $OUT
 python3 bench.py --mode seald --steps 20 > $OUT/bench_seald.json 2>/dev/null || exit 1
 python3 bench.py --mode seald-train --steps 50 > $OUT/bench_seald_train.json 2>/dev/null || exit 1
 python3 bench.py --mode density --steps 8 > $OUT/bench_density.json 2>/dev/null || exit 1
-python3 bench.py --steps 384 --scene lego --no-cpu-baseline --no-secondary > $OUT/bench_lego.json 2>/dev/null || exit 1
+python3 bench.py --full --steps 384 --scene lego --no-cpu-baseline --no-secondary > $OUT/bench_lego.json 2>/dev/null || exit 1
 echo "modes done"
 fi
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*agent_info.csv" -delete; find $OUT -name "*counter_collection.csv" -delete
