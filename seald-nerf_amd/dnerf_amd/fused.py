@@ -361,5 +361,8 @@ class DensityGridUpdater:
                       "density_grid_ema")
         check(sdn_backend.lib.sdn_density_grid_pack(ptr(grid), grid.numel(), ptr(self.sum), float(m.density_thresh), ptr(self.mean),
                                                     ptr(m.density_bitfield), stream()), "density_grid_pack")
+        # written through raw pointers: move the version counters, so that caches keyed on them (the drop-in marcher's cull grids)
+        # see the new occupancy
+        torch.autograd.graph.increment_version((m.density_bitfield, grid))
         m.iter_density += 1
         return self.mean

@@ -561,9 +561,13 @@ class DeviceLoop:
             for k in range(3):
                 box.map_source[k] = a["map_source"][k]
             box.has_map_source = 1
-        box.scratch = a["scratch"].data_ptr()
+        # the record's 32 scratch bytes (modify_rgb's sum / count, the mapSource flag word) belong to THIS loop, zeroed once: the loops
+        # of a PipelinedDeviceLoop share the mapper and run on their own streams, and one buffer between them would let one loop's
+        # memset / sums land in another's mean brightness, and a later loop's mapSource tag cancel an earlier one's redirect
+        scratch = torch.zeros(32, dtype=torch.uint8, device=dev)
+        box.scratch = scratch.data_ptr()
         mask = torch.empty(self.buf["sigmas"].shape[0], dtype=torch.uint8, device=dev)
-        self._seal = (box, mask, a)      # keep the record, the mask and the triangle tensor alive
+        self._seal = (box, mask, a, scratch)      # keep the record, the mask, the triangle tensor and the scratch alive
         c.seal, c.seal_mask = ctypes.addressof(box), mask.data_ptr()
 
     def prepare_timing(self, frames):
@@ -613,8 +617,8 @@ class DeviceLoop:
         import sdn_backend as B
         # The kept grid carries the slice's occupancy bits themselves (the packed fine-bit image the marchers copy to LDS), so a stale
         # entry means marching on stale OCCUPANCY: the epoch includes the bitfield's version counter -- load_state_dict, fill_bitfield
-        # and reset_extra_state rewrite the bitfield in place without a new iter_density -- and the cache lives ON the model object
-        # (an id()-keyed table would hand a new model the entry of a collected one whose id Python reused).
+        # and a direct `raymarching.packbits` into a slice rewrite the bitfield in place without a new iter_density -- and the cache
+        # lives ON the model object (an id()-keyed table would hand a new model the entry of a collected one whose id Python reused).
         cache = self.model.__dict__.get("_sdn_cull_cache")
         if cache is None:
             cache = {"epoch": None, "grids": {}}
@@ -633,8 +637,9 @@ class DeviceLoop:
     @staticmethod
     def invalidate_cull_grids(model=None):
         """Forget the kept cull grids of `model`: only needed after writing `density_bitfield` behind torch's back (a raw pointer, DLPack,
-        a custom kernel) -- torch-level writes (`update_extra_state`, `fill_bitfield`, `load_state_dict`, `copy_`) bump the tensor's
-        version counter and are seen by themselves."""
+        a custom kernel of the caller's) without moving its version counter (`torch.autograd.graph.increment_version`).  Torch-level
+        writes (`fill_bitfield`, `load_state_dict`, `copy_`) move it by themselves, and this package's kernel writers (`packbits` with a
+        bitfield, which `update_extra_state` calls; the native density update) move it after their launch: all of those are seen."""
         if model is not None:
             model.__dict__.pop("_sdn_cull_cache", None)
 

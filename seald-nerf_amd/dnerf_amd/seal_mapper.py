@@ -244,7 +244,8 @@ class SealBBoxMapper(SealMapper):
                                 test_dir=cfl(f32(_TEST_DIR if self.map_test_dir is None else self.map_test_dir.cpu().numpy())),
                                 tinv=cfl(f32(md["transform"][:3, :4])), rinv=cfl(f32(md["rotation"])), scale=cfl(f32(md["scale"])),
                                 center=cfl(f32(md["center"])),
-                                # [0..15] modify_rgb's sum / count, [16..19] the mapSource flag word (only ever raised), zeroed once
+                                # [0..15] modify_rgb's sum / count, [16..19] the mapSource flag word (only ever raised), zeroed once;
+                                # used by the in-place calls below (a DeviceLoop keeps its own: loops on other streams share the mapper)
                                 scratch=torch.zeros(32, dtype=torch.uint8, device=device))
             if "map_source" in md:
                 self._native["source_bound"] = cfl(f32(md["empty_bound"].reshape(2, 3)))

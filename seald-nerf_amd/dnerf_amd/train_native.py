@@ -113,6 +113,10 @@ class NativeTrainStep:
         self._cull_cache, self._cull_epoch = {}, None
         self._set, self._pending, self._side, self._before_step = 0, None, None, None
         self.grad_sync, self.train_deform = grad_sync, bool(train_deform)
+        # what the optimizer pass writes in place (a frozen deformation segment is read, never written): its version counters are moved
+        # after every step, so that what is derived from the parameters -- NeRFNetwork's fused-dispatch caches, the grid encoder's QUAD
+        # copy of the table -- is rebuilt
+        self._written = [p for i, (p, t) in enumerate(zip(self.params, self._trained)) if t and (self.train_deform or not 1 <= i <= 8)]
         self._table_side = None
         if overlap_table_update:
             self._table_side = (torch.cuda.Stream(device=self.device), torch.cuda.Event(), torch.cuda.Event())
@@ -384,6 +388,7 @@ class NativeTrainStep:
         _sdn.check(_sdn.lib.sdn_train_step_f16(ctypes.byref(r), _sdn.stream()), "train_step_f16")
         m.local_step += 1
         if not grads_only:
+            torch.autograd.graph.increment_version(self._written)
             self.step_count += 1
             self.ema_updates += 1
         return self.loss

@@ -105,10 +105,15 @@ class _packbits(Function):
         """raymarching.py:132-153.  grid [C, H^3] f32 -> bitfield [C*H^3/8] u8 (written in place if given)."""
         grid = _dev(grid).contiguous()
         N = grid.shape[0] * grid.shape[1] // 8
-        if bitfield is None:
+        given = bitfield is not None
+        if not given:
             bitfield = torch.empty(N, dtype=torch.uint8, device=grid.device)
         _check(_lib.sdn_packbits(_ptr(grid, _f32, "grid"), N, float(thresh), _ptr(bitfield, torch.uint8, "bitfield"), _stream()),
                "packbits")
+        if given:
+            # the kernel wrote through a raw pointer: move the version counter (a view's is its base's) so that what is derived from
+            # the old bits -- the marcher's cull grids, the native loops' kept grids -- is rebuilt
+            torch.autograd.graph.increment_version(bitfield)
         return bitfield
 
 
@@ -209,8 +214,11 @@ _CULL_CACHE = {}          # (data_ptr, bytes, device) -> (tensor version, cull g
 
 def _cull_grid_of(bitfield, C, H):
     """The marcher's coarse skip grid of one occupancy slice (128^3, cascade 1, 8-byte aligned), derived once per content: keyed by the
-    slice's address and its tensor version (a view shares its base's counter: `density_bitfield[t]` of a bitfield rewritten in place --
-    update_extra_state, load_state_dict, fill_bitfield -- misses).  None: this slice takes the plain marcher."""
+    slice's address and its tensor version (a view shares its base's counter, so a rewrite of any slice of `density_bitfield` misses).
+    Torch-level writes (load_state_dict, fill_bitfield, copy_) move the counter by themselves; this package's own kernel writers --
+    `packbits` with a bitfield (update_extra_state) and the native density update (dnerf_amd.fused.DensityGridUpdater) -- move it
+    after their launch.  A caller that writes the bits behind torch's back (raw pointer, DLPack, its own kernel) must call
+    `torch.autograd.graph.increment_version` on the tensor it wrote.  None: this slice takes the plain marcher."""
     if int(H) != 128 or int(C) != 1 or not bitfield.is_cuda or bitfield.dtype != torch.uint8 or not bitfield.is_contiguous():
         return None
     if bitfield.numel() != 128 * 128 * 128 // 8 or (bitfield.data_ptr() & 7) != 0:
