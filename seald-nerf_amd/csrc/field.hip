@@ -39,13 +39,6 @@
 #include "grid_common.h"
 #include "sh_eval.h"
 
-
-// Staggered half-workgroups in the hidden layers (waves 4-7 half a layer behind waves 0-3): built and bit-identical, measured neutral
-// to -3 % (profiles/r03_rejected_field_stagger.txt) -- compiled out by default; `make -C seald-nerf_amd/csrc stagger` builds the variant.
-#ifndef SDN_FIELD_STAGGER
-#define SDN_FIELD_STAGGER 0
-#endif
-
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -114,10 +107,6 @@ struct FieldArgs {
     float cell_inv;           // 1 / (grid_size - 1) in fp32: torch divides a tensor by a host scalar as a multiplication by its reciprocal
     float cell_span;          // bound_cas - half_grid   (dnerf/renderer.py:484-488)
     float cell_half;          // half_grid = bound_cas / grid_size
-    // workgroup stagger: workgroups [stagger_lo, stagger_hi) -- the second workgroup of every CU in the launch's first wave of
-    // workgroups -- start `stagger_cycles` shader cycles late, so that the two workgroups of a CU run their matrix and vector phases out
-    // of step (0 = off)
-    uint32_t stagger_cycles, stagger_lo, stagger_hi;
     uint32_t n_frames;        // rows of bias0 (frames of a frame group; 1 without slot_frame)
     uint32_t pp_soft;         // persistent kernel: the workgroup count to stay within unless more workgroups save a whole round (0 = gridDim.x)
 };
@@ -260,10 +249,6 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
     }
     const uint32_t count = P.state ? P.live_count[P.state[3]] : (P.live_idx ? *P.live_count : P.M);
     if (blockIdx.x * (uint32_t)kPointsPerWG >= count) return;  // workgroup-uniform: nothing to do, no barrier touched
-    if (P.stagger_cycles != 0u && blockIdx.x >= P.stagger_lo && blockIdx.x < P.stagger_hi) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)P.stagger_cycles) __builtin_amdgcn_s_sleep(64);
-    }
     const uint32_t n = lane & 31u, h = lane >> 5;
     const uint32_t i = blockIdx.x * (uint32_t)kPointsPerWG + wave * 32u + n;
     const bool valid = i < count;
@@ -351,24 +336,7 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
     // fills the remaining 24 and the two phases overlap.
     FSTAMP(1);
     __builtin_amdgcn_s_setprio(2);
-#if SDN_FIELD_STAGGER
-    // ---- staggered half-workgroups (cdna_hip_programming.md / MI355X_MICROARCH.md "Two waves per SIMD", item 9) ---------------------------
-    // The eight waves of a workgroup used to pass every layer boundary together: accumulator -> operand conversion (~100 VALU
-    // instructions), stage barrier, then 32 MFMAs -- the matrix pipe idled through every conversion, and the co-resident workgroup ran
-    // the same phases at the same time more often than not (in-kernel stamps of round 2: 3.6 K cycles per hidden layer where the
-    // pipe needs 2.0 K).  Now waves 4-7 (a SIMD's second wave of this workgroup) run HALF A LAYER behind waves 0-3: a hidden layer is
-    // two units of 16 MFMAs (k-steps 0-3 / 4-7) with one barrier each, and while one half-workgroup converts and starts a layer the
-    // other issues the second half of the previous layer's MFMAs.  Waves 4-7 simply pass one barrier more before layer 0 and one
-    // less before the tail (different points, no data dependence -- only the two 32 KiB weight buffers are shared):
-    //   global phase p:   waves 0-3 run unit p (p = -1: layer 0, 0..11: hidden units, 12: tail), waves 4-7 unit p - 1.
-    //   stage s (2..7) refills buffer s & 1 in phase 2 s - 3: its previous content, stage s - 2, was last read by waves 4-7 in phase
-    //   2 s - 4, and waves 0-3 first read stage s in phase 2 s - 2, behind every wave's vmcnt(0) + the barrier of that phase.
-    const bool late = __builtin_amdgcn_readfirstlane(wave) >= 4u;
-    stage_wait_and_sync();            // barrier of phase -1: D0 and D1 are resident
-    if (late) stage_wait_and_sync();  // barrier of phase 0 (waves 0-3 arrive at it after their layer 0)
-#else
     stage_wait_and_sync();  // D0 and D1 are resident
-#endif
     FSTAMP(2);
     #pragma unroll
     for (int ks = 0; ks < 4; ks++) {
@@ -376,64 +344,6 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
         for (int mt = 0; mt < 4; mt++) acc[mt] = mfma(lds_frag(s_w0, mt * 4 + ks, lane), bf[ks], acc[mt]);
     }
     FSTAMP(3);
-#if SDN_FIELD_STAGGER
-    // One unit: half a hidden layer (k-steps 4 HALF .. 4 HALF + 3), fragments from `cur`; refill (wave-uniform, run time: it depends
-    // on the half-workgroup): this wave's four 1-KiB pieces of stage `stage` go to `other`, issued together in front of the MFMAs
-    // under ONE scalar branch (a branch per piece between the MFMAs cut the chain into scheduling regions and spilled registers).
-    auto unit = [&](auto half_c, bool refill, const unsigned char *cur, unsigned char *other, int stage) __attribute__((always_inline)) {
-        constexpr int half = decltype(half_c)::value;
-        stage_wait_and_sync();
-        if (refill) {
-            // (stage 7, the tail, follows D6 in the packed buffer: one formula for every stage)
-            const unsigned char *__restrict__ refill_src = P.weights + (size_t)(kBlkD1 + (stage - 1) * 32) * 1024;
-            #pragma unroll
-            for (int k = 0; k < kStageBytes / 1024 / kWaves; k++) stage_piece(refill_src, other, k, wave, lane);
-        }
-        if constexpr (half == 0) {
-            #pragma unroll
-            for (int t = 0; t < 4; t++) acc_to_frags<true>(acc[t], bf[2 * t], bf[2 * t + 1]);
-            __builtin_amdgcn_sched_barrier(0);     // (the fragment read-ahead must not be hoisted over the conversion: it spills at 128 VGPRs)
-        }
-        half8 ring[LA];
-        #pragma unroll
-        for (int j = 0; j < LA; j++) ring[j] = lds_frag(cur, (j & 3) * 8 + 4 * half + (j >> 2), lane);
-        #pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const int ks = 4 * half + (i >> 2), mt = i & 3;
-            const half8 a = ring[i % LA];
-            if (i + LA < 16) ring[i % LA] = lds_frag(cur, ((i + LA) & 3) * 8 + 4 * half + ((i + LA) >> 2), lane);
-            if (ks == 0) {
-                f32x16 z;
-                #pragma unroll
-                for (int r = 0; r < 16; r++) z[r] = 0.0f;
-                acc[mt] = mfma(a, bf[0], z);
-            } else {
-                acc[mt] = mfma(a, bf[ks], acc[mt]);
-            }
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, LA, 0);
-        #pragma unroll
-        for (int i = 0; i < 16 - LA; i++) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, LA, 0);
-    };
-    static_assert(LA <= 16 && kBlkD7 == kBlkD1 + 6 * 32, "look-ahead is per unit of 16 MFMAs; the tail stage follows D6");
-    constexpr std::integral_constant<int, 0> H1{};
-    constexpr std::integral_constant<int, 1> H2{};
-    #pragma unroll 1
-    for (int b2 = 0; b2 < 3; b2++) {      // layers 2 b2 + 1 (stage in s_w1) and 2 b2 + 2 (stage in s_w0): units 4 b2 .. 4 b2 + 3
-        // waves 0-3 refill in their odd units (stage (u + 3) / 2), waves 4-7 -- one phase behind -- in their even units (stage (u + 4) / 2)
-        unit(H1, late, s_w1, s_w0, 2 * b2 + 2);
-        unit(H2, !late, s_w1, s_w0, 2 * b2 + 2);
-        unit(H1, late, s_w0, s_w1, 2 * b2 + 3);
-        unit(H2, !late, s_w0, s_w1, 2 * b2 + 3);
-    }
-    #pragma unroll
-    for (int t = 0; t < 4; t++) acc_to_frags<true>(acc[t], bf[2 * t], bf[2 * t + 1]);
-    if (!late) stage_wait_and_sync();   // barrier of phase 12: the tail stage (D7 | S0 | S1 | C0 | C1 | C2) is resident in buffer 1 (waves 4-7 passed it before their last unit)
-#else
     // ---------------- deform layers 1..6 (128 -> 128, ReLU): stage l+1 uses buffer (l+1)&1 ----------------
     // One hidden layer: fragments from `cur`, refill of `other` (static arrays: see the comment at their declaration).
     auto hidden_layer = [&](int l, const unsigned char *cur, unsigned char *other) __attribute__((always_inline)) {
@@ -486,7 +396,6 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
     for (int t = 0; t < 4; t++) acc_to_frags<true>(acc[t], bf[2 * t], bf[2 * t + 1]);
     stage_wait_and_sync();  // tail stage (D7 | S0 | S1 | C0 | C1 | C2) resident in buffer 1
     FSTAMP(10);
-#endif
     const unsigned char *tail = s_w1;
     constexpr int tD7 = 0, tS0 = kBlkS0 - kBlkD7, tS1 = kBlkS1 - kBlkD7, tC0 = kBlkC0 - kBlkD7, tC1 = kBlkC1 - kBlkD7, tC2 = kBlkC2 - kBlkD7;
 
@@ -798,6 +707,7 @@ namespace sdn_int {
 
 static int g_field_pp = -1;   // 1: large launches take the persistent ping-pong kernel (default), 0: never; -1: read SDN_FIELD_PP
 static int g_field_pp_wgs = 0;   // workgroups of a persistent launch; 0 = one per CU
+constexpr uint32_t kPPMinTilesPerCU = 4;   // launches of at least this many 256-point tiles per CU take the persistent kernel
 
 // launch used by both the C entry point and the device-driven render loop (render.hip)
 int field_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state,
@@ -814,6 +724,7 @@ int field_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live
     a.inv_2bound = exact_reciprocal(2 * bound);
     a.slot_frame = slot_frame; a.n_frames = slot_frame ? (n_frames > 16u ? 16u : n_frames) : 1u;
     a.cell_noise = nullptr; a.cell_seed = 0; a.cell_inv = a.cell_span = a.cell_half = 0;
+    a.pp_soft = 0;
     const uint32_t wgs = sdn_div_up(M, (uint32_t)kPointsPerWG);
     static int cus = 0;
     if (cus == 0) {
@@ -836,15 +747,6 @@ int field_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live
         if (pin == 1) small = false;
         if (pin == 2) small = true;
     }
-    a.stagger_cycles = 0; a.stagger_lo = a.stagger_hi = 0; a.pp_soft = 0;
-    if (!small) {
-        static int stag = -1;
-        if (stag < 0) {
-            const char *e = getenv("SDN_FIELD_STAGGER_CYCLES");
-            stag = e ? atoi(e) : 0;
-        }
-        a.stagger_cycles = (uint32_t)stag; a.stagger_lo = (uint32_t)cus; a.stagger_hi = 2u * (uint32_t)cus;
-    }
     const int layout = table_layout(offsets_host);
     // persistent ping-pong form (field_pp.inc): one 16-wave workgroup per CU walking tile pairs, for launches of at least two rounds of
     // the CUs (SDN_FIELD_PP=0 keeps every launch on the one-tile-per-workgroup kernels: measurements only)
@@ -852,21 +754,9 @@ int field_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live
         const char *e = getenv("SDN_FIELD_PP");
         g_field_pp = e ? atoi(e) : 1;
     }
-    static int pp_min_tiles_per_cu = -1;      // launches of at least this many 256-point tiles per CU take the persistent kernel
-    if (pp_min_tiles_per_cu < 0) {
-        const char *e = getenv("SDN_FIELD_PP_MIN_TILES");
-        pp_min_tiles_per_cu = e ? atoi(e) : 4;
-    }
-    if (g_field_pp && layout == kLayoutQuad && busy >= (uint32_t)pp_min_tiles_per_cu * (uint32_t)cus && a.n_frames <= kPPMaxFrames && M < (1u << 28)) {
+    if (g_field_pp && layout == kLayoutQuad && busy >= kPPMinTilesPerCU * (uint32_t)cus && a.n_frames <= kPPMaxFrames && M < (1u << 28)) {
         const uint32_t pairs = sdn_div_up(M, kPPTile);     // (tiles: the unit the kernel deals out)
-        // (SDN_FIELD_PP_CUS: workgroups of the persistent launch, default one per CU -- fewer leave CUs to the other frames' small kernels
-        //  of a pipelined stream, which cannot share a CU with a 16-wave, 156-KiB workgroup: a measurement knob)
-        static int env_cus = -1;
-        if (env_cus < 0) {
-            const char *e = getenv("SDN_FIELD_PP_CUS");
-            env_cus = e ? atoi(e) : 0;
-        }
-        int pp_cus = env_cus > 0 ? env_cus : (g_field_pp_wgs > 0 ? g_field_pp_wgs : cus);
+        int pp_cus = g_field_pp_wgs > 0 ? g_field_pp_wgs : cus;
         if (pp_cus > cus) pp_cus = cus;
         // The launch covers every CU; the kernel, which knows the live count, keeps G of the workgroups (the others leave at once):
         // the fewest that finish in as many rounds as `pp_cus` would need -- or, when one workgroup per CU saves a whole round over
@@ -909,7 +799,7 @@ int field_cells_f16(const int32_t *cells, const uint32_t *cell_count, uint32_t n
     a.inv_2bound = exact_reciprocal(2 * bound);
     a.slot_frame = nullptr;
     a.cell_noise = noise; a.cell_seed = seed;
-    a.stagger_cycles = 0; a.stagger_lo = a.stagger_hi = 0; a.n_frames = 1; a.pp_soft = 0;
+    a.n_frames = 1; a.pp_soft = 0;
     const float half_grid = cas_bound / (float)grid_size;
     a.cell_inv = 1.0f / (float)(grid_size - 1); a.cell_span = cas_bound - half_grid; a.cell_half = half_grid;
     const uint32_t wgs = sdn_div_up(n, (uint32_t)kPointsPerWG);

@@ -523,19 +523,9 @@ int sdn_grid_encode_forward_quad_f16(const float *inputs, const void *quad_table
         q.offset_q[l] = (uint32_t)ref_offsets_host[l] + 2u * l;
         q.hsize[l] = hs; q.s1[l] = st3[1]; q.s2[l] = st3[2]; q.scale[l] = scale;
     }
-    static int lv = 0;            // levels per lane: 4 (SDN_GRID_QUAD_LEVELS = 1 | 2 | 4 | 8 | 16 for measurements)
-    if (lv == 0) { const char *e = getenv("SDN_GRID_QUAD_LEVELS"); lv = e ? atoi(e) : 4; }
-    const dim3 b256(256);
-    hipStream_t st = (hipStream_t)stream;
-    const uint4 *qt = (const uint4 *)quad_table;
-    __half *o = (__half *)outputs;
-    switch (lv) {
-        case 1: hipLaunchKernelGGL(k_grid_fwd_quad<1>, dim3(sdn_div_up(B, 256u), 16), b256, 0, st, inputs, qt, o, B, q); break;
-        case 2: hipLaunchKernelGGL(k_grid_fwd_quad<2>, dim3(sdn_div_up(B, 256u), 8), b256, 0, st, inputs, qt, o, B, q); break;
-        case 8: hipLaunchKernelGGL(k_grid_fwd_quad<8>, dim3(sdn_div_up(B, 256u), 2), b256, 0, st, inputs, qt, o, B, q); break;
-        case 16: hipLaunchKernelGGL(k_grid_fwd_quad<16>, dim3(sdn_div_up(B, 256u), 1), b256, 0, st, inputs, qt, o, B, q); break;
-        default: hipLaunchKernelGGL(k_grid_fwd_quad<4>, dim3(sdn_div_up(B, 256u), 4), b256, 0, st, inputs, qt, o, B, q); break;
-    }
+    constexpr int kLevelsPerLane = 4;   // measured against 1, 2, 8 and 16 (profiles/r04_grid_quad_forward.txt)
+    hipLaunchKernelGGL(k_grid_fwd_quad<kLevelsPerLane>, dim3(sdn_div_up(B, 256u), 16 / kLevelsPerLane), dim3(256), 0, (hipStream_t)stream, inputs,
+                       (const uint4 *)quad_table, (__half *)outputs, B, q);
     return sdn_launch_status();
 }
 

@@ -168,23 +168,13 @@ int sdn_render_step_f16_ev(const SdnRenderCtx *c, uint32_t bound_alive, void *ev
 namespace {
 
 constexpr uint32_t kRecompactMin = 8192;   // below this many alive rays a launch is latency-bound whatever its list looks like
-bool recompact_enabled() {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("SDN_RECOMPACT"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
 // Re-compact when at most this percentage of the frozen list is still alive.  Measured (profiles/r03_recompaction.txt): a long list
 // (a group of 4 full frames freezes ~320 K entries) wants it on nearly every iteration -- 0.431 ms per frame at 95-100 % against 0.459 at
 // 50 % and 0.490 without; a short one (one frame, or 8 shards of a frame: ~80 K entries) is best left alone until half of it is dead
 // (0.487 / 0.0694 at 50 % against 0.50-0.52 / 0.072-0.076 at 95 %): the four extra launches of a compacting iteration are latency on
 // that loop, the waves it saves are proportional to the list.  The cut sits above the longest list one 640 000-ray frame can freeze
-// (N / 8 = 80 000).  SDN_RECOMPACT_PCT / SDN_RECOMPACT_MIN override (measurements).
-uint32_t recompact_pct(uint32_t list_len) {
-    static int v = -2;
-    if (v == -2) { const char *e = getenv("SDN_RECOMPACT_PCT"); v = e ? atoi(e) : -1; }
-    return v >= 0 ? (uint32_t)v : (list_len > 81920u ? 95u : 50u);
-}
-uint32_t recompact_min() { static int v = -1; if (v < 0) { const char *e = getenv("SDN_RECOMPACT_MIN"); v = e ? atoi(e) : (int)kRecompactMin; } return (uint32_t)v; }
+// (N / 8 = 80 000).
+uint32_t recompact_pct(uint32_t list_len) { return list_len > 81920u ? 95u : 50u; }
 constexpr int kDriverTimeoutSeconds = 20;   // no iteration of any frame in flight completes for this long: SDN_E_TIMEOUT
 
 // One ray group's loop as a two-phase state machine, so that one host thread can drive several groups round-robin.
@@ -333,7 +323,7 @@ struct FrameRun {
                     steady = true;
                     list_bound = bound;
                 }
-            } else if (recompact_enabled() && (uint64_t)n_prev * 100u <= (uint64_t)list_bound * recompact_pct(list_bound) && (uint32_t)n_prev >= recompact_min()) {
+            } else if ((uint64_t)n_prev * 100u <= (uint64_t)list_bound * recompact_pct(list_bound) && (uint32_t)n_prev >= kRecompactMin) {
                 recompact = true;     // the iteration enqueued next ends with the compaction
             }
         }
