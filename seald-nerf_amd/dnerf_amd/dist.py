@@ -166,8 +166,12 @@ class GradSync:
 
     def broadcast_parameters(self, src=0):
         """Replicas start equal (the reference has no DP; this is what DistributedDataParallel does at construction)."""
-        for p in self.table + self.rest:
-            self.dist.broadcast(p.data, src, group=self.group)
+        params = self.table + self.rest
+        for p in params:
+            self.dist.broadcast(p.detach(), src, group=self.group)
+        # the collective writes behind autograd's back: move the version counters, or what is cached on them (NeRFNetwork's
+        # fused-dispatch weights, the grid encoder's QUAD copy of the table) keeps this replica's old values
+        torch.autograd.graph.increment_version(params)
 
     def _reduce(self, t, async_op=False):
         if t.is_cuda and self.dist.get_backend(self.group) == "gloo":  # one-GPU rehearsal: gloo moves host memory

@@ -148,6 +148,7 @@ class FusedField:
     @torch.no_grad()
     def load_table(self, embeddings):
         """(Re)fills the kernel's fp16 table from the network's embeddings [rows, 2] (float32 or float16, reference layout)."""
+        sdn_backend.await_pending_write(self.model.encoder.embeddings)     # (a table pass that may still run on another stream)
         if self.layout == "quad":
             emb = embeddings.detach()
             if emb.dtype not in (torch.float32, torch.float16):
@@ -266,6 +267,7 @@ class DensityGridUpdater:
     def refresh(self):
         """Re-pack the (trained) weights and the fp16 table; call after optimizer steps."""
         f, enc = self.field, self.model.encoder
+        sdn_backend.await_pending_write(enc.embeddings)     # (the fp32 queries read the table in place)
         if self.fp32:
             f.refresh()
             return

@@ -21,6 +21,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import sdn_backend
+
 from freqencoder import FreqEncoder
 from gridencoder import GridEncoder
 from shencoder import SHEncoder
@@ -185,6 +187,7 @@ class NeRFNetwork(NeRFRenderer):
     def _forward_fused32(self, x, d, t):
         """The fp32 network in one launch: sigma [M], rgb [M,3], deform [M,3] (zeros on the canonical frame), all float32, within 1e-4 of
         the op-by-op evaluation (tests/test_gpu_field_f32.py)."""
+        sdn_backend.await_pending_write(self.encoder.embeddings)     # (read in place below: a table pass still running elsewhere)
         epoch = self._parameter_epoch()
         cache = self.__dict__.get("_fused_cache32")
         if cache is None or cache[0] != epoch[1:] or cache[2][0] != epoch[0][0]:

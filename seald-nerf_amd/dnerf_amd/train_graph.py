@@ -47,6 +47,10 @@ class GraphedTrainStep:
         self.time = torch.full((1, 1), 0.5, dtype=f32, device=device)
         self.graph, self.graph_opt, self.loss, self.warmup, self.grad_sync = None, None, None, warmup, grad_sync
         self._loaded, self._budget, self.captures = False, None, 0
+        # what the replayed optimizer writes in place: torch sees none of a replay's writes, so the version counters are moved after
+        # every step -- what is derived from the parameters (NeRFNetwork's fused-dispatch caches, the grid encoder's QUAD copy of the
+        # table) is then rebuilt.  (A step that GradScaler skips moves them too: that costs a rebuild, nothing else.)
+        self._written = [p for g in optimizer.param_groups for p in g["params"]]
 
     def _step(self):
         with torch.autocast("cuda", dtype=torch.float16, enabled=self.scaler.is_enabled()):
@@ -164,6 +168,7 @@ class GraphedTrainStep:
         if self.graph_opt is not None:
             self.grad_sync.reduce_all()                # RCCL all-reduces of the gradients the backward graph left in place
             self.graph_opt.replay()
+        torch.autograd.graph.increment_version(self._written)
         slot = m.local_step % 16
         if slot != self._slot:
             m.step_counter[slot].copy_(m.step_counter[self._slot])

@@ -45,7 +45,9 @@ class NativeTrainStep:
         overlap_table_update: the optimizer's pass over the embedding table (366 MB of traffic, most of the pass) runs on a second
         stream beside the NEXT step's deformation-MLP forward, which does not read the table (~35 us of a 0.27 ms step).  The next
         step / `refresh()` / `flush()` order the caller's stream behind it; code that reads or writes `encoder.embeddings`, its Adam
-        moments or its EMA shadow on its own right after a step must call `flush()` first (a device-wide synchronize also does).
+        moments or its EMA shadow on its own right after a step must call `flush()` first (a device-wide synchronize also does).  This
+        package's own readers of the table -- the grid encoder, NeRFNetwork's fused dispatch, `FusedField.load_table`, the density
+        update -- do so themselves (`sdn_backend.await_pending_write`).
         grad_sync: a `dnerf_amd.dist.GradSync` for data-parallel training -- every rank runs forward + backward on its own batch, the
         fp16 gradient buffers of the step (24 MB table gradient + one 250 KB block with every MLP's) are all-reduced over RCCL, and
         the optimizer pass divides by the world size on top of the loss scale."""
@@ -206,6 +208,10 @@ class NativeTrainStep:
         no-op otherwise.  Call it before touching `encoder.embeddings`, its optimizer state or its EMA shadow outside the step."""
         if self._table_side is not None and self._rec is not None:
             _sdn.check(_sdn.lib.sdn_train_flush(ctypes.byref(self._rec), _sdn.stream()), "train_flush")
+
+    def pending(self):
+        """May the table pass of the last step still be running on the second stream (overlap_table_update)?"""
+        return self._table_side is not None and self._rec is not None and not self._table_side[2].query()
 
     def invalidate_cull_grids(self):
         """Forget the cached skip grids (the occupancy bitfield was rewritten by something this object cannot see)."""
@@ -389,6 +395,9 @@ class NativeTrainStep:
         m.local_step += 1
         if not grads_only:
             torch.autograd.graph.increment_version(self._written)
+            if self._table_side is not None:
+                # the table's pass is still running on the second stream: its readers outside the step order behind it (sdn_backend)
+                _sdn.set_pending_write(self.params[0], self)
             self.step_count += 1
             self.ema_updates += 1
         return self.loss

@@ -189,6 +189,7 @@ def grid_encode(inputs, embeddings, offsets, per_level_scale, base_resolution, c
     """grid.py:27-93 (`grid_encode = _grid_encode.apply`).  A call that can need no gradient -- grad mode off, or neither the inputs nor the
     table require one -- under fp16 autocast takes the QUAD-copy forward when the geometry has one; everything else is the autograd
     Function as before."""
+    _sdn.await_pending_write(embeddings)     # (an optimizer pass over the table that may still run on another stream)
     if (torch.is_autocast_enabled("cuda") and not calc_grad_inputs
             and not (torch.is_grad_enabled() and (inputs.requires_grad or embeddings.requires_grad))):
         require_device()

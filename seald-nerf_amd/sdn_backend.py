@@ -6,6 +6,7 @@ called without a HIP device (or with a tensor that is not on one) it raises.
 """
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -246,6 +247,32 @@ def stream():
     if _raw_stream is not None:
         return _raw_stream(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+# Writes into model state that may still be running on a stream of their own when the call that enqueued them returns: the
+# optimizer's pass over `encoder.embeddings` of NativeTrainStep(overlap_table_update=True) has moved the table's version counter
+# already, so a reader that rebuilds a cached copy (or reads the table in place) on torch's current stream must first be ordered behind
+# it.  The writer registers itself against the tensor; the table's readers outside the step call `await_pending_write` before they read.
+_PENDING_WRITES = {}
+
+
+def set_pending_write(t, writer):
+    """`writer.pending()`: may the write into `t` still be running?  `writer.flush()`: order torch's current stream behind it."""
+    _PENDING_WRITES[id(t)] = (weakref.ref(t), weakref.ref(writer))
+
+
+def await_pending_write(t):
+    """Orders torch's current stream behind a registered write into `t` that may still be running; forgets it once it has finished."""
+    if not _PENDING_WRITES:
+        return
+    hit = _PENDING_WRITES.get(id(t))
+    if hit is None or hit[0]() is not t:
+        return
+    writer = hit[1]()
+    if writer is None or not writer.pending():
+        del _PENDING_WRITES[id(t)]
+        return
+    writer.flush()
 
 
 def dtype_id(dt):

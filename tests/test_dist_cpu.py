@@ -174,6 +174,36 @@ def test_data_parallel_gradient_exchange_gloo(tmp_path):
     assert all(bool(np.load(tmp_path / f"dp_{r}.npy")[0]) for r in range(world))
 
 
+def _broadcast_worker(rank, world, port, out_dir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from dnerf_amd.dist import GradSync
+        torch.manual_seed(100 + rank)                      # replicas start DIFFERENT
+        model = _ToyField()
+        torch.nn.init.normal_(model.encoder.embeddings)
+        versions = [p._version for p in model.parameters()]
+        GradSync(model).broadcast_parameters()
+        flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        parts = [torch.empty_like(flat) for _ in range(world)]
+        dist.all_gather(parts, flat)
+        moved = [p._version > v for p, v in zip(model.parameters(), versions)]
+        np.save(os.path.join(out_dir, f"bc_{rank}.npy"), np.array([all(torch.equal(parts[0], q) for q in parts)] + moved))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_broadcast_parameters_moves_version_counters(tmp_path):
+    """The broadcast writes every replica's parameters in place; what is cached on a parameter's version counter (the fused
+    dispatch's packed weights, the grid encoder's QUAD copy of the table) must see it, so every counter moves."""
+    world = 2
+    mp.spawn(_broadcast_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    for r in range(world):
+        res = np.load(tmp_path / f"bc_{r}.npy")
+        assert res[0] and res[1:].all(), (r, res)
+
+
 def _hand_on_worker(rank, world, port, H, W, n_loops, out_dir):
     """One rank of a ray-sharded job whose loops finish OUT OF ORDER (4 in flight, as the pipelined frame driver keeps them): a fake
     driver thread publishes loop completions in a per-rank shuffled order, `InOrderHandOn` runs the per-loop gather from its helper
