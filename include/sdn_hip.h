@@ -625,6 +625,17 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream);
 /* Makes `stream` wait for the table pass a previous step left on table_stream (no-op without one). */
 int sdn_train_flush(const SdnTrainStep *s, void *stream);
 
+/* The same step in fp32 (the reference without `-O`: fp32 network, disabled GradScaler): fp32 MLPs on v_mfma_f32_32x32x2_f32, the grid
+ * encoder on the fp32 table in place, fp32 gradients in the workspace at the g_* offsets of sdn_train_layout_f32 (same flat, padded
+ * shapes as the fp16 step, 4-byte elements), Adam on the unscaled gradients with no non-finite check and no skip.  The record is the
+ * fp16 step's; loss_scale, growth_tracker and the scaler fields are not read.  Supported: mode 0 / 1, phases 0 / 1 / 2, deform_frozen,
+ * det_scratch (fp32 fixed point), params[i].ema.  Refused (SDN_E_BADARG): mode 2 and table_stream (data parallelism, the overlapped
+ * table pass).  sdn_train_layout_f32 fills the same record: w_* are 0 (no parameter copies exist), found_inf stays 0. */
+int sdn_train_layout_f32(uint32_t N, uint32_t M, uint32_t max_steps, const int32_t *grid_offsets, SdnTrainLayout *out);
+/* Clears the fp32 table-gradient accumulator (call once before the first step, as sdn_train_refresh for the fp16 step). */
+int sdn_train_refresh_f32(const SdnTrainStep *s, void *stream);
+int sdn_train_step_f32(const SdnTrainStep *s, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

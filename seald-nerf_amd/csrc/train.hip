@@ -910,3 +910,820 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
 }
 
 }  // extern "C"
+
+// =====================================================================================================================================
+// The training step in fp32 (the reference WITHOUT `-O`: the network in float32, the disabled GradScaler of nerf/utils.py:395):
+// sdn_train_step_f32.  The same phases, modes and workspace contract as sdn_train_step_f16; what differs:
+//   * every product and sum is fp32.  The three MLP chains run on v_mfma_f32_32x32x2_f32 (one wave = 32 samples, the sample on the
+//     lane): accumulator register v of output tile mt IS the B operand of the next layer for the k-pair (row, row + 4), row =
+//     32 mt + 8 (v / 4) + v % 4 -- the k-order is baked into the weight packing (k_f32_pack), as in field_f32.hip.  The backward chain
+//     is the same kernel shape on the transposed packing, the ReLU' mask read from the stored activations.  All 13 weight gradients
+//     are one split-K MFMA launch over 512-sample chunks plus one fixed-order reduction (deterministic).
+//   * the grid encoder runs on the fp32 table IN PLACE (no copy) and accumulates an fp32 table gradient;
+//   * the optimizer is Adam on the unscaled gradients: no loss scale, no non-finite check, no skip (the disabled scaler does neither);
+//     there are no copies to write, the pass clears the fp32 table gradient.
+// Launches of a full step: 5 to march (as fp16), pack, encode, 3 forward chains, x + deform, grid forward, compositing forward, loss,
+// compositing backward, 2 backward chains (colour, sigma), dh, grid backward, deformation gradient row, deformation backward chain,
+// dW + reduction, prologue, Adam.
+// =====================================================================================================================================
+namespace {
+
+typedef float f32x16v __attribute__((ext_vector_type(16)));
+constexpr uint32_t kDwChunk = 512;                      // samples per split-K chunk of the weight gradients
+constexpr uint32_t kDefIn32 = 80;                       // 76 frequency features padded to a multiple of 4 k-pairs
+
+__device__ __forceinline__ f32x16v mfma32(float a, float b, f32x16v c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ float relu32(float x) { return x > 0.0f ? x : 0.0f; }
+
+// ---- weight packing --------------------------------------------------------------------------------------------------------------
+// A product Y[rows] = A[rows, K] x[K] on the matrix cores: packed[((t * S/4 + q) * 64 + lane) * 4 + j] = A[32 t + lane % 32][k(4 q + j,
+// lane / 32)].  k(s, h) = 2 s + h when x is loaded from a row-major buffer ("row" order), or 32 (s / 16) + 8 ((s % 16) / 4) + 4 h + s % 4
+// when x is the previous layer's accumulator ("acc" order).  A is a layer's weight W (forward) or its transpose (backward); W[r][c] of
+// the flat layout reads the parameter with the colour MLP's log-density column (c == split) structurally zero.
+struct Pack32 {
+    const float *w;              // parameter [rows_w, cols_w]
+    float *out;
+    uint32_t rows_w, cols_w, split;   // split: flat column that is zero (columns behind it read cols - 1), or 0xFFFFFFFF
+    uint32_t tiles, steps, transpose, acc_order, begin;   // begin: first thread of this job
+};
+struct Pack32Args { Pack32 job[30]; uint32_t n; };
+
+__device__ __forceinline__ float flat_w(const Pack32 &J, uint32_t r, uint32_t c) {
+    if (r >= J.rows_w) return 0.0f;
+    if (J.split != 0xFFFFFFFFu) {
+        if (c == J.split) return 0.0f;
+        if (c > J.split) c -= 1;
+    }
+    return c < J.cols_w ? J.w[(size_t)r * J.cols_w + c] : 0.0f;
+}
+
+__global__ void __launch_bounds__(256) k_f32_pack(Pack32Args A) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t s = 0;
+    for (uint32_t k = 1; k < A.n; k++) s = t >= A.job[k].begin ? k : s;
+    const Pack32 &J = A.job[s];
+    const uint32_t i = t - J.begin;
+    if (i >= J.tiles * J.steps * 64u) return;
+    const uint32_t j = i & 3u, lane = (i >> 2) & 63u, q = (i >> 8) % (J.steps / 4u), tile = (i >> 8) / (J.steps / 4u);
+    const uint32_t step = 4u * q + j, h = lane >> 5, r = 32u * tile + (lane & 31u);
+    const uint32_t k = J.acc_order ? 32u * (step >> 4) + 8u * ((step & 15u) >> 2) + 4u * h + (step & 3u) : 2u * step + h;
+    J.out[i] = J.transpose ? flat_w(J, k, r) : flat_w(J, r, k);
+}
+
+// one layer: STEPS k-steps of B operands (registers) against packed A operands, MT output tiles
+template <uint32_t STEPS, uint32_t MT>
+__device__ __forceinline__ void layer32(const float *__restrict__ pk, const float (&b)[STEPS], f32x16v (&acc)[MT], uint32_t lane) {
+    #pragma unroll
+    for (uint32_t mt = 0; mt < MT; mt++) acc[mt] = f32x16v{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    #pragma unroll
+    for (uint32_t q = 0; q < STEPS / 4; q++) {
+        float4 a[MT];
+        #pragma unroll
+        for (uint32_t mt = 0; mt < MT; mt++) a[mt] = reinterpret_cast<const float4 *>(pk)[((size_t)mt * (STEPS / 4) + q) * 64 + lane];
+        #pragma unroll
+        for (uint32_t mt = 0; mt < MT; mt++) {
+            acc[mt] = mfma32(a[mt].x, b[4 * q + 0], acc[mt]);
+            acc[mt] = mfma32(a[mt].y, b[4 * q + 1], acc[mt]);
+            acc[mt] = mfma32(a[mt].z, b[4 * q + 2], acc[mt]);
+            acc[mt] = mfma32(a[mt].w, b[4 * q + 3], acc[mt]);
+        }
+    }
+}
+
+// B operands of a row-major [*, LD] input row (k-step s, half h: element 2 s + h); 16-byte loads
+template <uint32_t LD>
+__device__ __forceinline__ void load_row_b(const float *__restrict__ row, bool live, uint32_t h, float (&b)[LD / 2]) {
+    #pragma unroll
+    for (uint32_t j = 0; j < LD / 4; j++) {
+        const float4 v = live ? reinterpret_cast<const float4 *>(row)[j] : float4{0, 0, 0, 0};
+        b[2 * j] = h ? v.y : v.x;
+        b[2 * j + 1] = h ? v.w : v.z;
+    }
+}
+
+// the 16 rows this lane holds of tile mt (rows 32 mt + 8 q + 4 h + 0..3) <-> a row-major [*, ld] row
+template <uint32_t MT>
+__device__ __forceinline__ void store_tiles(float *__restrict__ row, const f32x16v (&acc)[MT], uint32_t h) {
+    #pragma unroll
+    for (uint32_t mt = 0; mt < MT; mt++)
+        #pragma unroll
+        for (uint32_t q = 0; q < 4; q++)
+            *reinterpret_cast<float4 *>(row + 32 * mt + 8 * q + 4 * h) = float4{acc[mt][4 * q], acc[mt][4 * q + 1], acc[mt][4 * q + 2], acc[mt][4 * q + 3]};
+}
+
+// ---- forward chain: X -> L hidden layers of width 32 MT (ReLU) -> 16 outputs (rows >= the real output count are zero) --------------
+// X is row-major [M, IN] or, with LEVEL_MAJOR, the grid encoder's [IN / 2][M][2].  Hidden activations (after the ReLU) are kept
+// row-major [L][M][32 MT] for the backward chain and the weight gradients; outputs row-major [M, 16].
+template <uint32_t IN, uint32_t MT, uint32_t L, bool LEVEL_MAJOR>
+__global__ void __launch_bounds__(64) k_f32_chain_fwd(const float *__restrict__ X, const float *__restrict__ pk, uint32_t M, float *__restrict__ hidden,
+                                                      float *__restrict__ out) {
+    constexpr uint32_t W = 32 * MT, S = 16 * MT;
+    const uint32_t lane = threadIdx.x, n = lane & 31u, h = lane >> 5;
+    const uint32_t b_raw = blockIdx.x * 32 + n;
+    const bool live = b_raw < M;
+    const uint32_t b = live ? b_raw : M - 1;
+    f32x16v acc[MT];
+    {
+        float bin[IN / 2];
+        if constexpr (LEVEL_MAJOR) {
+            #pragma unroll
+            for (uint32_t s = 0; s < IN / 2; s++) bin[s] = live ? X[((size_t)s * M + b) * 2 + h] : 0.0f;
+        } else {
+            load_row_b<IN>(X + (size_t)b * IN, live, h, bin);
+        }
+        layer32<IN / 2, MT>(pk, bin, acc, lane);
+        pk += (size_t)MT * (IN / 2) * 64;
+    }
+    for (uint32_t l = 0; l < L; l++) {
+        float bh[S];
+        #pragma unroll
+        for (uint32_t mt = 0; mt < MT; mt++)
+            #pragma unroll
+            for (uint32_t v = 0; v < 16; v++) { const float r = relu32(acc[mt][v]); bh[16 * mt + v] = r; acc[mt][v] = r; }
+        if (live) store_tiles<MT>(hidden + ((size_t)l * M + b) * W, acc, h);
+        if (l + 1 < L) {
+            layer32<S, MT>(pk, bh, acc, lane);
+            pk += (size_t)MT * S * 64;
+        } else {
+            f32x16v o[1];
+            layer32<S, 1>(pk, bh, o, lane);
+            if (live) {
+                float *row = out + (size_t)b * 16;
+                *reinterpret_cast<float4 *>(row + 4 * h) = float4{o[0][0], o[0][1], o[0][2], o[0][3]};
+                *reinterpret_cast<float4 *>(row + 8 + 4 * h) = float4{o[0][4], o[0][5], o[0][6], o[0][7]};
+            }
+        }
+    }
+}
+
+// ---- backward chain: dY [M, 16] -> G_l = (W_{l+1}^T G_{l+1}) * relu'(h_l) for l = L-1 .. 0 (row-major [L][M][32 MT]) -> optionally
+// dX = W_0^T G_0, DXT tiles of 32 input features, row-major [M, 32 DXT] or (LEVEL_MAJOR) the grid encoder's [32 DXT / 2][M][2]
+template <uint32_t MT, uint32_t L, uint32_t DXT, bool LEVEL_MAJOR>
+__global__ void __launch_bounds__(64) k_f32_chain_bwd(const float *__restrict__ dY, const float *__restrict__ pk, const float *__restrict__ hidden, uint32_t M,
+                                                      float *__restrict__ G, float *__restrict__ dX) {
+    constexpr uint32_t W = 32 * MT, S = 16 * MT;
+    const uint32_t lane = threadIdx.x, n = lane & 31u, h = lane >> 5;
+    const uint32_t b_raw = blockIdx.x * 32 + n;
+    const bool live = b_raw < M;
+    const uint32_t b = live ? b_raw : M - 1;
+    f32x16v acc[MT];
+    {
+        float bin[8];
+        load_row_b<16>(dY + (size_t)b * 16, live, h, bin);
+        layer32<8, MT>(pk, bin, acc, lane);
+        pk += (size_t)MT * 8 * 64;
+    }
+    for (int l = (int)L - 1; l >= 0; l--) {
+        const float *act = hidden + ((size_t)l * M + b) * W;
+        float bh[S];
+        #pragma unroll
+        for (uint32_t mt = 0; mt < MT; mt++)
+            #pragma unroll
+            for (uint32_t q = 0; q < 4; q++) {
+                const float4 a = live ? *reinterpret_cast<const float4 *>(act + 32 * mt + 8 * q + 4 * h) : float4{0, 0, 0, 0};
+                const float av[4] = {a.x, a.y, a.z, a.w};
+                #pragma unroll
+                for (uint32_t e = 0; e < 4; e++) {
+                    const float g = av[e] > 0.0f ? acc[mt][4 * q + e] : 0.0f;
+                    acc[mt][4 * q + e] = g;
+                    bh[16 * mt + 4 * q + e] = g;
+                }
+            }
+        if (live) store_tiles<MT>(G + ((size_t)l * M + b) * W, acc, h);
+        if (l > 0) {
+            layer32<S, MT>(pk, bh, acc, lane);
+            pk += (size_t)MT * S * 64;
+        } else if constexpr (DXT > 0) {
+            f32x16v d[DXT];
+            layer32<S, DXT>(pk, bh, d, lane);
+            if (live) {
+                if constexpr (LEVEL_MAJOR) {
+                    #pragma unroll
+                    for (uint32_t t = 0; t < DXT; t++)
+                        #pragma unroll
+                        for (uint32_t q = 0; q < 4; q++) {
+                            const uint32_t f = 32 * t + 8 * q + 4 * h;      // features f .. f + 3 = levels f / 2, f / 2 + 1
+                            *reinterpret_cast<float2 *>(dX + ((size_t)(f / 2) * M + b) * 2) = float2{d[t][4 * q], d[t][4 * q + 1]};
+                            *reinterpret_cast<float2 *>(dX + ((size_t)(f / 2 + 1) * M + b) * 2) = float2{d[t][4 * q + 2], d[t][4 * q + 3]};
+                        }
+                } else {
+                    store_tiles<DXT>(dX + (size_t)b * 32 * DXT, d, h);
+                }
+            }
+        }
+    }
+}
+
+// ---- weight gradients: dW[R, C] = sum_b G[b][r] X[b][c], one wave per (job, 32 x 32 tile, 512-sample chunk), partial sums per chunk,
+// then one reduction over the chunks in a fixed order
+struct Dw32 {
+    const float *G, *X;
+    float *out;
+    uint32_t ldg, ldx, R, C, x_level_major;
+    uint32_t tiles_c, tile_begin, out_begin;       // tile_begin: first tile of this job; out_begin: offset in a chunk's partial row
+};
+struct Dw32Args { Dw32 job[13]; uint32_t n, tiles, total; };
+
+__global__ void __launch_bounds__(64) k_f32_dw(Dw32Args A, uint32_t M, float *__restrict__ partial) {
+    const uint32_t tile = blockIdx.x, chunk = blockIdx.y;
+    uint32_t s = 0;
+    for (uint32_t k = 1; k < A.n; k++) s = tile >= A.job[k].tile_begin ? k : s;
+    const Dw32 &J = A.job[s];
+    const uint32_t lane = threadIdx.x, n = lane & 31u, h = lane >> 5;
+    const uint32_t t = tile - J.tile_begin, tr = t / J.tiles_c, tc = t - tr * J.tiles_c;
+    const uint32_t r = 32 * tr + n, c = 32 * tc + n;
+    const bool r_ok = r < J.R, c_ok = c < J.C;
+    f32x16v acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const uint32_t b0 = chunk * kDwChunk, b1 = min(b0 + kDwChunk, M);
+    for (uint32_t bb = b0; bb < b1; bb += 8) {
+        float a[4], x[4];
+        #pragma unroll
+        for (uint32_t u = 0; u < 4; u++) {
+            const uint32_t b = bb + 2 * u + h;
+            const bool ok = b < b1;
+            a[u] = ok && r_ok ? J.G[(size_t)b * J.ldg + r] : 0.0f;
+            x[u] = !(ok && c_ok) ? 0.0f : J.x_level_major ? J.X[((size_t)(c >> 1) * M + b) * 2 + (c & 1u)] : J.X[(size_t)b * J.ldx + c];
+        }
+        #pragma unroll
+        for (uint32_t u = 0; u < 4; u++) acc = mfma32(a[u], x[u], acc);
+    }
+    float *dst = partial + (size_t)chunk * A.total + J.out_begin;
+    #pragma unroll
+    for (uint32_t v = 0; v < 16; v++) {
+        const uint32_t row = 32 * tr + 8 * (v >> 2) + 4 * h + (v & 3u);
+        if (row < J.R && c_ok) dst[(size_t)row * J.C + c] = acc[v];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_f32_dw_reduce(Dw32Args A, uint32_t chunks, const float *__restrict__ partial) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.total) return;
+    uint32_t s = 0;
+    for (uint32_t k = 1; k < A.n; k++) s = i >= A.job[k].out_begin ? k : s;
+    float sum = 0.0f;
+    for (uint32_t c = 0; c < chunks; c++) sum += partial[(size_t)c * A.total + i];
+    A.job[s].out[i - A.job[s].out_begin] = sum;
+}
+
+// ---- glue -------------------------------------------------------------------------------------------------------------------------
+// freq(x, 10) ++ freq(t, 6) in fp32 (freqencoder.cu:30-58; cosine = the sine shifted by pi / 2), rows of 80 (76 .. 79 zero)
+__global__ void __launch_bounds__(256) k_f32_encode(const float *__restrict__ xyzs, uint32_t M, float time, float *__restrict__ enc) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t b = t >> 4, j = t & 15u;
+    if (b >= M) return;
+    float *row = enc + (size_t)b * kDefIn32;
+    const float half_pi = 3.141592653589793f / 2;
+    if (j < 10) {
+        #pragma unroll
+        for (int d = 0; d < 3; d++) {
+            const float a = scalbnf(xyzs[(size_t)b * 3 + d], (int)j);
+            row[3 + 6 * j + d] = sinf(a + 0.0f);
+            row[6 + 6 * j + d] = sinf(a + half_pi);
+        }
+    } else if (j == 10) {
+        #pragma unroll
+        for (int d = 0; d < 3; d++) row[d] = xyzs[(size_t)b * 3 + d];
+    } else if (j == 11) {
+        row[63] = time;
+        #pragma unroll
+        for (int f = 0; f < 6; f++) {
+            const float a = scalbnf(time, f);
+            row[64 + 2 * f] = sinf(a + 0.0f);
+            row[65 + 2 * f] = sinf(a + half_pi);
+        }
+    } else if (j == 12) {
+        row[76] = 0; row[77] = 0; row[78] = 0; row[79] = 0;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_f32_xdef(const float *__restrict__ xyzs, const float *__restrict__ def_out, uint32_t M, int zero_deform,
+                                                  float bound, float *__restrict__ xdef) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M * 3) return;
+    const uint32_t b = t / 3, d = t - b * 3;
+    const float v = xyzs[t] + (zero_deform ? 0.0f : def_out[(size_t)b * 16 + d]);
+    xdef[t] = (v + bound) / (2 * bound);
+}
+
+// sigma = density_scale * exp(h[0]) (trunc_exp forward, activation.py:5-11); the colour MLP's input row [SH(d, 4) 16 | sigma-MLP output 16]
+__global__ void __launch_bounds__(256) k_f32_sigma_post(const float *__restrict__ hout, const float *__restrict__ dirs, uint32_t M, float density_scale,
+                                                        float *__restrict__ sigmas, float *__restrict__ col_in) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= M) return;
+    float sh[16], u0[1], u1[1], u2[1];
+    sh_eval<4, false>(dirs[(size_t)b * 3], dirs[(size_t)b * 3 + 1], dirs[(size_t)b * 3 + 2], sh, u0, u1, u2);
+    float4 *row = reinterpret_cast<float4 *>(col_in + (size_t)b * kColIn);
+    const float4 *o = reinterpret_cast<const float4 *>(hout + (size_t)b * 16);
+    #pragma unroll
+    for (int j = 0; j < 4; j++) { row[j] = float4{sh[4 * j], sh[4 * j + 1], sh[4 * j + 2], sh[4 * j + 3]}; row[4 + j] = o[j]; }
+    sigmas[b] = density_scale * expf(hout[(size_t)b * 16]);
+}
+
+struct Composite32 {
+    const float *sigmas, *deltas, *col_out, *hout;   // col_out [M,16] pre-sigmoid; hout [M,16] (column 0: log density)
+    const int32_t *rays;
+    const float *bg, *gt;
+    float *weights_sum, *depth, *image, *image_out, *sq_err;
+    float *dcol_out, *dh0;                           // backward: [M,16], [M]
+    uint32_t M, N;
+    float T_thresh, bg_value, density_scale;
+};
+
+__device__ __forceinline__ float sigmoid32(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+__device__ __forceinline__ SampleTerms sample_terms32(const Composite32 &P, uint32_t idx, bool in_ray, float T_carry, float t_carry, uint32_t lane,
+                                                      float &T_next, float &t_next) {
+    SampleTerms s{};
+    float one_minus = 1.0f, d1 = 0.0f;
+    if (in_ray) {
+        s.delta0 = P.deltas[(size_t)idx * 2];
+        d1 = P.deltas[(size_t)idx * 2 + 1];
+        s.alpha = 1.0f - sdn_exp_cr(-P.sigmas[idx] * s.delta0);
+        one_minus = 1.0f - s.alpha;
+        #pragma unroll
+        for (int ch = 0; ch < 3; ch++) s.c[ch] = sigmoid32(P.col_out[(size_t)idx * 16 + ch]);
+    }
+    s.T = T_carry * wave_excl_product(one_minus, lane);
+    s.t = t_carry + wave_incl_sum(d1, lane);
+    s.on = in_ray && s.T >= P.T_thresh;
+    s.weight = s.on ? s.alpha * s.T : 0.0f;
+    T_next = __shfl(s.T * one_minus, 63);
+    t_next = __shfl(s.t, 63);
+    return s;
+}
+
+__global__ void __launch_bounds__(256) k_f32_composite_fwd(Composite32 P) {
+    const uint32_t lane = threadIdx.x & 63u, n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= P.N) return;
+    const uint32_t index = (uint32_t)P.rays[n * 3], offset = (uint32_t)P.rays[n * 3 + 1], count = (uint32_t)P.rays[n * 3 + 2];
+    float ws = 0, d = 0, r = 0, g = 0, b = 0;
+    if (count != 0 && offset + count <= P.M) {
+        float T_carry = 1.0f, t_carry = 0.0f;
+        for (uint32_t c0 = 0; c0 < count && T_carry >= P.T_thresh; c0 += 64) {
+            float T_next, t_next;
+            const SampleTerms s = sample_terms32(P, offset + c0 + lane, c0 + lane < count, T_carry, t_carry, lane, T_next, t_next);
+            ws += s.weight; d += s.weight * s.t;
+            r += s.weight * s.c[0]; g += s.weight * s.c[1]; b += s.weight * s.c[2];
+            T_carry = T_next; t_carry = t_next;
+        }
+        ws = wave_sum(ws); d = wave_sum(d); r = wave_sum(r); g = wave_sum(g); b = wave_sum(b);
+    }
+    if (lane == 0) {
+        P.weights_sum[index] = ws; P.depth[index] = d;
+        const float img[3] = {r, g, b};
+        float sq = 0.0f;
+        #pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            P.image[(size_t)index * 3 + ch] = img[ch];
+            const float bgc = P.bg ? P.bg[(size_t)index * 3 + ch] : P.bg_value;
+            const float pred = img[ch] + (1.0f - ws) * bgc;
+            const float e = pred - P.gt[(size_t)index * 3 + ch];
+            sq += e * e;
+            if (P.image_out) P.image_out[(size_t)index * 3 + ch] = pred;
+        }
+        P.sq_err[index] = sq;
+    }
+}
+
+// raymarching.cu:602-682 in fp32, plus the sigmoid's and trunc_exp's gradients (activation.py:12-17); the loss is unscaled
+__global__ void __launch_bounds__(256) k_f32_composite_bwd(Composite32 P) {
+    const uint32_t lane = threadIdx.x & 63u, n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= P.N) return;
+    const uint32_t index = (uint32_t)P.rays[n * 3], offset = (uint32_t)P.rays[n * 3 + 1], count = (uint32_t)P.rays[n * 3 + 2];
+    if (count == 0 || offset + count > P.M) return;
+    const float ws_final = P.weights_sum[index];
+    const float cg = (1.0f / (float)P.N) / 3.0f;
+    float gi[3], fin[3], gws = 0.0f;
+    #pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        fin[ch] = P.image[(size_t)index * 3 + ch];
+        const float bgc = P.bg ? P.bg[(size_t)index * 3 + ch] : P.bg_value;
+        const float pred = fin[ch] + (1.0f - ws_final) * bgc;
+        gi[ch] = ((pred - P.gt[(size_t)index * 3 + ch]) * 2.0f) * cg;
+        gws -= gi[ch] * bgc;
+    }
+    float T_carry = 1.0f, t_carry = 0.0f, acc_c[3] = {0, 0, 0};
+    for (uint32_t c0 = 0; c0 < count && T_carry >= P.T_thresh; c0 += 64) {
+        float T_next, t_next;
+        const uint32_t idx = offset + c0 + lane;
+        const SampleTerms s = sample_terms32(P, idx, c0 + lane < count, T_carry, t_carry, lane, T_next, t_next);
+        float run[3];
+        #pragma unroll
+        for (int ch = 0; ch < 3; ch++) run[ch] = acc_c[ch] + wave_incl_sum(s.weight * s.c[ch], lane);
+        if (s.on) {
+            const float T_after = s.T * (1.0f - s.alpha);
+            const float g_sigma = s.delta0 * (gi[0] * (T_after * s.c[0] - (fin[0] - run[0])) + gi[1] * (T_after * s.c[1] - (fin[1] - run[1])) +
+                                              gi[2] * (T_after * s.c[2] - (fin[2] - run[2])) + gws * (1.0f - ws_final));
+            float dc[3];
+            #pragma unroll
+            for (int ch = 0; ch < 3; ch++) dc[ch] = ((gi[ch] * s.weight) * (1.0f - s.c[ch])) * s.c[ch];
+            *reinterpret_cast<float4 *>(P.dcol_out + (size_t)idx * 16) = float4{dc[0], dc[1], dc[2], 0.0f};
+            const float x = fminf(fmaxf(P.hout[(size_t)idx * 16], -15.0f), 15.0f);
+            P.dh0[idx] = (g_sigma * P.density_scale) * expf(x);
+        }
+        #pragma unroll
+        for (int ch = 0; ch < 3; ch++) acc_c[ch] = __shfl(run[ch], 63);
+        T_carry = T_next; t_carry = t_next;
+    }
+}
+
+// d(sigma-MLP output) = [trunc_exp gradient | columns 17 .. 31 of the colour MLP's input gradient]
+__global__ void __launch_bounds__(256) k_f32_dh(const float *__restrict__ dh0, const float *__restrict__ dcol_in, uint32_t M, float *__restrict__ dh) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M * 16) return;
+    const uint32_t b = t >> 4, c = t & 15u;
+    dh[t] = c == 0 ? dh0[b] : dcol_in[(size_t)b * kColIn + 16 + c];
+}
+
+// the deformation MLP's output gradient: the grid's input gradient / (2 bound) in columns 0 .. 2 of 16
+__global__ void __launch_bounds__(256) k_f32_deform_grad(const float *__restrict__ dx, uint32_t M, float bound, float *__restrict__ ddef) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= M) return;
+    float4 *row = reinterpret_cast<float4 *>(ddef + (size_t)b * 16);
+    row[0] = float4{dx[(size_t)b * 3] / (2 * bound), dx[(size_t)b * 3 + 1] / (2 * bound), dx[(size_t)b * 3 + 2] / (2 * bound), 0.0f};
+    row[1] = float4{0, 0, 0, 0}; row[2] = float4{0, 0, 0, 0}; row[3] = float4{0, 0, 0, 0};
+}
+
+// ---- optimizer --------------------------------------------------------------------------------------------------------------------
+struct Prologue32 { Hyper *hyper; float *steps; double beta1, beta2, lr_table, lr_net; int deform_active; };
+
+// bias corrections in double, as torch's Adam computes them on the host; no scaler: every step counts
+__global__ void k_f32_prologue(Prologue32 P) {
+    Hyper *h = P.hyper;
+    P.steps[0] += 1.0f;
+    if (P.deform_active) P.steps[1] += 1.0f;
+    for (int g = 0; g < 2; g++) {
+        const double st = (double)P.steps[g] > 0 ? (double)P.steps[g] : 1.0;
+        const double bc1 = 1.0 - pow(P.beta1, st), bc2 = 1.0 - pow(P.beta2, st);
+        h->step_size[0][g] = (float)(P.lr_table / bc1);
+        h->step_size[1][g] = (float)(P.lr_net / bc1);
+        h->bc2_sqrt[g] = (float)sqrt(bc2);
+    }
+}
+
+struct AdamSeg32 {
+    float *p, *m, *v, *ema;
+    float *g;                         // fp32 gradient, element (r, c) at r * ld + c
+    uint32_t n, cols, ld, split;
+    uint32_t lr_idx, group, zero_grad, frozen, blk_begin;
+};
+struct Adam32Args {
+    AdamSeg32 seg[SDN_TRAIN_N_PARAMS];
+    uint32_t nseg;
+    const Hyper *hyper;
+    float one_minus_b1, b2, one_minus_b2, eps, ema_keep;
+};
+
+// torch.optim.Adam (_single_tensor_adam) on the unscaled fp32 gradients, torch_ema's shadow, and the table gradient cleared
+__global__ void __launch_bounds__(256) k_f32_adam(Adam32Args A) {
+    uint32_t s = 0;
+    for (uint32_t k = 1; k < A.nseg; k++) s = blockIdx.x >= A.seg[k].blk_begin ? k : s;
+    const AdamSeg32 &S = A.seg[s];
+    const Hyper &H = *A.hyper;
+    const bool update = !S.frozen;
+    const float step_size = H.step_size[S.lr_idx][S.group], bc2s = H.bc2_sqrt[S.group];
+    const uint32_t first = (blockIdx.x - S.blk_begin) * 1024u;
+    if (S.cols == S.ld && first + 1024u <= S.n && !S.ema && update) {
+        const uint32_t i = first + 4u * threadIdx.x;
+        float4 p = *reinterpret_cast<const float4 *>(S.p + i), m = *reinterpret_cast<const float4 *>(S.m + i), v = *reinterpret_cast<const float4 *>(S.v + i);
+        const float4 g4 = *reinterpret_cast<const float4 *>(S.g + i);
+        float *pp = &p.x, *mm = &m.x, *vv = &v.x;
+        const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
+        #pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const float g = gg[e];
+            mm[e] = mm[e] + A.one_minus_b1 * (g - mm[e]);
+            vv[e] = vv[e] * A.b2 + (A.one_minus_b2 * g) * g;
+            const float denom = sqrtf(vv[e]) / bc2s + A.eps;
+            pp[e] = pp[e] - step_size * (mm[e] / denom);
+        }
+        *reinterpret_cast<float4 *>(S.m + i) = m; *reinterpret_cast<float4 *>(S.v + i) = v; *reinterpret_cast<float4 *>(S.p + i) = p;
+        if (S.zero_grad) *reinterpret_cast<float4 *>(S.g + i) = float4{0, 0, 0, 0};
+        return;
+    }
+    const uint32_t base = first + threadIdx.x;
+    #pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t i = base + 256u * k;
+        if (i >= S.n) break;
+        uint32_t j = i;
+        if (S.cols != S.ld) { const uint32_t r = i / S.cols, c = i - r * S.cols; j = r * S.ld + c + (c >= S.split ? 1u : 0u); }
+        float p = S.p[i];
+        if (update) {
+            const float g = S.g[j];
+            float m = S.m[i], v = S.v[i];
+            m = m + A.one_minus_b1 * (g - m);
+            v = v * A.b2 + (A.one_minus_b2 * g) * g;
+            const float denom = sqrtf(v) / bc2s + A.eps;
+            p = p - step_size * (m / denom);
+            S.m[i] = m; S.v[i] = v; S.p[i] = p;
+        }
+        if (S.zero_grad) S.g[j] = 0.0f;
+        if (S.ema) { const float e = S.ema[i]; S.ema[i] = e - (e - p) * A.ema_keep; }
+    }
+}
+
+// ---- workspace --------------------------------------------------------------------------------------------------------------------
+struct Layout32 {
+    uint64_t total;
+    uint64_t g_table, hyper, pk;
+    uint64_t nears, fars, noises, rays, pts, march, set_stride;
+    uint64_t dcol_out, dh0;
+    uint64_t enc_in, def_hidden, def_out, xdef, grid_out, dy_dx, h1, hout, sigmas, col_in, col_hidden, col_out;
+    uint64_t weights_sum, depth, image, sq_err;
+    uint64_t col_bwd, dcol_in, dh, dh1, denc, dx, ddef, def_bwd;
+    uint64_t g_deform, g_sigma0, g_sigma1, g_color, dw_partial;
+};
+
+// packed floats of one product: tiles x steps x 64
+constexpr uint64_t pk_floats(uint32_t rows, uint32_t steps) { return (uint64_t)((rows + 31u) / 32u) * steps * 64u; }
+// forward chain: first layer (in / 2 steps), L - 1 hidden, last (1 tile); backward chain: last^T (8 steps), L - 1 hidden^T, first^T if dX
+constexpr uint64_t chain_fwd_floats(uint32_t in, uint32_t W, uint32_t L) { return pk_floats(W, in / 2) + (L - 1) * pk_floats(W, W / 2) + pk_floats(16, W / 2); }
+constexpr uint64_t chain_bwd_floats(uint32_t in, uint32_t W, uint32_t L, bool dx) { return pk_floats(W, 8) + (L - 1) * pk_floats(W, W / 2) + (dx ? pk_floats(in, W / 2) : 0); }
+constexpr uint64_t kPkDefF = 0, kPkDefB = kPkDefF + chain_fwd_floats(kDefIn32, kDefW, kDefL);
+constexpr uint64_t kPkSigF = kPkDefB + chain_bwd_floats(kDefIn32, kDefW, kDefL, false);
+constexpr uint64_t kPkSigB = kPkSigF + chain_fwd_floats(kSigIn, kSigW, 1);
+constexpr uint64_t kPkColF = kPkSigB + chain_bwd_floats(kSigIn, kSigW, 1, true);
+constexpr uint64_t kPkColB = kPkColF + chain_fwd_floats(kColIn, kColW, kColL);
+constexpr uint64_t kPkTotal = kPkColB + chain_bwd_floats(kColIn, kColW, kColL, true);
+constexpr uint32_t kDwTotal = kDefFlat + kSigW * kSigIn + kSigOut * kSigW + kColFlat;
+
+Layout32 make_layout32(uint32_t N, uint32_t M, uint32_t max_steps, uint64_t table_entries) {
+    Layout32 L{};
+    uint64_t at = 0;
+    auto take = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 255u) & ~(uint64_t)255u; return o; };
+    const uint64_t m = M, n = N;
+    L.g_table = take(table_entries * 4);
+    L.hyper = take(sizeof(Hyper));
+    L.pk = take(kPkTotal * 4);
+    L.nears = take(n * 4);  L.fars = take(n * 4);  L.noises = take(n * 4);  L.rays = take(n * 12);
+    L.pts = take(m * 32);
+    L.march = take(sdn_march_rays_train_scratch_bytes(N, max_steps));
+    L.set_stride = at - L.nears;
+    at += L.set_stride;
+    L.dcol_out = take(m * 64);  L.dh0 = take(m * 4);              // zero-filled by every step (one fill: dh0 follows dcol_out)
+    L.enc_in = take(m * kDefIn32 * 4);  L.def_hidden = take(m * kDefL * kDefW * 4);  L.def_out = take(m * 64);
+    L.xdef = take(m * 12);  L.grid_out = take(m * kLevels * 8);  L.dy_dx = take(m * kLevels * 24);
+    L.h1 = take(m * kSigW * 4);  L.hout = take(m * kSigOut * 4);  L.sigmas = take(m * 4);
+    L.col_in = take(m * kColIn * 4);  L.col_hidden = take(m * kColL * kColW * 4);  L.col_out = take(m * 64);
+    L.weights_sum = take(n * 4);  L.depth = take(n * 4);  L.image = take(n * 12);  L.sq_err = take(n * 4);
+    L.col_bwd = take(m * kColL * kColW * 4);  L.dcol_in = take(m * kColIn * 4);
+    L.dh = take(m * kSigOut * 4);  L.dh1 = take(m * kSigW * 4);  L.denc = take(m * kLevels * 8);  L.dx = take(m * 12);
+    L.ddef = take(m * 64);  L.def_bwd = take(m * kDefL * kDefW * 4);
+    L.g_deform = take(kDefFlat * 4);  L.g_sigma0 = take(kSigW * kSigIn * 4);  L.g_sigma1 = take(kSigOut * kSigW * 4);  L.g_color = take(kColFlat * 4);
+    L.dw_partial = take((uint64_t)sdn_div_up(M, kDwChunk) * kDwTotal * 4);
+    L.total = at;
+    return L;
+}
+
+// the 13 weight-gradient products (deformation MLP first: the canonical frame launches only the rest)
+uint32_t dw32_jobs(const Layout32 &L, unsigned char *ws, uint32_t M, bool with_deform, Dw32Args &A) {
+    auto F = [&](uint64_t off) { return (float *)(ws + off); };
+    const size_t mw = (size_t)M * kDefW, mc = (size_t)M * kColW;
+    Dw32 j[13];
+    uint32_t n = 0;
+    if (with_deform) {
+        j[n++] = {F(L.def_bwd), F(L.enc_in), F(L.g_deform), kDefW, kDefIn32, kDefW, kDefIn32, 0};
+        for (uint32_t l = 1; l < kDefL; l++)
+            j[n++] = {F(L.def_bwd) + l * mw, F(L.def_hidden) + (l - 1) * mw, F(L.g_deform) + kDefW * kDefIn32 + (l - 1) * kDefW * kDefW, kDefW, kDefW, kDefW, kDefW, 0};
+        j[n++] = {F(L.ddef), F(L.def_hidden) + (kDefL - 1) * mw, F(L.g_deform) + kDefW * kDefIn32 + (kDefL - 1) * kDefW * kDefW, 16, kDefW, 16, kDefW, 0};
+    }
+    j[n++] = {F(L.dh1), F(L.grid_out), F(L.g_sigma0), kSigW, 0, kSigW, kSigIn, 1};
+    j[n++] = {F(L.dh), F(L.h1), F(L.g_sigma1), kSigOut, kSigW, kSigOut, kSigW, 0};
+    j[n++] = {F(L.col_bwd), F(L.col_in), F(L.g_color), kColW, kColIn, kColW, kColIn, 0};
+    j[n++] = {F(L.col_bwd) + mc, F(L.col_hidden), F(L.g_color) + kColW * kColIn, kColW, kColW, kColW, kColW, 0};
+    j[n++] = {F(L.dcol_out), F(L.col_hidden) + mc, F(L.g_color) + kColW * kColIn + kColW * kColW, 16, kColW, 16, kColW, 0};
+    uint32_t tiles = 0, total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        j[i].tiles_c = sdn_div_up(j[i].C, 32u);
+        j[i].tile_begin = tiles;
+        j[i].out_begin = total;
+        tiles += sdn_div_up(j[i].R, 32u) * j[i].tiles_c;
+        total += j[i].R * j[i].C;
+        A.job[i] = j[i];
+    }
+    A.n = n; A.tiles = tiles; A.total = total;
+    return n;
+}
+
+// both directions of the three MLPs from the fp32 parameters (params 1 .. 13), one launch
+void pack32_jobs(const SdnTrainStep *s, const Layout32 &L, unsigned char *ws, Pack32Args &A) {
+    float *pk = (float *)(ws + L.pk);
+    uint32_t n = 0, thr = 0;
+    auto add = [&](uint32_t pi, uint64_t &at, uint32_t out_rows, uint32_t steps, int transpose, int acc, uint32_t rows_w, uint32_t cols_w, uint32_t split) {
+        Pack32 &J = A.job[n++];
+        J.w = s->params[pi].param; J.out = pk + at;
+        J.rows_w = rows_w; J.cols_w = cols_w; J.split = split;
+        J.tiles = sdn_div_up(out_rows, 32u); J.steps = steps; J.transpose = (uint32_t)transpose; J.acc_order = (uint32_t)acc; J.begin = thr;
+        const uint32_t cnt = J.tiles * steps * 64u;
+        thr += sdn_div_up(cnt, 256u) * 256u;                // every job starts on a workgroup boundary
+        at += cnt;
+    };
+    const uint32_t NS = 0xFFFFFFFFu;
+    // deformation: fwd first [128, 80 (76)], hidden [128,128] x 6, last [16 (3), 128]; bwd last^T, hidden^T (7 .. 2), no first^T
+    uint64_t at = kPkDefF;
+    add(1, at, kDefW, kDefIn32 / 2, 0, 0, kDefW, kDefCols, NS);
+    for (uint32_t l = 1; l < kDefL; l++) add(1 + l, at, kDefW, kDefW / 2, 0, 1, kDefW, kDefW, NS);
+    add(8, at, 16, kDefW / 2, 0, 1, 3, kDefW, NS);
+    at = kPkDefB;
+    add(8, at, kDefW, 8, 1, 0, 3, kDefW, NS);
+    for (uint32_t l = kDefL - 1; l >= 1; l--) add(1 + l, at, kDefW, kDefW / 2, 1, 1, kDefW, kDefW, NS);
+    // sigma: fwd [64, 32], [16, 64]; bwd [16, 64]^T, [64, 32]^T
+    at = kPkSigF;
+    add(9, at, kSigW, kSigIn / 2, 0, 0, kSigW, kSigIn, NS);
+    add(10, at, 16, kSigW / 2, 0, 1, kSigOut, kSigW, NS);
+    at = kPkSigB;
+    add(10, at, kSigW, 8, 1, 0, kSigOut, kSigW, NS);
+    add(9, at, kSigIn, kSigW / 2, 1, 1, kSigW, kSigIn, NS);
+    // colour: input [SH 16 | zero column | geo 15]
+    at = kPkColF;
+    add(11, at, kColW, kColIn / 2, 0, 0, kColW, kColCols, 16);
+    add(12, at, kColW, kColW / 2, 0, 1, kColW, kColW, NS);
+    add(13, at, 16, kColW / 2, 0, 1, 3, kColW, NS);
+    at = kPkColB;
+    add(13, at, kColW, 8, 1, 0, 3, kColW, NS);
+    add(12, at, kColW, kColW / 2, 1, 1, kColW, kColW, NS);
+    add(11, at, kColIn, kColW / 2, 1, 1, kColW, kColCols, 16);
+    A.n = n;
+}
+
+uint32_t pack32_threads(const Pack32Args &A) {
+    const Pack32 &J = A.job[A.n - 1];
+    return J.begin + J.tiles * J.steps * 64u;
+}
+
+uint32_t build_segments32(const SdnTrainStep *s, const Layout32 &L, Adam32Args &A) {
+    unsigned char *ws = (unsigned char *)s->workspace;
+    auto F = [&](uint64_t off) { return (float *)(ws + off); };
+    struct Place { uint64_t g; uint32_t off, rows, cols, ld, lr, group; };
+    Place pl[SDN_TRAIN_N_PARAMS];
+    const uint32_t table_n = (uint32_t)s->grid_offsets[kLevels] * 2u;
+    pl[0] = {L.g_table, 0, table_n / 2, 2, 2, 0, 0};
+    pl[1] = {L.g_deform, 0, kDefW, kDefCols, kDefIn32, 1, 1};
+    for (uint32_t i = 1; i < kDefL; i++) pl[1 + i] = {L.g_deform, kDefW * kDefIn32 + (i - 1) * kDefW * kDefW, kDefW, kDefW, kDefW, 1, 1};
+    pl[8] = {L.g_deform, kDefW * kDefIn32 + (kDefL - 1) * kDefW * kDefW, 3, kDefW, kDefW, 1, 1};
+    pl[9] = {L.g_sigma0, 0, kSigW, kSigIn, kSigIn, 1, 0};
+    pl[10] = {L.g_sigma1, 0, kSigOut, kSigW, kSigW, 1, 0};
+    pl[11] = {L.g_color, 0, kColW, kColCols, kColIn, 1, 0};
+    pl[12] = {L.g_color, kColW * kColIn, kColW, kColW, kColW, 1, 0};
+    pl[13] = {L.g_color, kColW * kColIn + kColW * kColW, 3, kColW, kColW, 1, 0};
+    uint32_t blk = 0;
+    for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) {
+        const SdnTrainParam &q = s->params[i];
+        AdamSeg32 &S = A.seg[i];
+        S.p = q.param; S.m = q.exp_avg; S.v = q.exp_avg_sq; S.ema = q.ema;
+        S.g = F(pl[i].g) + pl[i].off;
+        S.n = pl[i].rows * pl[i].cols; S.cols = pl[i].cols; S.ld = pl[i].ld; S.split = i == 11 ? 16u : 0xFFFFFFFFu;
+        S.lr_idx = pl[i].lr; S.group = pl[i].group; S.zero_grad = i == 0; S.frozen = 0; S.blk_begin = blk;
+        blk += sdn_div_up(S.n, 1024u);
+    }
+    A.nseg = SDN_TRAIN_N_PARAMS;
+    return blk;
+}
+
+bool step_ok32(const SdnTrainStep *s) {
+    if (!s || !s->workspace || ((uintptr_t)s->workspace & 255u)) return false;
+    if (s->mode < 0 || s->mode > 1) return false;                                  // no optimizer-only mode (data parallelism)
+    if (s->table_stream || s->table_ready || s->table_done) return false;         // no overlapped table pass
+    if (s->phase < 0 || s->phase > 2) return false;
+    if (s->phase != 2 && (!s->rays_o || !s->rays_d || !s->bitfield || !s->aabb || !s->counter)) return false;
+    if (s->phase != 1 && (!s->target || !s->loss_out)) return false;
+    if (s->N == 0 || s->M == 0 || s->max_steps == 0 || s->bound <= 0 || s->grid_offsets[kLevels] <= 0) return false;
+    for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) if (!s->params[i].param) return false;
+    if (s->mode == 0) {
+        if (!s->adam_steps) return false;
+        for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) {
+            const bool frozen = s->deform_frozen && i >= 1 && i <= (int)kDefL + 1;
+            if (!frozen && (!s->params[i].exp_avg || !s->params[i].exp_avg_sq)) return false;
+        }
+    }
+    const uint64_t expect[SDN_TRAIN_N_PARAMS] = {(uint64_t)s->grid_offsets[kLevels] * 2, kDefW * kDefCols, kDefW * kDefW, kDefW * kDefW, kDefW * kDefW, kDefW * kDefW,
+                                                 kDefW * kDefW, kDefW * kDefW, 3 * kDefW, kSigW * kSigIn, kSigOut * kSigW, kColW * kColCols, kColW * kColW, 3 * kColW};
+    for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) if (s->params[i].n != expect[i]) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdn_train_layout_f32(uint32_t N, uint32_t M, uint32_t max_steps, const int32_t *grid_offsets, SdnTrainLayout *out) {
+    if (!grid_offsets || !out || N == 0 || M == 0 || max_steps == 0 || grid_offsets[kLevels] <= 0) return SDN_E_BADARG;
+    const Layout32 L = make_layout32(N, M, max_steps, (uint64_t)grid_offsets[kLevels] * 2);
+    *out = SdnTrainLayout{};
+    out->total_bytes = L.total;
+    // no parameter copies in fp32: the kernels read the parameters themselves (w_* stay 0)
+    out->g_table = L.g_table; out->g_deform = L.g_deform; out->g_sigma0 = L.g_sigma0; out->g_sigma1 = L.g_sigma1; out->g_color = L.g_color;
+    out->xyzs = L.pts; out->dirs = L.pts + (uint64_t)M * 12; out->deltas = L.pts + (uint64_t)M * 24; out->rays = L.rays;
+    out->sample_set_stride = L.set_stride;
+    out->sigmas = L.sigmas; out->weights_sum = L.weights_sum; out->depth = L.depth; out->image = L.image;
+    out->found_inf = L.hyper + offsetof(Hyper, found_inf);
+    return 0;
+}
+
+int sdn_train_refresh_f32(const SdnTrainStep *s, void *stream) {
+    if (!s || !s->workspace || ((uintptr_t)s->workspace & 255u) || s->N == 0 || s->M == 0 || s->max_steps == 0 || s->grid_offsets[kLevels] <= 0)
+        return SDN_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const Layout32 L = make_layout32(s->N, s->M, s->max_steps, (uint64_t)s->grid_offsets[kLevels] * 2);
+    unsigned char *ws = (unsigned char *)s->workspace;
+    if (hipMemsetAsync(ws + L.g_table, 0, (uint64_t)s->grid_offsets[kLevels] * 8, st) != hipSuccess || hipMemsetAsync(ws + L.hyper, 0, sizeof(Hyper), st) != hipSuccess)
+        return sdn_launch_status();
+    return sdn_launch_status();
+}
+
+int sdn_train_step_f32(const SdnTrainStep *s, void *stream) {
+    if (!step_ok32(s)) return SDN_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t N = s->N, M = s->M;
+    const Layout32 L = make_layout32(N, M, s->max_steps, (uint64_t)s->grid_offsets[kLevels] * 2);
+    unsigned char *ws = (unsigned char *)s->workspace;
+    auto F = [&](uint64_t off) { return (float *)(ws + off); };
+    Hyper *hyper = (Hyper *)(ws + L.hyper);
+    const int zero_deform = s->time == 0.0f;
+    const int no_deform_grad = zero_deform || s->deform_frozen;
+    const int freeze_deform = zero_deform || s->deform_frozen;
+    int rc;
+    #define SDN_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+    const uint64_t set_off = s->sample_set ? L.set_stride : 0;
+    float *xyzs = F(L.pts + set_off), *dirs = xyzs + (size_t)M * 3, *deltas = xyzs + (size_t)M * 6;
+    const int32_t *ray_table = (const int32_t *)(ws + L.rays + set_off);
+    if (s->phase != 2) {
+        // ---- rays -> samples: the fp16 step's phase 0 / 1 (nothing of it has a dtype) ----------------------------------------------
+        hipLaunchKernelGGL(k_train_rays, dim3(sdn_div_up(N, 256u)), dim3(256), 0, st, F(L.noises + set_off), s->noises, N, s->noise_seed, s->perturb, s->counter);
+        SDN_TRY(sdn_near_far_from_aabb(s->rays_o, s->rays_d, s->aabb, N, s->min_near, F(L.nears + set_off), F(L.fars + set_off), st));
+        if (hipMemsetAsync(ws + L.pts + set_off, 0, (uint64_t)M * 32, st) != hipSuccess) return sdn_launch_status();
+        SDN_TRY(sdn_int::march_rays_train(s->rays_o, s->rays_d, s->bitfield, s->bound, s->dt_gamma, s->max_steps, N, s->cascade, s->grid_size, M,
+                                          F(L.nears + set_off), F(L.fars + set_off), xyzs, dirs, deltas, (int32_t *)(ws + L.rays + set_off), s->counter,
+                                          F(L.noises + set_off), ws + L.march + set_off, s->cull_grid, st));
+    }
+    if (s->phase == 1) return sdn_launch_status();
+    const float *table = s->params[0].param;
+    float *g_table = F(L.g_table);
+    if (s->mode == 1 && hipMemsetAsync(g_table, 0, (uint64_t)s->grid_offsets[kLevels] * 8, st) != hipSuccess) return sdn_launch_status();
+    // the gradient rows compositing fills only for the samples rays own, and dh0 behind them
+    if (hipMemsetAsync(ws + L.dcol_out, 0, L.dh0 - L.dcol_out + (uint64_t)M * 4, st) != hipSuccess) return sdn_launch_status();
+
+    // ---- this step's packed weights (both directions of the three MLPs, one launch) --------------------------------------------------
+    Pack32Args pa{};
+    pack32_jobs(s, L, ws, pa);
+    hipLaunchKernelGGL(k_f32_pack, dim3(sdn_div_up(pack32_threads(pa), 256u)), dim3(256), 0, st, pa);
+    const float *pk = F(L.pk);
+    const dim3 waves(sdn_div_up(M, 32u));
+
+    // ---- forward (network.py:123-169 in fp32) -------------------------------------------------------------------------------------------
+    hipLaunchKernelGGL(k_f32_encode, dim3(sdn_div_up(M * 16u, 256u)), dim3(256), 0, st, xyzs, M, s->time, F(L.enc_in));
+    hipLaunchKernelGGL((k_f32_chain_fwd<kDefIn32, kDefW / 32, kDefL, false>), waves, dim3(64), 0, st, F(L.enc_in), pk + kPkDefF, M, F(L.def_hidden), F(L.def_out));
+    hipLaunchKernelGGL(k_f32_xdef, dim3(sdn_div_up(M * 3u, 256u)), dim3(256), 0, st, xyzs, F(L.def_out), M, zero_deform, s->bound, F(L.xdef));
+    SDN_TRY(sdn_grid_encode_forward(F(L.xdef), table, s->grid_offsets, F(L.grid_out), M, 3, 2, kLevels, s->grid_S, s->grid_H,
+                                    no_deform_grad ? nullptr : F(L.dy_dx), 1, 0, 0, SDN_F32, st));
+    hipLaunchKernelGGL((k_f32_chain_fwd<kSigIn, kSigW / 32, 1, true>), waves, dim3(64), 0, st, F(L.grid_out), pk + kPkSigF, M, F(L.h1), F(L.hout));
+    hipLaunchKernelGGL(k_f32_sigma_post, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, F(L.hout), dirs, M, s->density_scale, F(L.sigmas), F(L.col_in));
+    hipLaunchKernelGGL((k_f32_chain_fwd<kColIn, kColW / 32, kColL, false>), waves, dim3(64), 0, st, F(L.col_in), pk + kPkColF, M, F(L.col_hidden), F(L.col_out));
+    // ---- compositing, loss and their gradients, one wave per ray -------------------------------------------------------------------------
+    const Composite32 ca{F(L.sigmas), deltas, F(L.col_out), F(L.hout), ray_table, s->bg_color, s->target, F(L.weights_sum), F(L.depth), F(L.image),
+                         s->image_out, F(L.sq_err), F(L.dcol_out), F(L.dh0), M, N, s->T_thresh, s->bg_value, s->density_scale};
+    hipLaunchKernelGGL(k_f32_composite_fwd, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
+    hipLaunchKernelGGL(k_train_loss, dim3(1), dim3(1024), 0, st, F(L.sq_err), N, s->loss_out);
+    hipLaunchKernelGGL(k_f32_composite_bwd, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
+
+    // ---- backward through the field ----------------------------------------------------------------------------------------------------
+    hipLaunchKernelGGL((k_f32_chain_bwd<kColW / 32, kColL, 1, false>), waves, dim3(64), 0, st, F(L.dcol_out), pk + kPkColB, F(L.col_hidden), M,
+                       F(L.col_bwd), F(L.dcol_in));
+    hipLaunchKernelGGL(k_f32_dh, dim3(sdn_div_up(M * 16u, 256u)), dim3(256), 0, st, F(L.dh0), F(L.dcol_in), M, F(L.dh));
+    hipLaunchKernelGGL((k_f32_chain_bwd<kSigW / 32, 1, 1, true>), waves, dim3(64), 0, st, F(L.dh), pk + kPkSigB, F(L.h1), M, F(L.dh1), F(L.denc));
+    if (s->det_scratch)
+        SDN_TRY(sdn_grid_encode_backward_det(F(L.denc), F(L.xdef), s->grid_offsets, g_table, M, 3, 2, kLevels, s->grid_S, s->grid_H,
+                                             no_deform_grad ? nullptr : F(L.dy_dx), no_deform_grad ? nullptr : F(L.dx), 1, 0, 0, SDN_F32, s->det_scratch, st));
+    else
+        SDN_TRY(sdn_grid_encode_backward(F(L.denc), F(L.xdef), s->grid_offsets, g_table, M, 3, 2, kLevels, s->grid_S, s->grid_H,
+                                         no_deform_grad ? nullptr : F(L.dy_dx), no_deform_grad ? nullptr : F(L.dx), 1, 0, 0, SDN_F32, st));
+    if (!no_deform_grad) {
+        hipLaunchKernelGGL(k_f32_deform_grad, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, F(L.dx), M, s->bound, F(L.ddef));
+        hipLaunchKernelGGL((k_f32_chain_bwd<kDefW / 32, kDefL, 0, false>), waves, dim3(64), 0, st, F(L.ddef), pk + kPkDefB, F(L.def_hidden), M,
+                           F(L.def_bwd), (float *)nullptr);
+    } else if (hipMemsetAsync(ws + L.g_deform, 0, kDefFlat * 4, st) != hipSuccess) {      // no gradient: zeros, not last step's values
+        return sdn_launch_status();
+    }
+    Dw32Args da{};
+    dw32_jobs(L, ws, M, !no_deform_grad, da);
+    const uint32_t chunks = sdn_div_up(M, kDwChunk);
+    hipLaunchKernelGGL(k_f32_dw, dim3(da.tiles, chunks), dim3(64), 0, st, da, M, F(L.dw_partial));
+    hipLaunchKernelGGL(k_f32_dw_reduce, dim3(sdn_div_up(da.total, 256u)), dim3(256), 0, st, da, chunks, F(L.dw_partial));
+    if (s->mode == 1) return sdn_launch_status();
+
+    // ---- optimizer: Adam on the unscaled gradients, every step counts (the disabled GradScaler) -------------------------------------------
+    const Prologue32 pr{hyper, s->adam_steps, s->beta1, s->beta2, s->lr_table, s->lr_net, !freeze_deform};
+    hipLaunchKernelGGL(k_f32_prologue, dim3(1), dim3(1), 0, st, pr);
+    Adam32Args A{};
+    const uint32_t blocks = build_segments32(s, L, A);
+    if (freeze_deform) for (uint32_t i = 1; i <= kDefL + 1; i++) A.seg[i].frozen = 1;
+    A.hyper = hyper;
+    A.one_minus_b1 = (float)(1.0 - s->beta1); A.b2 = (float)s->beta2; A.one_minus_b2 = (float)(1.0 - s->beta2); A.eps = (float)s->eps;
+    A.ema_keep = 1.0f - s->ema_decay;
+    hipLaunchKernelGGL(k_f32_adam, dim3(blocks), dim3(256), 0, st, A);
+    #undef SDN_TRY
+    return sdn_launch_status();
+}
+
+}  // extern "C"

@@ -27,6 +27,9 @@ class EditTrainStep:
     def __init__(self, teacher, student, mapper, optimizer, scaler, n_rays, device, time, native=True, one_pass=True, **render_kw):
         """one_pass: the teacher's proxy render in one pass (`RayBatchRenderer`: march, one field launch, whole-ray compositing --
         the loop's image bit for bit) instead of the iteration loop built for whole frames (a chain of ~30 launches per batch)."""
+        if native and (scaler is None or not scaler.is_enabled()):
+            raise NotImplementedError("EditTrainStep: fp32 edit training is not native (the teacher is the fp16 FusedField); use an enabled "
+                                      "GradScaler or native=False")
         self.teacher, self.student = teacher, student
         self.field = fused.FusedField(teacher, time, fp16=True)
         if one_pass:

@@ -11,6 +11,10 @@ torch.optim.Adam instance's own moment tensors and the GradScaler's own scale, s
 
 Requirements: the occupancy-grid path with a known sample budget (`model.mean_count > 0`, the reference's steady state after the
 first `update_extra_state`), the default network geometry of dnerf/network.py, no background model.
+
+Without `-O` (a GradScaler built with `enabled=False`, as nerf/utils.py:395 does for fp32, or `scaler=None`) the same class runs
+`sdn_train_step_f32`: the network, its gradients and the table gradient in fp32, Adam on the unscaled loss with no non-finite check
+and no skip.  That path does not support `grad_sync` or `overlap_table_update` (NotImplementedError).
 """
 import ctypes
 
@@ -38,7 +42,8 @@ def _budget(mean_count, align=128):
 class NativeTrainStep:
     def __init__(self, model, optimizer, scaler, n_rays, device, ema_decay=None, perturb=True, bg_color=1, dt_gamma=0.0, max_steps=1024,
                  T_thresh=1e-4, seed=0, grad_sync=None, train_deform=True, overlap_table_update=False, deterministic=None):
-        """optimizer: a torch.optim.Adam over `model.get_params(lr, lr_net)` (or merged groups); scaler: torch.amp.GradScaler.
+        """optimizer: a torch.optim.Adam over `model.get_params(lr, lr_net)` (or merged groups); scaler: torch.amp.GradScaler --
+        enabled: the fp16 (`-O`) step; disabled or None: the fp32 step (sdn_train_step_f32).
         ema_decay: None, or the decay of a torch_ema-style shadow kept in `self.ema_shadow` (nerf/utils.py:906).
         train_deform=False: the deformation MLP is evaluated but not trained (SealD-NeRF's edit training, SealDNeRF/utils.py:692-694;
         the optimizer then need not hold its parameters).
@@ -55,6 +60,11 @@ class NativeTrainStep:
             raise ValueError("NativeTrainStep needs the occupancy-grid path with a known point budget (model.mean_count > 0)")
         if getattr(model, "bg_radius", 0) > 0:
             raise NotImplementedError("NativeTrainStep: the background model is not part of the native step")
+        self.fp32 = scaler is None or not scaler.is_enabled()       # the reference without -O: fp32 network, disabled scaler
+        if self.fp32 and grad_sync is not None:
+            raise NotImplementedError("NativeTrainStep: data-parallel training (grad_sync) is not built for the fp32 step")
+        if self.fp32 and overlap_table_update:
+            raise NotImplementedError("NativeTrainStep: overlap_table_update is not built for the fp32 step")
         if not isinstance(optimizer, torch.optim.Adam) or any(g.get("weight_decay", 0) or g.get("amsgrad") or g.get("maximize") for g in optimizer.param_groups):
             raise ValueError("NativeTrainStep implements torch.optim.Adam without weight decay / amsgrad / maximize (main_dnerf.py:118)")
         _sdn.require_device()
@@ -105,10 +115,10 @@ class NativeTrainStep:
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             steps[i] = float(st["step"])
         self.adam_steps[0], self.adam_steps[1] = steps[0], steps.get(1, 0.0)
-        if scaler.is_enabled() and scaler._scale is None:
+        if not self.fp32 and scaler._scale is None:
             scaler._lazy_init_scale_growth_tracker(self.device)
-        if not scaler.is_enabled():
-            raise ValueError("NativeTrainStep is the fp16 (`-O`) training step: it needs an enabled GradScaler")
+        self._fn = _sdn.lib.sdn_train_step_f32 if self.fp32 else _sdn.lib.sdn_train_step_f16
+        self._grads_left = False
         self.ema_decay, self.ema_updates = ema_decay, 0
         self.ema_shadow = [p.detach().clone() for p in self.params] if ema_decay is not None else None
         self.step_count, self._M, self._ws, self._rec = 0, None, None, None
@@ -142,7 +152,8 @@ class NativeTrainStep:
         m = self.model
         M = _budget(int(m.mean_count))
         lay = _sdn.SdnTrainLayout()
-        _sdn.check(_sdn.lib.sdn_train_layout(self.n_rays, M, self.max_steps, self._offsets, ctypes.byref(lay)), "train_layout")
+        layout = _sdn.lib.sdn_train_layout_f32 if self.fp32 else _sdn.lib.sdn_train_layout
+        _sdn.check(layout(self.n_rays, M, self.max_steps, self._offsets, ctypes.byref(lay)), "train_layout")
         self.layout = lay
         self._ws = torch.empty(int(lay.total_bytes) + 256, dtype=torch.uint8, device=self.device)
         base = self._ws.data_ptr()
@@ -170,15 +181,16 @@ class NativeTrainStep:
                 q.exp_avg, q.exp_avg_sq = None, None      # frozen segment: never read (deform_frozen)
             q.ema = self.ema_shadow[i].data_ptr() if self.ema_shadow is not None else None
         r.adam_steps = self.adam_steps.data_ptr()
-        r.loss_scale, r.growth_tracker = self.scaler._scale.data_ptr(), self.scaler._growth_tracker.data_ptr()
-        r.growth_factor, r.backoff_factor = float(self.scaler.get_growth_factor()), float(self.scaler.get_backoff_factor())
-        r.growth_interval = int(self.scaler.get_growth_interval())
+        if not self.fp32:                                 # (the fp32 step has no loss scale)
+            r.loss_scale, r.growth_tracker = self.scaler._scale.data_ptr(), self.scaler._growth_tracker.data_ptr()
+            r.growth_factor, r.backoff_factor = float(self.scaler.get_growth_factor()), float(self.scaler.get_backoff_factor())
+            r.growth_interval = int(self.scaler.get_growth_interval())
         r.loss_out, r.image_out, r.workspace = self.loss.data_ptr(), self.image.data_ptr(), self._ws_ptr
         if self._table_side is not None:
             r.table_stream, r.table_ready, r.table_done = (self._table_side[0].cuda_stream, self._table_side[1].cuda_event, self._table_side[2].cuda_event)
         if self.deterministic:
             # order-independent table gradient (sdn_grid_encode_backward_det): one 64-bit fixed-point accumulator per table element
-            self._det = torch.empty(int(self._offsets[16]) * 2, dtype=torch.int64, device=self.device)
+            self._det = torch.empty(int(self._offsets[16]) * 2, dtype=torch.int64, device=self.device)     # (fp16 and fp32 tables alike)
             r.det_scratch = self._det.data_ptr()
         if self._rec is not None:
             self.flush()                                  # the old record's table pass may still be in flight: order this stream behind it
@@ -235,15 +247,21 @@ class NativeTrainStep:
                     st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].to(p.device), st["exp_avg_sq"].to(p.device)
                 if i in (0, 1):
                     self.adam_steps[i] = float(st["step"])
-            if self.scaler._scale is None:
+            if not self.fp32 and self.scaler._scale is None:
                 self.scaler._lazy_init_scale_growth_tracker(self.device)
             self._rec = None
         if self._rec is None:
             return self._build()
+        if self.fp32:       # nothing to copy: the fp32 kernels read the parameters; the table-gradient accumulator is cleared
+            _sdn.check(_sdn.lib.sdn_train_refresh_f32(ctypes.byref(self._rec), _sdn.stream()), "train_refresh_f32")
+            return
         _sdn.check(_sdn.lib.sdn_train_refresh(ctypes.byref(self._rec), _sdn.stream()), "train_refresh")
 
     def view(self, name, dtype, shape):
-        """A tensor view of a workspace buffer named in `SdnTrainLayout` (gradients `g_*`, fp16 parameter copies `w_*`, samples...)."""
+        """A tensor view of a workspace buffer named in `SdnTrainLayout` (gradients `g_*`, fp16 parameter copies `w_*`, samples...).
+        The fp32 step keeps fp32 gradients at the same flat shapes and has no `w_*` copies."""
+        if self.fp32 and name.startswith("w_"):
+            raise ValueError(f"NativeTrainStep.view({name!r}): the fp32 step keeps no parameter copies")
         off = int(getattr(self.layout, name)) + (self._ws_ptr - self._ws.data_ptr())
         n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
         return self._ws[off:off + n].view(dtype).view(*shape)
@@ -333,7 +351,7 @@ class NativeTrainStep:
             r.time, r.rays_o, r.rays_d = tv, ro.data_ptr(), rd.data_ptr()
             self._fill_scene(r, tv, m.local_step)
             r.mode, r.phase, r.sample_set = 0, 1, q
-            _sdn.check(_sdn.lib.sdn_train_step_f16(ctypes.byref(r), _sdn.stream()), "train_step_f16 (march ahead)")
+            _sdn.check(self._fn(ctypes.byref(r), _sdn.stream()), "train_step (march ahead)")
             done = torch.cuda.Event()
             done.record(side)
         self._pending = {"set": q, "event": done, "time": tv, "local_step": m.local_step, "step_count": self.step_count, "rays": (ro, rd)}
@@ -391,7 +409,11 @@ class NativeTrainStep:
             r.mode = 2
         else:
             r.mode, r.keep_deform, r.grad_divisor = (1 if grads_only else 0), 0, 1.0
-        _sdn.check(_sdn.lib.sdn_train_step_f16(ctypes.byref(r), _sdn.stream()), "train_step_f16")
+        if self.fp32 and not grads_only and self._grads_left:
+            # a grads-only call left its table gradient in the accumulator, which a full step adds to (the Adam pass clears it)
+            _sdn.check(_sdn.lib.sdn_train_refresh_f32(ctypes.byref(r), _sdn.stream()), "train_refresh_f32")
+        self._grads_left = self.fp32 and grads_only
+        _sdn.check(self._fn(ctypes.byref(r), _sdn.stream()), "train_step")
         m.local_step += 1
         if not grads_only:
             torch.autograd.graph.increment_version(self._written)

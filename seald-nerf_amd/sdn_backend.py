@@ -136,6 +136,9 @@ PROTOTYPES.update({
     "sdn_train_refresh": [ctypes.POINTER(SdnTrainStep), _vp],
     "sdn_train_step_f16": [ctypes.POINTER(SdnTrainStep), _vp],
     "sdn_train_flush": [ctypes.POINTER(SdnTrainStep), _vp],
+    "sdn_train_layout_f32": [_u32, _u32, _u32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(SdnTrainLayout)],
+    "sdn_train_refresh_f32": [ctypes.POINTER(SdnTrainStep), _vp],
+    "sdn_train_step_f32": [ctypes.POINTER(SdnTrainStep), _vp],
 })
 
 PROTOTYPES_U32 = {
