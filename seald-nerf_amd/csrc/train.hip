@@ -23,6 +23,8 @@
 #include <math.h>
 #include <stddef.h>
 
+#include <type_traits>
+
 #include "sdn_common.h"
 #include "sdn_internal.h"
 #include "sh_eval.h"
@@ -41,6 +43,8 @@ constexpr uint32_t kDefFlat = kDefW * kDefIn + (kDefL - 1) * kDefW * kDefW + 16 
 constexpr uint32_t kColFlat = kColW * kColIn + (kColL - 1) * kColW * kColW + 16 * kColW;
 constexpr uint32_t kLevels = 16;
 constexpr uint32_t ACT_RELU = 0;
+static_assert(kDefIn % 8 == 0, "kDefIn: whole 16-byte fp16 row pieces, whole 4-k-pair steps of the fp32 chains");
+template <typename T> constexpr bool kHalf = std::is_same<T, _Float16>::value;   // the fp16 (-O) step's instance of a shared kernel
 
 struct Hyper {          // written by the optimizer prologue, read by the update kernel
     float inv_scale;
@@ -51,54 +55,83 @@ struct Hyper {          // written by the optimizer prologue, read by the update
     int32_t pad_[7];
 };
 
+// the fp32 step's packed weights (k_f32_pack): packed floats of one product: tiles x steps x 64.  Forward chain: first layer (in / 2
+// steps), L - 1 hidden, last (1 tile); backward chain: last^T (8 steps), L - 1 hidden^T, first^T if dX
+constexpr uint64_t pk_floats(uint32_t rows, uint32_t steps) { return (uint64_t)((rows + 31u) / 32u) * steps * 64u; }
+constexpr uint64_t chain_fwd_floats(uint32_t in, uint32_t W, uint32_t L) { return pk_floats(W, in / 2) + (L - 1) * pk_floats(W, W / 2) + pk_floats(16, W / 2); }
+constexpr uint64_t chain_bwd_floats(uint32_t in, uint32_t W, uint32_t L, bool dx) { return pk_floats(W, 8) + (L - 1) * pk_floats(W, W / 2) + (dx ? pk_floats(in, W / 2) : 0); }
+constexpr uint64_t kPkDefF = 0, kPkDefB = kPkDefF + chain_fwd_floats(kDefIn, kDefW, kDefL);
+constexpr uint64_t kPkSigF = kPkDefB + chain_bwd_floats(kDefIn, kDefW, kDefL, false);
+constexpr uint64_t kPkSigB = kPkSigF + chain_fwd_floats(kSigIn, kSigW, 1);
+constexpr uint64_t kPkColF = kPkSigB + chain_bwd_floats(kSigIn, kSigW, 1, true);
+constexpr uint64_t kPkColB = kPkColF + chain_fwd_floats(kColIn, kColW, kColL);
+constexpr uint64_t kPkTotal = kPkColB + chain_bwd_floats(kColIn, kColW, kColL, true);
+// the fp32 step's split-K weight gradients: samples per chunk, floats per chunk's partial sums
+constexpr uint32_t kDwChunk = 512;
+constexpr uint32_t kDwTotal = kDefFlat + kSigW * kSigIn + kSigOut * kSigW + kColFlat;
+
+// The workspace of either step (sdn_train_layout / _f32).  The fp32 step's rows and gradients have the fp16 step's shapes at 4-byte
+// elements; only the fp16 step has parameter copies (w_*), ffmlp packings (pk_*_*) and enc_rm, only the fp32 step has `pk`.
 struct Layout {
     uint64_t total;
     uint64_t w_table, w_deform, w_sigma0, w_sigma1, w_color, g_table, hyper;                 // persistent
-    uint64_t pk_def_f, pk_def_b, pk_col_f, pk_col_b;
+    uint64_t pk_def_f, pk_def_b, pk_col_f, pk_col_b, pk;
     uint64_t nears, fars, noises, rays, pts, march;     // sample set 0 ...
     uint64_t set_stride;                                //  ... set 1 = + set_stride
     uint64_t dcol_out, dh0;
     uint64_t enc_in, def_hidden, def_out, xdef, grid_out, dy_dx, enc_rm, h1, hout, sigmas, col_in, col_hidden, col_out;
     uint64_t weights_sum, depth, image, sq_err;
-    uint64_t col_bwd, dcol_in, dh, dh1, denc, dx16, ddef, def_bwd;
+    uint64_t col_bwd, dcol_in, dh, dh1, denc, dx, ddef, def_bwd;
     uint64_t g_deform, g_sigma0, g_sigma1, g_color, dw_partial;
 };
 
 void dw_job_list(const Layout &L, unsigned char *ws, uint32_t M, sdn_ffh::DwJob *jobs, uint32_t &n);
 
-Layout make_layout(uint32_t N, uint32_t M, uint32_t max_steps, uint64_t table_entries) {
+Layout make_layout(uint32_t N, uint32_t M, uint32_t max_steps, uint64_t table_entries, bool fp32) {
     Layout L{};
     uint64_t at = 0;
     auto take = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 255u) & ~(uint64_t)255u; return o; };
-    const uint64_t m = M, n = N;
-    L.w_table = take(table_entries * 2);  L.w_deform = take(kDefFlat * 2);  L.w_sigma0 = take(kSigW * kSigIn * 2);
-    L.w_sigma1 = take(kSigOut * kSigW * 2);  L.w_color = take(kColFlat * 2);  L.g_table = take(table_entries * 2);
+    const uint64_t m = M, n = N, e = fp32 ? 4 : 2;    // bytes per element of the network's rows and gradients
+    if (!fp32) {
+        L.w_table = take(table_entries * 2);  L.w_deform = take(kDefFlat * 2);  L.w_sigma0 = take(kSigW * kSigIn * 2);
+        L.w_sigma1 = take(kSigOut * kSigW * 2);  L.w_color = take(kColFlat * 2);
+    }
+    L.g_table = take(table_entries * e);
     L.hyper = take(sizeof(Hyper));
-    L.pk_def_f = take((uint64_t)sdn_ffh::total_frags(kDefIn, kDefW, kDefL, 0, 1) * 1024);
-    L.pk_def_b = take((uint64_t)sdn_ffh::total_frags(kDefIn, kDefW, kDefL, 1, 0) * 1024);
-    L.pk_col_f = take((uint64_t)sdn_ffh::total_frags(kColIn, kColW, kColL, 0, 1) * 1024);
-    L.pk_col_b = take((uint64_t)sdn_ffh::total_frags(kColIn, kColW, kColL, 1, 1) * 1024);
+    if (fp32) {
+        L.pk = take(kPkTotal * 4);
+    } else {
+        L.pk_def_f = take((uint64_t)sdn_ffh::total_frags(kDefIn, kDefW, kDefL, 0, 1) * 1024);
+        L.pk_def_b = take((uint64_t)sdn_ffh::total_frags(kDefIn, kDefW, kDefL, 1, 0) * 1024);
+        L.pk_col_f = take((uint64_t)sdn_ffh::total_frags(kColIn, kColW, kColL, 0, 1) * 1024);
+        L.pk_col_b = take((uint64_t)sdn_ffh::total_frags(kColIn, kColW, kColL, 1, 1) * 1024);
+    }
     // two sets of sample buffers (phase 1 of the next batch runs beside phase 2 of this one)
     L.nears = take(n * 4);  L.fars = take(n * 4);  L.noises = take(n * 4);  L.rays = take(n * 12);
     L.pts = take(m * 32);                       // xyzs [M,3] | dirs [M,3] | deltas [M,2], zero-filled by every march
     L.march = take(sdn_march_rays_train_scratch_bytes(N, max_steps));
     L.set_stride = at - L.nears;
     at += L.set_stride;
-    L.dcol_out = take(m * 32);                  // the gradient rows the compositing backward fills for the samples rays own:
-    L.dh0 = take(m * 2);                        // zero-filled by every step (dh0 must follow dcol_out: one fill)
-    L.enc_in = take(m * kDefIn * 2);  L.def_hidden = take(m * kDefL * kDefW * 2);  L.def_out = take(m * 32);
-    L.xdef = take(m * 12);  L.grid_out = take(m * kLevels * 4);  L.dy_dx = take(m * kLevels * 12);
-    L.enc_rm = take(m * kSigIn * 2);  L.h1 = take(m * kSigW * 2);  L.hout = take(m * kSigOut * 2);  L.sigmas = take(m * 4);
-    L.col_in = take(m * kColIn * 2);  L.col_hidden = take(m * kColL * kColW * 2);  L.col_out = take(m * 32);
+    L.dcol_out = take(m * 16 * e);              // the gradient rows the compositing backward fills for the samples rays own:
+    L.dh0 = take(m * e);                        // zero-filled by every step (dh0 must follow dcol_out: one fill)
+    L.enc_in = take(m * kDefIn * e);  L.def_hidden = take(m * kDefL * kDefW * e);  L.def_out = take(m * 16 * e);
+    L.xdef = take(m * 12);  L.grid_out = take(m * kLevels * 2 * e);  L.dy_dx = take(m * kLevels * 6 * e);
+    if (!fp32) L.enc_rm = take(m * kSigIn * 2);
+    L.h1 = take(m * kSigW * e);  L.hout = take(m * kSigOut * e);  L.sigmas = take(m * 4);
+    L.col_in = take(m * kColIn * e);  L.col_hidden = take(m * kColL * kColW * e);  L.col_out = take(m * 16 * e);
     L.weights_sum = take(n * 4);  L.depth = take(n * 4);  L.image = take(n * 12);  L.sq_err = take(n * 4);
-    L.col_bwd = take(m * kColL * kColW * 2);  L.dcol_in = take(m * kColIn * 2);
-    L.dh = take(m * kSigOut * 2);  L.dh1 = take(m * kSigW * 2);  L.denc = take(m * kLevels * 4);  L.dx16 = take(m * 6);
-    L.ddef = take(m * 32);  L.def_bwd = take(m * kDefL * kDefW * 2);
-    L.g_deform = take(kDefFlat * 2);  L.g_sigma0 = take(kSigW * kSigIn * 2);  L.g_sigma1 = take(kSigOut * kSigW * 2);  L.g_color = take(kColFlat * 2);
-    sdn_ffh::DwJob jobs[16];
-    uint32_t nj = 0;
-    dw_job_list(L, nullptr, M, jobs, nj);
-    L.dw_partial = take(sdn_ffh::dw_jobs_bytes(jobs, nj, M));
+    L.col_bwd = take(m * kColL * kColW * e);  L.dcol_in = take(m * kColIn * e);
+    L.dh = take(m * kSigOut * e);  L.dh1 = take(m * kSigW * e);  L.denc = take(m * kLevels * 2 * e);  L.dx = take(m * 3 * e);
+    L.ddef = take(m * 16 * e);  L.def_bwd = take(m * kDefL * kDefW * e);
+    L.g_deform = take(kDefFlat * e);  L.g_sigma0 = take(kSigW * kSigIn * e);  L.g_sigma1 = take(kSigOut * kSigW * e);  L.g_color = take(kColFlat * e);
+    if (fp32) {
+        L.dw_partial = take((uint64_t)sdn_div_up(M, kDwChunk) * kDwTotal * 4);
+    } else {
+        sdn_ffh::DwJob jobs[16];
+        uint32_t nj = 0;
+        dw_job_list(L, nullptr, M, jobs, nj);
+        L.dw_partial = take(sdn_ffh::dw_jobs_bytes(jobs, nj, M));
+    }
     L.total = at;
     return L;
 }
@@ -142,36 +175,39 @@ __global__ void __launch_bounds__(256) k_train_rays(float *__restrict__ noises, 
     if (i < N) noises[i] = perturb ? (given ? given[i] : u01(seed, i)) : 0.0f;
 }
 
-// freq(x, 10) ++ freq(t, 6) as the fp16 input rows of the deformation MLP (freqencoder.cu:30-58's formula; the autocast cast of
+// freq(x, 10) ++ freq(t, 6) as the input rows of the deformation MLP (freqencoder.cu:30-58's formula; in fp16 the autocast cast of
 // F.linear's input).  One thread per (sample, 16th of a row).
-__global__ void __launch_bounds__(256) k_train_encode(const float *__restrict__ xyzs, uint32_t M, float time, _Float16 *__restrict__ enc, Hyper *hyper,
+template <typename T>
+__global__ void __launch_bounds__(256) k_train_encode(const float *__restrict__ xyzs, uint32_t M, float time, T *__restrict__ enc, Hyper *hyper,
                                                       uint4 *__restrict__ zero_fill, uint32_t zero_n16) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t == 0) hyper->found_inf = 0.0f;       // first kernel of a step's own phase: the non-finite flag of this step's gradients
-    // the gradient rows the compositing backward fills only for the samples rays own (dcol_out .. dh0: 34 B per sample, i.e. at most
-    // three 16-byte words per 16 threads of a sample) are cleared here instead of by a fill of their own
-    if (t < zero_n16) zero_fill[t] = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (kHalf<T>) {   // the fp16 step only (the fp32 step has no found_inf and clears these rows with a fill)
+        if (t == 0) hyper->found_inf = 0.0f;       // first kernel of a step's own phase: the non-finite flag of this step's gradients
+        // the gradient rows the compositing backward fills only for the samples rays own (dcol_out .. dh0: 34 B per sample, i.e. at
+        // most three 16-byte words per 16 threads of a sample) are cleared here instead of by a fill of their own
+        if (t < zero_n16) zero_fill[t] = make_uint4(0u, 0u, 0u, 0u);
+    }
     const uint32_t b = t >> 4, j = t & 15u;
     if (b >= M) return;
-    _Float16 *row = enc + (size_t)b * kDefIn;
+    T *row = enc + (size_t)b * kDefIn;
     const float half_pi = 3.141592653589793f / 2;
     if (j < 10) {
         #pragma unroll
         for (int d = 0; d < 3; d++) {
             const float a = scalbnf(xyzs[(size_t)b * 3 + d], (int)j);
-            row[3 + 6 * j + d] = (_Float16)sinf(a + 0.0f);
-            row[6 + 6 * j + d] = (_Float16)sinf(a + half_pi);
+            row[3 + 6 * j + d] = (T)sinf(a + 0.0f);
+            row[6 + 6 * j + d] = (T)sinf(a + half_pi);
         }
     } else if (j == 10) {
         #pragma unroll
-        for (int d = 0; d < 3; d++) row[d] = (_Float16)xyzs[(size_t)b * 3 + d];
+        for (int d = 0; d < 3; d++) row[d] = (T)xyzs[(size_t)b * 3 + d];
     } else if (j == 11) {
-        row[63] = (_Float16)time;
+        row[63] = (T)time;
         #pragma unroll
         for (int f = 0; f < 6; f++) {
             const float a = scalbnf(time, f);
-            row[64 + 2 * f] = (_Float16)sinf(a + 0.0f);
-            row[65 + 2 * f] = (_Float16)sinf(a + half_pi);
+            row[64 + 2 * f] = (T)sinf(a + 0.0f);
+            row[65 + 2 * f] = (T)sinf(a + half_pi);
         }
     } else if (j == 12) {
         row[76] = 0; row[77] = 0; row[78] = 0; row[79] = 0;
@@ -179,7 +215,8 @@ __global__ void __launch_bounds__(256) k_train_encode(const float *__restrict__ 
 }
 
 // x + deform (network.py:140-145, deform = 0 on the canonical frame), normalised as GridEncoder.forward does (grid.py:146)
-__global__ void __launch_bounds__(256) k_train_xdef(const float *__restrict__ xyzs, const _Float16 *__restrict__ def_out, uint32_t M, int zero_deform,
+template <typename T>
+__global__ void __launch_bounds__(256) k_train_xdef(const float *__restrict__ xyzs, const T *__restrict__ def_out, uint32_t M, int zero_deform,
                                                     float bound, float *__restrict__ xdef) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= M * 3) return;
@@ -327,21 +364,52 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-struct CompositeArgs {
+// one chunk of <= 64 samples of a ray: everything the forward AND the backward need about sample `i`
+struct SampleTerms { bool on; float alpha, T, weight, delta0, t, c[3]; };
+
+// The precision the compositing kernels run in.  Fp16Net: the -O step -- fp16 colour MLP output (the fp16 sigmoid), fp16 gradient
+// rows, the loss scaled by the GradScaler's factor.  Fp32Net: everything fp32, the loss unscaled (the disabled scaler).
+struct Fp16Net {
+    typedef _Float16 T;
+    static __device__ __forceinline__ float colour(_Float16 c) { return (float)sigmoid16(c); }
+    static __device__ __forceinline__ float loss_scale(const float *s) { return *s; }
+    // the first 16 bytes of sample s's colour-gradient row, from the gradient gi of its ray's image
+    static __device__ __forceinline__ void store_dcol(_Float16 *row, const float (&gi)[3], const SampleTerms &s) {
+        _Float16 dc[3];
+        #pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            const _Float16 g16 = (_Float16)(gi[ch] * s.weight);                          // composite's float32 cast, backwards
+            dc[ch] = (_Float16)(((float)g16 * (1.0f - s.c[ch])) * s.c[ch]);              // sigmoid backward on fp16 (a * (1 - y) * y in float)
+        }
+        *reinterpret_cast<h8 *>(row) = h8{dc[0], dc[1], dc[2], 0, 0, 0, 0, 0};
+    }
+};
+struct Fp32Net {
+    typedef float T;
+    static __device__ __forceinline__ float colour(float c) { return 1.0f / (1.0f + expf(-c)); }
+    static __device__ __forceinline__ float loss_scale(const float *) { return 1.0f; }
+    static __device__ __forceinline__ void store_dcol(float *row, const float (&gi)[3], const SampleTerms &s) {
+        float dc[3];
+        #pragma unroll
+        for (int ch = 0; ch < 3; ch++) dc[ch] = ((gi[ch] * s.weight) * (1.0f - s.c[ch])) * s.c[ch];
+        *reinterpret_cast<float4 *>(row) = float4{dc[0], dc[1], dc[2], 0.0f};
+    }
+};
+
+template <class Net> struct CompositeArgs {
+    typedef typename Net::T T;
     const float *sigmas, *deltas;        // [M] (density_scale applied), [M,2]
-    const _Float16 *col_out, *hout;      // [M,16] colour MLP output (pre-sigmoid), [M,16] sigma MLP output (column 0: log density)
+    const T *col_out, *hout;             // [M,16] colour MLP output (pre-sigmoid), [M,16] sigma MLP output (column 0: log density)
     const int32_t *rays;                 // [N,3]
-    const float *bg, *gt, *loss_scale;
+    const float *bg, *gt, *loss_scale;   // (loss_scale: the fp16 step's only)
     float *weights_sum, *depth, *image, *image_out, *sq_err;   // per ray; sq_err [N]: sum over channels of (pred - gt)^2
-    _Float16 *dcol_out, *dh0;            // backward: [M,16], [M]
+    T *dcol_out, *dh0;                   // backward: [M,16], [M]
     uint32_t M, N;
     float T_thresh, bg_value, density_scale;
 };
 
-// one chunk of <= 64 samples of a ray: everything the forward AND the backward need about sample `i`
-struct SampleTerms { bool on; float alpha, T, weight, delta0, t, c[3]; };
-
-__device__ __forceinline__ SampleTerms sample_terms(const CompositeArgs &P, uint32_t idx, bool in_ray, float T_carry, float t_carry, uint32_t lane,
+template <class Net>
+__device__ __forceinline__ SampleTerms sample_terms(const CompositeArgs<Net> &P, uint32_t idx, bool in_ray, float T_carry, float t_carry, uint32_t lane,
                                                     float &T_next, float &t_next) {
     SampleTerms s{};
     float one_minus = 1.0f, d1 = 0.0f;
@@ -351,7 +419,7 @@ __device__ __forceinline__ SampleTerms sample_terms(const CompositeArgs &P, uint
         s.alpha = 1.0f - sdn_exp_cr(-P.sigmas[idx] * s.delta0);
         one_minus = 1.0f - s.alpha;
         #pragma unroll
-        for (int ch = 0; ch < 3; ch++) s.c[ch] = (float)sigmoid16(P.col_out[(size_t)idx * 16 + ch]);
+        for (int ch = 0; ch < 3; ch++) s.c[ch] = Net::colour(P.col_out[(size_t)idx * 16 + ch]);
     }
     s.T = T_carry * wave_excl_product(one_minus, lane);
     s.t = t_carry + wave_incl_sum(d1, lane);
@@ -362,7 +430,8 @@ __device__ __forceinline__ SampleTerms sample_terms(const CompositeArgs &P, uint
     return s;
 }
 
-__global__ void __launch_bounds__(256) k_train_composite_fwd(CompositeArgs P) {
+template <class Net>
+__global__ void __launch_bounds__(256) k_train_composite_fwd(CompositeArgs<Net> P) {
     const uint32_t lane = threadIdx.x & 63u, n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= P.N) return;
     const uint32_t index = (uint32_t)P.rays[n * 3], offset = (uint32_t)P.rays[n * 3 + 1], count = (uint32_t)P.rays[n * 3 + 2];
@@ -413,14 +482,15 @@ __global__ void __launch_bounds__(1024) k_train_loss(const float *__restrict__ s
     }
 }
 
-__global__ void __launch_bounds__(256) k_train_composite_bwd(CompositeArgs P) {
+template <class Net>
+__global__ void __launch_bounds__(256) k_train_composite_bwd(CompositeArgs<Net> P) {
     const uint32_t lane = threadIdx.x & 63u, n = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= P.N) return;
     const uint32_t index = (uint32_t)P.rays[n * 3], offset = (uint32_t)P.rays[n * 3 + 1], count = (uint32_t)P.rays[n * 3 + 2];
     if (count == 0 || offset + count > P.M) return;
     // gradient of scale * loss with respect to this ray's image and weights_sum (MSE mean over 3 N values; the background mix)
     const float ws_final = P.weights_sum[index];
-    const float cg = (*P.loss_scale / (float)P.N) / 3.0f;
+    const float cg = (Net::loss_scale(P.loss_scale) / (float)P.N) / 3.0f;
     float gi[3], fin[3], gws = 0.0f;
     #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
@@ -443,15 +513,9 @@ __global__ void __launch_bounds__(256) k_train_composite_bwd(CompositeArgs P) {
             const float T_after = s.T * (1.0f - s.alpha);
             const float g_sigma = s.delta0 * (gi[0] * (T_after * s.c[0] - (fin[0] - run[0])) + gi[1] * (T_after * s.c[1] - (fin[1] - run[1])) +
                                               gi[2] * (T_after * s.c[2] - (fin[2] - run[2])) + gws * (1.0f - ws_final));
-            _Float16 dc[3];
-            #pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                const _Float16 g16 = (_Float16)(gi[ch] * s.weight);                       // composite's float32 cast, backwards
-                dc[ch] = (_Float16)(((float)g16 * (1.0f - s.c[ch])) * s.c[ch]);             // sigmoid backward on fp16 (a * (1 - y) * y in float)
-            }
-            *reinterpret_cast<h8 *>(P.dcol_out + (size_t)idx * 16) = h8{dc[0], dc[1], dc[2], 0, 0, 0, 0, 0};
+            Net::store_dcol(P.dcol_out + (size_t)idx * 16, gi, s);
             const float x = fminf(fmaxf((float)P.hout[(size_t)idx * kSigOut], -15.0f), 15.0f);
-            P.dh0[idx] = (_Float16)((g_sigma * P.density_scale) * expf(x));              // density_scale, trunc_exp backward, cast to fp16
+            P.dh0[idx] = (typename Net::T)((g_sigma * P.density_scale) * expf(x));      // density_scale, trunc_exp backward (fp16: the cast)
         }
         #pragma unroll
         for (int ch = 0; ch < 3; ch++) acc_c[ch] = __shfl(run[ch], 63);
@@ -513,17 +577,20 @@ __global__ void __launch_bounds__(64) k_train_sigma_bwd(SigmaBwd P) {
     }
 }
 
-// gradient of the deformation MLP's output: grid input gradient (fp16 -> float), / (2 bound) of the normalisation, the fp16 cast of
-// `deform.to(x.dtype)`; zero columns 3..15 of the operator's 16-wide output
-__global__ void __launch_bounds__(256) k_train_deform_grad(const _Float16 *__restrict__ dx16, uint32_t M, float bound, _Float16 *__restrict__ ddef) {
+// gradient of the deformation MLP's output: grid input gradient, / (2 bound) of the normalisation (in fp16 the cast of
+// `deform.to(x.dtype)`); zero columns 3..15 of the operator's 16-wide output
+template <typename T>
+__global__ void __launch_bounds__(256) k_train_deform_grad(const T *__restrict__ dx, uint32_t M, float bound, T *__restrict__ ddef) {
+    typedef T piece __attribute__((ext_vector_type(16 / sizeof(T))));   // 16 bytes of a row: a row of 16 is sizeof(T) pieces
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= M) return;
-    _Float16 d[3];
+    T d[3];
     #pragma unroll
-    for (int c = 0; c < 3; c++) d[c] = (_Float16)((float)dx16[(size_t)b * 3 + c] / (2 * bound));
-    h8 *row = reinterpret_cast<h8 *>(ddef + (size_t)b * 16);
-    row[0] = h8{d[0], d[1], d[2], 0, 0, 0, 0, 0};
-    row[1] = h8{0, 0, 0, 0, 0, 0, 0, 0};
+    for (int c = 0; c < 3; c++) d[c] = (T)((float)dx[(size_t)b * 3 + c] / (2 * bound));
+    piece *row = reinterpret_cast<piece *>(ddef + (size_t)b * 16);
+    row[0] = piece{d[0], d[1], d[2]};
+    #pragma unroll
+    for (uint32_t k = 1; k < sizeof(T); k++) row[k] = piece{};
 }
 
 // ---- optimizer ------------------------------------------------------------------------------------------------------------------
@@ -561,12 +628,18 @@ __global__ void __launch_bounds__(256) k_train_check(CheckArgs A) {
 
 // One thread: the skip decision, bias corrections in double as torch's Adam computes them on the host (adam.py _single_tensor_adam:
 // 1 - beta ** step, lr / bias_correction1, bias_correction2 ** 0.5), and amp_update_scale (AmpKernels.cu) for the NEXT step.
+// Without a scaler (the fp32 step: the disabled GradScaler) every step counts; found_inf, scale and tracker are not read.
+template <bool SCALER>
 __global__ void k_train_prologue(Prologue P) {
     Hyper *h = P.hyper;
-    const bool found = h->found_inf != 0.0f;
-    const float scale = *P.scale;
-    h->skip = found ? 1 : 0;
-    h->inv_scale = (float)(1.0 / ((double)scale * (double)P.divisor));
+    bool found = false;
+    float scale = 1.0f;
+    if constexpr (SCALER) {
+        found = h->found_inf != 0.0f;
+        scale = *P.scale;
+        h->skip = found ? 1 : 0;
+        h->inv_scale = (float)(1.0 / ((double)scale * (double)P.divisor));
+    }
     if (!found) {
         P.steps[0] += 1.0f;
         if (P.deform_active) P.steps[1] += 1.0f;
@@ -578,6 +651,7 @@ __global__ void k_train_prologue(Prologue P) {
         h->step_size[1][g] = (float)(P.lr_net / bc1);
         h->bc2_sqrt[g] = (float)sqrt(bc2);
     }
+    if constexpr (!SCALER) return;
     if (found) {
         *P.scale = scale * P.backoff;
         *P.tracker = 0;
@@ -593,43 +667,49 @@ __global__ void k_train_prologue(Prologue P) {
     }
 }
 
-struct AdamSeg {
+template <typename G> struct AdamSeg {
     float *p, *m, *v, *ema;
-    _Float16 *g;        // fp16 gradient, element (r, c) at r * ld + c
-    _Float16 *w16;      // fp16 copy, same layout
+    G *g;               // gradient (fp16: scaled by the loss scale), element (r, c) at r * ld + c
+    _Float16 *w16;      // fp16 copy, same layout (the fp16 step's only)
     uint32_t n, cols, ld, split;      // columns >= split sit one column further right (the colour MLP's input layer: [SH 16 | 0 | geo 15])
     uint32_t lr_idx, group, zero_grad, frozen, blk_begin;
 };
-struct AdamArgs {
-    AdamSeg seg[SDN_TRAIN_N_PARAMS];
+template <typename G> struct AdamArgs {
+    AdamSeg<G> seg[SDN_TRAIN_N_PARAMS];
     uint32_t nseg;
     const Hyper *hyper;
     float one_minus_b1, b2, one_minus_b2, eps, ema_keep;   // ema_keep = 1 - decay
 };
 
-// torch.optim.Adam, single-tensor form (adam.py:_single_tensor_adam; amsgrad / weight_decay / maximize off), on gradients unscaled
-// the way GradScaler.unscale_ does (float(grad) * inv_scale):   m.lerp_(g, 1 - b1);  v.mul_(b2).addcmul_(g, g, 1 - b2);
-// denom = sqrt(v) / bias_correction2_sqrt + eps;  p.addcdiv_(m, denom, -step_size).   The same pass writes the fp16 copy the next
-// step's kernels read (the autocast casts of the reference), clears the table's gradient accumulator, and applies torch_ema's
-// shadow -= (1 - decay) * (shadow - p).  A step with a non-finite gradient changes nothing but the accumulator and the shadows.
-__global__ void __launch_bounds__(256) k_train_adam(AdamArgs A) {
+// the gradient Adam sees: the fp16 step's unscaled the way GradScaler.unscale_ does (float(grad) * inv_scale), the fp32 step's as is
+__device__ __forceinline__ float adam_grad(_Float16 g, float inv_scale) { return (float)g * inv_scale; }
+__device__ __forceinline__ float adam_grad(float g, float) { return g; }
+
+// torch.optim.Adam, single-tensor form (adam.py:_single_tensor_adam; amsgrad / weight_decay / maximize off):   m.lerp_(g, 1 - b1);
+// v.mul_(b2).addcmul_(g, g, 1 - b2);  denom = sqrt(v) / bias_correction2_sqrt + eps;  p.addcdiv_(m, denom, -step_size).   The same
+// pass clears the table's gradient accumulator and applies torch_ema's shadow -= (1 - decay) * (shadow - p).  In the fp16 step
+// (G = _Float16) it also writes the fp16 copy the next step's kernels read (the autocast casts of the reference), and a step with a
+// non-finite gradient changes nothing but the accumulator and the shadows; the fp32 step has no copies and no skip.
+template <typename G>
+__global__ void __launch_bounds__(256) k_train_adam(AdamArgs<G> A) {
+    typedef G g4 __attribute__((ext_vector_type(4)));
     uint32_t s = 0;
     for (uint32_t k = 1; k < A.nseg; k++) s = blockIdx.x >= A.seg[k].blk_begin ? k : s;
-    const AdamSeg &S = A.seg[s];
+    const AdamSeg<G> &S = A.seg[s];
     const Hyper &H = *A.hyper;
-    const bool update = !H.skip && !S.frozen;
+    const bool update = !(kHalf<G> && H.skip) && !S.frozen;
     const float inv_scale = H.inv_scale, step_size = H.step_size[S.lr_idx][S.group], bc2s = H.bc2_sqrt[S.group];
     // the table (12.2 M contiguous entries: the pass's HBM traffic) four entries per lane: 16-byte loads and stores
     const uint32_t first = (blockIdx.x - S.blk_begin) * 1024u;
     if (S.cols == S.ld && first + 1024u <= S.n && !S.ema && update) {
         const uint32_t i = first + 4u * threadIdx.x;
         float4 p = *reinterpret_cast<const float4 *>(S.p + i), m = *reinterpret_cast<const float4 *>(S.m + i), v = *reinterpret_cast<const float4 *>(S.v + i);
-        const h4 g16 = *reinterpret_cast<const h4 *>(S.g + i);
+        const g4 gv = *reinterpret_cast<const g4 *>(S.g + i);
         float *pp = &p.x, *mm = &m.x, *vv = &v.x;
         h4 w;
         #pragma unroll
         for (int e = 0; e < 4; e++) {
-            const float g = (float)g16[e] * inv_scale;
+            const float g = adam_grad(gv[e], inv_scale);
             mm[e] = mm[e] + A.one_minus_b1 * (g - mm[e]);
             vv[e] = vv[e] * A.b2 + (A.one_minus_b2 * g) * g;
             const float denom = sqrtf(vv[e]) / bc2s + A.eps;
@@ -637,8 +717,8 @@ __global__ void __launch_bounds__(256) k_train_adam(AdamArgs A) {
             w[e] = (_Float16)pp[e];
         }
         *reinterpret_cast<float4 *>(S.m + i) = m; *reinterpret_cast<float4 *>(S.v + i) = v; *reinterpret_cast<float4 *>(S.p + i) = p;
-        *reinterpret_cast<h4 *>(S.w16 + i) = w;
-        if (S.zero_grad) *reinterpret_cast<h4 *>(S.g + i) = h4{0, 0, 0, 0};
+        if constexpr (kHalf<G>) *reinterpret_cast<h4 *>(S.w16 + i) = w;
+        if (S.zero_grad) *reinterpret_cast<g4 *>(S.g + i) = g4{0, 0, 0, 0};
         return;
     }
     const uint32_t base = first + threadIdx.x;
@@ -650,25 +730,25 @@ __global__ void __launch_bounds__(256) k_train_adam(AdamArgs A) {
         if (S.cols != S.ld) { const uint32_t r = i / S.cols, c = i - r * S.cols; j = r * S.ld + c + (c >= S.split ? 1u : 0u); }
         float p = S.p[i];
         if (update) {
-            const float g = (float)S.g[j] * inv_scale;
+            const float g = adam_grad(S.g[j], inv_scale);
             float m = S.m[i], v = S.v[i];
             m = m + A.one_minus_b1 * (g - m);
             v = v * A.b2 + (A.one_minus_b2 * g) * g;
             const float denom = sqrtf(v) / bc2s + A.eps;
             p = p - step_size * (m / denom);
             S.m[i] = m; S.v[i] = v; S.p[i] = p;
-            S.w16[j] = (_Float16)p;
+            if constexpr (kHalf<G>) S.w16[j] = (_Float16)p;
         }
-        if (S.zero_grad) S.g[j] = (_Float16)0;
+        if (S.zero_grad) S.g[j] = (G)0;
         if (S.ema) { const float e = S.ema[i]; S.ema[i] = e - (e - p) * A.ema_keep; }
     }
 }
 
 // fp16 copies from the fp32 masters (sdn_train_refresh)
-__global__ void __launch_bounds__(256) k_train_copy16(AdamArgs A) {
+__global__ void __launch_bounds__(256) k_train_copy16(AdamArgs<_Float16> A) {
     uint32_t s = 0;
     for (uint32_t k = 1; k < A.nseg; k++) s = blockIdx.x >= A.seg[k].blk_begin ? k : s;
-    const AdamSeg &S = A.seg[s];
+    const AdamSeg<_Float16> &S = A.seg[s];
     const uint32_t base = (blockIdx.x - S.blk_begin) * 1024u + threadIdx.x;
     #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -680,10 +760,10 @@ __global__ void __launch_bounds__(256) k_train_copy16(AdamArgs A) {
     }
 }
 
-// parameter i of SDN_TRAIN_N_PARAMS -> its place in the fp16 copies / gradients
-uint32_t build_segments(const SdnTrainStep *s, const Layout &L, AdamArgs &A) {
+// parameter i of SDN_TRAIN_N_PARAMS -> its place in the gradients (and the fp16 step's copies)
+template <typename G>
+uint32_t build_segments(const SdnTrainStep *s, const Layout &L, AdamArgs<G> &A) {
     unsigned char *ws = (unsigned char *)s->workspace;
-    auto H = [&](uint64_t off) { return (_Float16 *)(ws + off); };
     struct Place { uint64_t w, g; uint32_t off, rows, cols, ld, lr, group; };
     Place pl[SDN_TRAIN_N_PARAMS];
     const uint32_t table_n = (uint32_t)s->grid_offsets[kLevels] * 2u;
@@ -699,9 +779,9 @@ uint32_t build_segments(const SdnTrainStep *s, const Layout &L, AdamArgs &A) {
     uint32_t blk = 0;
     for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) {
         const SdnTrainParam &q = s->params[i];
-        AdamSeg &S = A.seg[i];
+        AdamSeg<G> &S = A.seg[i];
         S.p = q.param; S.m = q.exp_avg; S.v = q.exp_avg_sq; S.ema = q.ema;
-        S.g = H(pl[i].g) + pl[i].off; S.w16 = H(pl[i].w) + pl[i].off;
+        S.g = (G *)(ws + pl[i].g) + pl[i].off; S.w16 = kHalf<G> ? (_Float16 *)(ws + pl[i].w) + pl[i].off : nullptr;
         S.n = pl[i].rows * pl[i].cols; S.cols = pl[i].cols; S.ld = pl[i].ld; S.split = i == 11 ? 16u : 0xFFFFFFFFu;
         S.lr_idx = pl[i].lr; S.group = pl[i].group; S.zero_grad = i == 0; S.frozen = 0; S.blk_begin = blk;
         blk += sdn_div_up(S.n, 1024u);
@@ -711,8 +791,8 @@ uint32_t build_segments(const SdnTrainStep *s, const Layout &L, AdamArgs &A) {
 }
 
 // Adam over the segments [i0, i1) of a full segment list (workgroup ranges re-based)
-void launch_adam(const AdamArgs &all, uint32_t i0, uint32_t i1, hipStream_t st) {
-    AdamArgs A = all;
+void launch_adam(const AdamArgs<_Float16> &all, uint32_t i0, uint32_t i1, hipStream_t st) {
+    AdamArgs<_Float16> A = all;
     uint32_t blk = 0;
     for (uint32_t i = i0; i < i1; i++) {
         A.seg[i - i0] = all.seg[i];
@@ -720,7 +800,18 @@ void launch_adam(const AdamArgs &all, uint32_t i0, uint32_t i1, hipStream_t st) 
         blk += sdn_div_up(all.seg[i].n, 1024u);
     }
     A.nseg = i1 - i0;
-    hipLaunchKernelGGL(k_train_adam, dim3(blk), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_train_adam<_Float16>, dim3(blk), dim3(256), 0, st, A);
+}
+
+// the optimizer pass of a step: its segments, the frozen deformation MLP, Adam's and the EMA's constants
+template <typename G>
+uint32_t adam_args(const SdnTrainStep *s, const Layout &L, Hyper *hyper, bool freeze_deform, AdamArgs<G> &A) {
+    const uint32_t blocks = build_segments(s, L, A);
+    if (freeze_deform) for (uint32_t i = 1; i <= kDefL + 1; i++) A.seg[i].frozen = 1;
+    A.hyper = hyper;
+    A.one_minus_b1 = (float)(1.0 - s->beta1); A.b2 = (float)s->beta2; A.one_minus_b2 = (float)(1.0 - s->beta2); A.eps = (float)s->eps;
+    A.ema_keep = 1.0f - s->ema_decay;
+    return blocks;
 }
 
 int table_wait(const SdnTrainStep *s, hipStream_t st) {
@@ -728,23 +819,28 @@ int table_wait(const SdnTrainStep *s, hipStream_t st) {
     return 0;
 }
 
-bool step_ok(const SdnTrainStep *s) {
-    if (!s || !s->workspace || ((uintptr_t)s->workspace & 255u)) return false;
-    if (s->mode < 0 || s->mode > 2) return false;
-    if ((s->table_stream != nullptr) != (s->table_ready != nullptr) || (s->table_stream != nullptr) != (s->table_done != nullptr)) return false;
+bool workspace_ok(const SdnTrainStep *s) { return s && s->workspace && !((uintptr_t)s->workspace & 255u); }
+
+// the record checks of sdn_train_step_f16 / _f32.  The fp32 step has no optimizer-only mode and no overlapped table pass (data
+// parallelism), and no scaler: loss_scale and growth_tracker are not read.
+bool step_ok(const SdnTrainStep *s, bool fp32) {
+    if (!workspace_ok(s)) return false;
+    if (s->mode < 0 || s->mode > (fp32 ? 1 : 2)) return false;
+    if (fp32 ? (s->table_stream || s->table_ready || s->table_done)
+             : (s->table_stream != nullptr) != (s->table_ready != nullptr) || (s->table_stream != nullptr) != (s->table_done != nullptr)) return false;
     if (s->phase < 0 || s->phase > 2 || (s->mode == 2 && s->phase != 0)) return false;
     if (s->mode != 2 && s->phase != 2 && (!s->rays_o || !s->rays_d || !s->bitfield || !s->aabb || !s->counter)) return false;
     if (s->mode != 2 && s->phase != 1 && (!s->target || !s->loss_out)) return false;
-    if (s->N == 0 || s->M == 0 || s->max_steps == 0 || s->bound <= 0) return false;
+    if (s->N == 0 || s->M == 0 || s->max_steps == 0 || s->bound <= 0 || (fp32 && s->grid_offsets[kLevels] <= 0)) return false;
     for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) if (!s->params[i].param) return false;
     if (s->mode != 1) {
-        if (!s->adam_steps || !s->loss_scale || !s->growth_tracker) return false;
+        if (!s->adam_steps || (!fp32 && (!s->loss_scale || !s->growth_tracker))) return false;
         // (a frozen deformation MLP -- SealD-NeRF's edit training -- has no optimizer state: its Adam segments are never touched)
         for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) {
             const bool frozen = s->deform_frozen && i >= 1 && i <= (int)kDefL + 1;
             if (!frozen && (!s->params[i].exp_avg || !s->params[i].exp_avg_sq)) return false;
         }
-    } else if (!s->loss_scale) {
+    } else if (!fp32 && !s->loss_scale) {
         return false;
     }
     const uint64_t expect[SDN_TRAIN_N_PARAMS] = {(uint64_t)s->grid_offsets[kLevels] * 2, kDefW * kDefCols, kDefW * kDefW, kDefW * kDefW, kDefW * kDefW, kDefW * kDefW,
@@ -753,13 +849,30 @@ bool step_ok(const SdnTrainStep *s) {
     return true;
 }
 
-}  // namespace
 
-extern "C" {
+#define SDN_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
 
-int sdn_train_layout(uint32_t N, uint32_t M, uint32_t max_steps, const int32_t *grid_offsets, SdnTrainLayout *out) {
+Layout step_layout(const SdnTrainStep *s, bool fp32) { return make_layout(s->N, s->M, s->max_steps, (uint64_t)s->grid_offsets[kLevels] * 2, fp32); }
+
+// phase 0 / 1 of either step: rays -> samples of the sample set at `set_off` (renderer.py:283-304; nothing of it has a dtype)
+int march_samples(const SdnTrainStep *s, const Layout &L, uint64_t set_off, hipStream_t st) {
+    const uint32_t N = s->N, M = s->M;
+    unsigned char *ws = (unsigned char *)s->workspace;
+    auto F = [&](uint64_t off) { return (float *)(ws + off); };
+    float *xyzs = F(L.pts + set_off), *dirs = xyzs + (size_t)M * 3, *deltas = xyzs + (size_t)M * 6;
+    int rc;
+    hipLaunchKernelGGL(k_train_rays, dim3(sdn_div_up(N, 256u)), dim3(256), 0, st, F(L.noises + set_off), s->noises, N, s->noise_seed, s->perturb, s->counter);
+    SDN_TRY(sdn_near_far_from_aabb(s->rays_o, s->rays_d, s->aabb, N, s->min_near, F(L.nears + set_off), F(L.fars + set_off), st));
+    if (hipMemsetAsync(ws + L.pts + set_off, 0, (uint64_t)M * 32, st) != hipSuccess) return sdn_launch_status();
+    return sdn_int::march_rays_train(s->rays_o, s->rays_d, s->bitfield, s->bound, s->dt_gamma, s->max_steps, N, s->cascade, s->grid_size, M,
+                                     F(L.nears + set_off), F(L.fars + set_off), xyzs, dirs, deltas, (int32_t *)(ws + L.rays + set_off), s->counter,
+                                     F(L.noises + set_off), ws + L.march + set_off, s->cull_grid, st);
+}
+
+// sdn_train_layout / _f32 (the fp32 step has no parameter copies: its w_* are 0)
+int fill_layout(uint32_t N, uint32_t M, uint32_t max_steps, const int32_t *grid_offsets, SdnTrainLayout *out, bool fp32) {
     if (!grid_offsets || !out || N == 0 || M == 0 || max_steps == 0 || grid_offsets[kLevels] <= 0) return SDN_E_BADARG;
-    const Layout L = make_layout(N, M, max_steps, (uint64_t)grid_offsets[kLevels] * 2);
+    const Layout L = make_layout(N, M, max_steps, (uint64_t)grid_offsets[kLevels] * 2, fp32);
     out->total_bytes = L.total;
     out->w_table = L.w_table; out->w_deform = L.w_deform; out->w_sigma0 = L.w_sigma0; out->w_sigma1 = L.w_sigma1; out->w_color = L.w_color;
     out->g_table = L.g_table; out->g_deform = L.g_deform; out->g_sigma0 = L.g_sigma0; out->g_sigma1 = L.g_sigma1; out->g_color = L.g_color;
@@ -770,18 +883,26 @@ int sdn_train_layout(uint32_t N, uint32_t M, uint32_t max_steps, const int32_t *
     return 0;
 }
 
+}  // namespace
+
+extern "C" {
+
+int sdn_train_layout(uint32_t N, uint32_t M, uint32_t max_steps, const int32_t *grid_offsets, SdnTrainLayout *out) {
+    return fill_layout(N, M, max_steps, grid_offsets, out, false);
+}
+
 int sdn_train_refresh(const SdnTrainStep *s, void *stream) {
-    if (!s || !s->workspace || ((uintptr_t)s->workspace & 255u)) return SDN_E_BADARG;
+    if (!workspace_ok(s)) return SDN_E_BADARG;
     for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) if (!s->params[i].param) return SDN_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = table_wait(s, st)) return rc;
-    const Layout L = make_layout(s->N, s->M, s->max_steps, (uint64_t)s->grid_offsets[kLevels] * 2);
+    const Layout L = step_layout(s, false);
     unsigned char *ws = (unsigned char *)s->workspace;
     // zero padding of the flat networks, and the table's gradient accumulator
     if (hipMemsetAsync(ws + L.w_deform, 0, kDefFlat * 2, st) != hipSuccess || hipMemsetAsync(ws + L.w_color, 0, kColFlat * 2, st) != hipSuccess ||
         hipMemsetAsync(ws + L.g_table, 0, (uint64_t)s->grid_offsets[kLevels] * 4, st) != hipSuccess || hipMemsetAsync(ws + L.hyper, 0, sizeof(Hyper), st) != hipSuccess)
         return sdn_launch_status();
-    AdamArgs A{};
+    AdamArgs<_Float16> A{};
     const uint32_t blocks = build_segments(s, L, A);
     hipLaunchKernelGGL(k_train_copy16, dim3(blocks), dim3(256), 0, st, A);
     return sdn_launch_status();
@@ -793,10 +914,10 @@ int sdn_train_flush(const SdnTrainStep *s, void *stream) {
 }
 
 int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
-    if (!step_ok(s)) return SDN_E_BADARG;
+    if (!step_ok(s, false)) return SDN_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t N = s->N, M = s->M;
-    const Layout L = make_layout(N, M, s->max_steps, (uint64_t)s->grid_offsets[kLevels] * 2);
+    const Layout L = step_layout(s, false);
     unsigned char *ws = (unsigned char *)s->workspace;
     auto F = [&](uint64_t off) { return (float *)(ws + off); };
     auto H = [&](uint64_t off) { return (_Float16 *)(ws + off); };
@@ -805,19 +926,10 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
     const int no_deform_grad = zero_deform || s->deform_frozen;           // nothing flows back through x + deform
     const int freeze_deform = (zero_deform && !s->keep_deform) || s->deform_frozen;
     int rc;
-    #define SDN_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
     const uint64_t set_off = s->sample_set ? L.set_stride : 0;
     float *xyzs = F(L.pts + set_off), *dirs = xyzs + (size_t)M * 3, *deltas = xyzs + (size_t)M * 6;
     const int32_t *ray_table = (const int32_t *)(ws + L.rays + set_off);
-    if (s->mode != 2 && s->phase != 2) {
-        // ---- rays -> samples (renderer.py:283-304) --------------------------------------------------------------------------------
-        hipLaunchKernelGGL(k_train_rays, dim3(sdn_div_up(N, 256u)), dim3(256), 0, st, F(L.noises + set_off), s->noises, N, s->noise_seed, s->perturb, s->counter);
-        SDN_TRY(sdn_near_far_from_aabb(s->rays_o, s->rays_d, s->aabb, N, s->min_near, F(L.nears + set_off), F(L.fars + set_off), st));
-        if (hipMemsetAsync(ws + L.pts + set_off, 0, (uint64_t)M * 32, st) != hipSuccess) return sdn_launch_status();
-        SDN_TRY(sdn_int::march_rays_train(s->rays_o, s->rays_d, s->bitfield, s->bound, s->dt_gamma, s->max_steps, N, s->cascade, s->grid_size, M,
-                                          F(L.nears + set_off), F(L.fars + set_off), xyzs, dirs, deltas, (int32_t *)(ws + L.rays + set_off), s->counter,
-                                          F(L.noises + set_off), ws + L.march + set_off, s->cull_grid, st));
-    }
+    if (s->mode != 2 && s->phase != 2) SDN_TRY(march_samples(s, L, set_off, st));
     if (s->phase == 1) return sdn_launch_status();
     if (s->mode != 2) {
     // (dcol_out .. dh0 are cleared by k_train_encode below: both buffers are padded to 256 bytes, so rounding the range up to 16 is safe)
@@ -835,10 +947,10 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
 
     // ---- forward (network.py:123-169) ---------------------------------------------------------------------------------------------
     if (zero_n16 > M * 16u) return SDN_E_BADARG;     // (34 B per sample + padding: never more than one word per thread)
-    hipLaunchKernelGGL(k_train_encode, dim3(sdn_div_up(M * 16u, 256u)), dim3(256), 0, st, xyzs, M, s->time, H(L.enc_in), hyper,
+    hipLaunchKernelGGL(k_train_encode<_Float16>, dim3(sdn_div_up(M * 16u, 256u)), dim3(256), 0, st, xyzs, M, s->time, H(L.enc_in), hyper,
                        (uint4 *)(ws + L.dcol_out), zero_n16);
     SDN_TRY(sdn_ffh::forward_packed(H(L.enc_in), ws + L.pk_def_f, M, kDefIn, kDefW, kDefL, ACT_RELU, H(L.def_hidden), H(L.def_out), st));
-    hipLaunchKernelGGL(k_train_xdef, dim3(sdn_div_up(M * 3u, 256u)), dim3(256), 0, st, xyzs, H(L.def_out), M, zero_deform, s->bound, F(L.xdef));
+    hipLaunchKernelGGL(k_train_xdef<_Float16>, dim3(sdn_div_up(M * 3u, 256u)), dim3(256), 0, st, xyzs, H(L.def_out), M, zero_deform, s->bound, F(L.xdef));
     SDN_TRY(table_wait(s, st));       // the previous step's pass over the table (fp16 copy, gradient accumulator), if it ran on table_stream
     SDN_TRY(sdn_grid_encode_forward(F(L.xdef), ws + L.w_table, s->grid_offsets, ws + L.grid_out, M, 3, 2, kLevels, s->grid_S, s->grid_H,
                                     no_deform_grad ? nullptr : ws + L.dy_dx, 1, 0, 0, SDN_F16, st));
@@ -846,24 +958,24 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
     hipLaunchKernelGGL(k_train_sigma_fwd, dim3(sdn_div_up(M, 32u)), dim3(64), 0, st, sf);
     SDN_TRY(sdn_ffh::forward_packed(H(L.col_in), ws + L.pk_col_f, M, kColIn, kColW, kColL, ACT_RELU, H(L.col_hidden), H(L.col_out), st));
     // ---- compositing, loss, and their gradients (renderer.py:309-318, utils.py:85-125), one wave per ray ----------------------------
-    const CompositeArgs ca{F(L.sigmas), deltas, H(L.col_out), H(L.hout), ray_table, s->bg_color, s->target, s->loss_scale, F(L.weights_sum),
+    const CompositeArgs<Fp16Net> ca{F(L.sigmas), deltas, H(L.col_out), H(L.hout), ray_table, s->bg_color, s->target, s->loss_scale, F(L.weights_sum),
                            F(L.depth), F(L.image), s->image_out, F(L.sq_err), H(L.dcol_out), H(L.dh0), M, N, s->T_thresh, s->bg_value, s->density_scale};
-    hipLaunchKernelGGL(k_train_composite_fwd, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
+    hipLaunchKernelGGL(k_train_composite_fwd<Fp16Net>, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
     hipLaunchKernelGGL(k_train_loss, dim3(1), dim3(1024), 0, st, F(L.sq_err), N, s->loss_out);
 
     // ---- backward through the field ---------------------------------------------------------------------------------------------------
-    hipLaunchKernelGGL(k_train_composite_bwd, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
+    hipLaunchKernelGGL(k_train_composite_bwd<Fp16Net>, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
     SDN_TRY(sdn_ffh::backward_packed(H(L.dcol_out), ws + L.pk_col_b, H(L.col_hidden), M, kColIn, kColW, kColL, ACT_RELU, 1, H(L.col_bwd), H(L.dcol_in), st));
     const SigmaBwd sb{H(L.dh0), H(L.dcol_in), H(L.h1), H(L.w_sigma0), H(L.w_sigma1), H(L.dh), H(L.dh1), H(L.denc), M};
     hipLaunchKernelGGL(k_train_sigma_bwd, dim3(sdn_div_up(M, 32u)), dim3(64), 0, st, sb);
     SDN_TRY(sdn_grid_encode_backward_det(ws + L.denc, F(L.xdef), s->grid_offsets, ws + L.g_table, M, 3, 2, kLevels, s->grid_S, s->grid_H,
-                                         no_deform_grad ? nullptr : ws + L.dy_dx, no_deform_grad ? nullptr : ws + L.dx16, 1, 0, 0, SDN_F16,
+                                         no_deform_grad ? nullptr : ws + L.dy_dx, no_deform_grad ? nullptr : ws + L.dx, 1, 0, 0, SDN_F16,
                                          s->det_scratch, st));
     sdn_ffh::DwJob jobs[16];
     uint32_t nj = 0;
     dw_job_list(L, ws, M, jobs, nj);
     if (!no_deform_grad) {
-        hipLaunchKernelGGL(k_train_deform_grad, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, H(L.dx16), M, s->bound, H(L.ddef));
+        hipLaunchKernelGGL(k_train_deform_grad<_Float16>, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, H(L.dx), M, s->bound, H(L.ddef));
         SDN_TRY(sdn_ffh::backward_packed(H(L.ddef), ws + L.pk_def_b, H(L.def_hidden), M, kDefIn, kDefW, kDefL, ACT_RELU, 0, H(L.def_bwd), nullptr, st));
         SDN_TRY(sdn_ffh::dw_jobs(jobs, nj, M, ws + L.dw_partial, st));
     } else {
@@ -886,14 +998,9 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
     const Prologue pr{hyper, s->adam_steps, s->loss_scale, s->growth_tracker, s->beta1, s->beta2, s->lr_table, s->lr_net, s->growth_factor, s->backoff_factor,
                       s->growth_interval, !freeze_deform, s->grad_divisor > 0.0f ? s->grad_divisor : 1.0f};
     hipLaunchKernelGGL(k_train_check, dim3(1024), dim3(256), 0, st, ck);
-    hipLaunchKernelGGL(k_train_prologue, dim3(1), dim3(1), 0, st, pr);
-    AdamArgs A{};
-    const uint32_t blocks = build_segments(s, L, A);
-    if (freeze_deform) for (uint32_t i = 1; i <= kDefL + 1; i++) A.seg[i].frozen = 1;
-    A.hyper = hyper;
-    A.one_minus_b1 = (float)(1.0 - s->beta1); A.b2 = (float)s->beta2; A.one_minus_b2 = (float)(1.0 - s->beta2); A.eps = (float)s->eps;
-    A.ema_keep = 1.0f - s->ema_decay;
-    (void)blocks;
+    hipLaunchKernelGGL(k_train_prologue<true>, dim3(1), dim3(1), 0, st, pr);
+    AdamArgs<_Float16> A{};
+    adam_args(s, L, hyper, freeze_deform, A);
     if (s->table_stream) {
         if (s->mode == 2) SDN_TRY(table_wait(s, st));           // (optimizer-only call: nothing above waited)
         hipStream_t ts = (hipStream_t)s->table_stream;
@@ -905,7 +1012,6 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
     } else {
         launch_adam(A, 0, SDN_TRAIN_N_PARAMS, st);
     }
-    #undef SDN_TRY
     return sdn_launch_status();
 }
 
@@ -913,7 +1019,9 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
 
 // =====================================================================================================================================
 // The training step in fp32 (the reference WITHOUT `-O`: the network in float32, the disabled GradScaler of nerf/utils.py:395):
-// sdn_train_step_f32.  The same phases, modes and workspace contract as sdn_train_step_f16; what differs:
+// sdn_train_step_f32.  The same phases, modes and workspace contract as sdn_train_step_f16.  Shared with it above: the march
+// (march_samples), the workspace (make_layout at 4-byte elements), the record checks (step_ok), and the encode, x + deform,
+// compositing, loss, deformation-gradient, prologue and Adam kernels instantiated for fp32 (float, Fp32Net, no scaler).  What differs:
 //   * every product and sum is fp32.  The three MLP chains run on v_mfma_f32_32x32x2_f32 (one wave = 32 samples, the sample on the
 //     lane): accumulator register v of output tile mt IS the B operand of the next layer for the k-pair (row, row + 4), row =
 //     32 mt + 8 (v / 4) + v % 4 -- the k-order is baked into the weight packing (k_f32_pack), as in field_f32.hip.  The backward chain
@@ -929,8 +1037,6 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
 namespace {
 
 typedef float f32x16v __attribute__((ext_vector_type(16)));
-constexpr uint32_t kDwChunk = 512;                      // samples per split-K chunk of the weight gradients
-constexpr uint32_t kDefIn32 = 80;                       // 76 frequency features padded to a multiple of 4 k-pairs
 
 __device__ __forceinline__ f32x16v mfma32(float a, float b, f32x16v c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float relu32(float x) { return x > 0.0f ? x : 0.0f; }
@@ -1166,45 +1272,6 @@ __global__ void __launch_bounds__(256) k_f32_dw_reduce(Dw32Args A, uint32_t chun
 }
 
 // ---- glue -------------------------------------------------------------------------------------------------------------------------
-// freq(x, 10) ++ freq(t, 6) in fp32 (freqencoder.cu:30-58; cosine = the sine shifted by pi / 2), rows of 80 (76 .. 79 zero)
-__global__ void __launch_bounds__(256) k_f32_encode(const float *__restrict__ xyzs, uint32_t M, float time, float *__restrict__ enc) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t b = t >> 4, j = t & 15u;
-    if (b >= M) return;
-    float *row = enc + (size_t)b * kDefIn32;
-    const float half_pi = 3.141592653589793f / 2;
-    if (j < 10) {
-        #pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float a = scalbnf(xyzs[(size_t)b * 3 + d], (int)j);
-            row[3 + 6 * j + d] = sinf(a + 0.0f);
-            row[6 + 6 * j + d] = sinf(a + half_pi);
-        }
-    } else if (j == 10) {
-        #pragma unroll
-        for (int d = 0; d < 3; d++) row[d] = xyzs[(size_t)b * 3 + d];
-    } else if (j == 11) {
-        row[63] = time;
-        #pragma unroll
-        for (int f = 0; f < 6; f++) {
-            const float a = scalbnf(time, f);
-            row[64 + 2 * f] = sinf(a + 0.0f);
-            row[65 + 2 * f] = sinf(a + half_pi);
-        }
-    } else if (j == 12) {
-        row[76] = 0; row[77] = 0; row[78] = 0; row[79] = 0;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_f32_xdef(const float *__restrict__ xyzs, const float *__restrict__ def_out, uint32_t M, int zero_deform,
-                                                  float bound, float *__restrict__ xdef) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= M * 3) return;
-    const uint32_t b = t / 3, d = t - b * 3;
-    const float v = xyzs[t] + (zero_deform ? 0.0f : def_out[(size_t)b * 16 + d]);
-    xdef[t] = (v + bound) / (2 * bound);
-}
-
 // sigma = density_scale * exp(h[0]) (trunc_exp forward, activation.py:5-11); the colour MLP's input row [SH(d, 4) 16 | sigma-MLP output 16]
 __global__ void __launch_bounds__(256) k_f32_sigma_post(const float *__restrict__ hout, const float *__restrict__ dirs, uint32_t M, float density_scale,
                                                         float *__restrict__ sigmas, float *__restrict__ col_in) {
@@ -1219,114 +1286,6 @@ __global__ void __launch_bounds__(256) k_f32_sigma_post(const float *__restrict_
     sigmas[b] = density_scale * expf(hout[(size_t)b * 16]);
 }
 
-struct Composite32 {
-    const float *sigmas, *deltas, *col_out, *hout;   // col_out [M,16] pre-sigmoid; hout [M,16] (column 0: log density)
-    const int32_t *rays;
-    const float *bg, *gt;
-    float *weights_sum, *depth, *image, *image_out, *sq_err;
-    float *dcol_out, *dh0;                           // backward: [M,16], [M]
-    uint32_t M, N;
-    float T_thresh, bg_value, density_scale;
-};
-
-__device__ __forceinline__ float sigmoid32(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ SampleTerms sample_terms32(const Composite32 &P, uint32_t idx, bool in_ray, float T_carry, float t_carry, uint32_t lane,
-                                                      float &T_next, float &t_next) {
-    SampleTerms s{};
-    float one_minus = 1.0f, d1 = 0.0f;
-    if (in_ray) {
-        s.delta0 = P.deltas[(size_t)idx * 2];
-        d1 = P.deltas[(size_t)idx * 2 + 1];
-        s.alpha = 1.0f - sdn_exp_cr(-P.sigmas[idx] * s.delta0);
-        one_minus = 1.0f - s.alpha;
-        #pragma unroll
-        for (int ch = 0; ch < 3; ch++) s.c[ch] = sigmoid32(P.col_out[(size_t)idx * 16 + ch]);
-    }
-    s.T = T_carry * wave_excl_product(one_minus, lane);
-    s.t = t_carry + wave_incl_sum(d1, lane);
-    s.on = in_ray && s.T >= P.T_thresh;
-    s.weight = s.on ? s.alpha * s.T : 0.0f;
-    T_next = __shfl(s.T * one_minus, 63);
-    t_next = __shfl(s.t, 63);
-    return s;
-}
-
-__global__ void __launch_bounds__(256) k_f32_composite_fwd(Composite32 P) {
-    const uint32_t lane = threadIdx.x & 63u, n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= P.N) return;
-    const uint32_t index = (uint32_t)P.rays[n * 3], offset = (uint32_t)P.rays[n * 3 + 1], count = (uint32_t)P.rays[n * 3 + 2];
-    float ws = 0, d = 0, r = 0, g = 0, b = 0;
-    if (count != 0 && offset + count <= P.M) {
-        float T_carry = 1.0f, t_carry = 0.0f;
-        for (uint32_t c0 = 0; c0 < count && T_carry >= P.T_thresh; c0 += 64) {
-            float T_next, t_next;
-            const SampleTerms s = sample_terms32(P, offset + c0 + lane, c0 + lane < count, T_carry, t_carry, lane, T_next, t_next);
-            ws += s.weight; d += s.weight * s.t;
-            r += s.weight * s.c[0]; g += s.weight * s.c[1]; b += s.weight * s.c[2];
-            T_carry = T_next; t_carry = t_next;
-        }
-        ws = wave_sum(ws); d = wave_sum(d); r = wave_sum(r); g = wave_sum(g); b = wave_sum(b);
-    }
-    if (lane == 0) {
-        P.weights_sum[index] = ws; P.depth[index] = d;
-        const float img[3] = {r, g, b};
-        float sq = 0.0f;
-        #pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            P.image[(size_t)index * 3 + ch] = img[ch];
-            const float bgc = P.bg ? P.bg[(size_t)index * 3 + ch] : P.bg_value;
-            const float pred = img[ch] + (1.0f - ws) * bgc;
-            const float e = pred - P.gt[(size_t)index * 3 + ch];
-            sq += e * e;
-            if (P.image_out) P.image_out[(size_t)index * 3 + ch] = pred;
-        }
-        P.sq_err[index] = sq;
-    }
-}
-
-// raymarching.cu:602-682 in fp32, plus the sigmoid's and trunc_exp's gradients (activation.py:12-17); the loss is unscaled
-__global__ void __launch_bounds__(256) k_f32_composite_bwd(Composite32 P) {
-    const uint32_t lane = threadIdx.x & 63u, n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= P.N) return;
-    const uint32_t index = (uint32_t)P.rays[n * 3], offset = (uint32_t)P.rays[n * 3 + 1], count = (uint32_t)P.rays[n * 3 + 2];
-    if (count == 0 || offset + count > P.M) return;
-    const float ws_final = P.weights_sum[index];
-    const float cg = (1.0f / (float)P.N) / 3.0f;
-    float gi[3], fin[3], gws = 0.0f;
-    #pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        fin[ch] = P.image[(size_t)index * 3 + ch];
-        const float bgc = P.bg ? P.bg[(size_t)index * 3 + ch] : P.bg_value;
-        const float pred = fin[ch] + (1.0f - ws_final) * bgc;
-        gi[ch] = ((pred - P.gt[(size_t)index * 3 + ch]) * 2.0f) * cg;
-        gws -= gi[ch] * bgc;
-    }
-    float T_carry = 1.0f, t_carry = 0.0f, acc_c[3] = {0, 0, 0};
-    for (uint32_t c0 = 0; c0 < count && T_carry >= P.T_thresh; c0 += 64) {
-        float T_next, t_next;
-        const uint32_t idx = offset + c0 + lane;
-        const SampleTerms s = sample_terms32(P, idx, c0 + lane < count, T_carry, t_carry, lane, T_next, t_next);
-        float run[3];
-        #pragma unroll
-        for (int ch = 0; ch < 3; ch++) run[ch] = acc_c[ch] + wave_incl_sum(s.weight * s.c[ch], lane);
-        if (s.on) {
-            const float T_after = s.T * (1.0f - s.alpha);
-            const float g_sigma = s.delta0 * (gi[0] * (T_after * s.c[0] - (fin[0] - run[0])) + gi[1] * (T_after * s.c[1] - (fin[1] - run[1])) +
-                                              gi[2] * (T_after * s.c[2] - (fin[2] - run[2])) + gws * (1.0f - ws_final));
-            float dc[3];
-            #pragma unroll
-            for (int ch = 0; ch < 3; ch++) dc[ch] = ((gi[ch] * s.weight) * (1.0f - s.c[ch])) * s.c[ch];
-            *reinterpret_cast<float4 *>(P.dcol_out + (size_t)idx * 16) = float4{dc[0], dc[1], dc[2], 0.0f};
-            const float x = fminf(fmaxf(P.hout[(size_t)idx * 16], -15.0f), 15.0f);
-            P.dh0[idx] = (g_sigma * P.density_scale) * expf(x);
-        }
-        #pragma unroll
-        for (int ch = 0; ch < 3; ch++) acc_c[ch] = __shfl(run[ch], 63);
-        T_carry = T_next; t_carry = t_next;
-    }
-}
-
 // d(sigma-MLP output) = [trunc_exp gradient | columns 17 .. 31 of the colour MLP's input gradient]
 __global__ void __launch_bounds__(256) k_f32_dh(const float *__restrict__ dh0, const float *__restrict__ dcol_in, uint32_t M, float *__restrict__ dh) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1335,158 +1294,17 @@ __global__ void __launch_bounds__(256) k_f32_dh(const float *__restrict__ dh0, c
     dh[t] = c == 0 ? dh0[b] : dcol_in[(size_t)b * kColIn + 16 + c];
 }
 
-// the deformation MLP's output gradient: the grid's input gradient / (2 bound) in columns 0 .. 2 of 16
-__global__ void __launch_bounds__(256) k_f32_deform_grad(const float *__restrict__ dx, uint32_t M, float bound, float *__restrict__ ddef) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= M) return;
-    float4 *row = reinterpret_cast<float4 *>(ddef + (size_t)b * 16);
-    row[0] = float4{dx[(size_t)b * 3] / (2 * bound), dx[(size_t)b * 3 + 1] / (2 * bound), dx[(size_t)b * 3 + 2] / (2 * bound), 0.0f};
-    row[1] = float4{0, 0, 0, 0}; row[2] = float4{0, 0, 0, 0}; row[3] = float4{0, 0, 0, 0};
-}
-
-// ---- optimizer --------------------------------------------------------------------------------------------------------------------
-struct Prologue32 { Hyper *hyper; float *steps; double beta1, beta2, lr_table, lr_net; int deform_active; };
-
-// bias corrections in double, as torch's Adam computes them on the host; no scaler: every step counts
-__global__ void k_f32_prologue(Prologue32 P) {
-    Hyper *h = P.hyper;
-    P.steps[0] += 1.0f;
-    if (P.deform_active) P.steps[1] += 1.0f;
-    for (int g = 0; g < 2; g++) {
-        const double st = (double)P.steps[g] > 0 ? (double)P.steps[g] : 1.0;
-        const double bc1 = 1.0 - pow(P.beta1, st), bc2 = 1.0 - pow(P.beta2, st);
-        h->step_size[0][g] = (float)(P.lr_table / bc1);
-        h->step_size[1][g] = (float)(P.lr_net / bc1);
-        h->bc2_sqrt[g] = (float)sqrt(bc2);
-    }
-}
-
-struct AdamSeg32 {
-    float *p, *m, *v, *ema;
-    float *g;                         // fp32 gradient, element (r, c) at r * ld + c
-    uint32_t n, cols, ld, split;
-    uint32_t lr_idx, group, zero_grad, frozen, blk_begin;
-};
-struct Adam32Args {
-    AdamSeg32 seg[SDN_TRAIN_N_PARAMS];
-    uint32_t nseg;
-    const Hyper *hyper;
-    float one_minus_b1, b2, one_minus_b2, eps, ema_keep;
-};
-
-// torch.optim.Adam (_single_tensor_adam) on the unscaled fp32 gradients, torch_ema's shadow, and the table gradient cleared
-__global__ void __launch_bounds__(256) k_f32_adam(Adam32Args A) {
-    uint32_t s = 0;
-    for (uint32_t k = 1; k < A.nseg; k++) s = blockIdx.x >= A.seg[k].blk_begin ? k : s;
-    const AdamSeg32 &S = A.seg[s];
-    const Hyper &H = *A.hyper;
-    const bool update = !S.frozen;
-    const float step_size = H.step_size[S.lr_idx][S.group], bc2s = H.bc2_sqrt[S.group];
-    const uint32_t first = (blockIdx.x - S.blk_begin) * 1024u;
-    if (S.cols == S.ld && first + 1024u <= S.n && !S.ema && update) {
-        const uint32_t i = first + 4u * threadIdx.x;
-        float4 p = *reinterpret_cast<const float4 *>(S.p + i), m = *reinterpret_cast<const float4 *>(S.m + i), v = *reinterpret_cast<const float4 *>(S.v + i);
-        const float4 g4 = *reinterpret_cast<const float4 *>(S.g + i);
-        float *pp = &p.x, *mm = &m.x, *vv = &v.x;
-        const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
-        #pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const float g = gg[e];
-            mm[e] = mm[e] + A.one_minus_b1 * (g - mm[e]);
-            vv[e] = vv[e] * A.b2 + (A.one_minus_b2 * g) * g;
-            const float denom = sqrtf(vv[e]) / bc2s + A.eps;
-            pp[e] = pp[e] - step_size * (mm[e] / denom);
-        }
-        *reinterpret_cast<float4 *>(S.m + i) = m; *reinterpret_cast<float4 *>(S.v + i) = v; *reinterpret_cast<float4 *>(S.p + i) = p;
-        if (S.zero_grad) *reinterpret_cast<float4 *>(S.g + i) = float4{0, 0, 0, 0};
-        return;
-    }
-    const uint32_t base = first + threadIdx.x;
-    #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t i = base + 256u * k;
-        if (i >= S.n) break;
-        uint32_t j = i;
-        if (S.cols != S.ld) { const uint32_t r = i / S.cols, c = i - r * S.cols; j = r * S.ld + c + (c >= S.split ? 1u : 0u); }
-        float p = S.p[i];
-        if (update) {
-            const float g = S.g[j];
-            float m = S.m[i], v = S.v[i];
-            m = m + A.one_minus_b1 * (g - m);
-            v = v * A.b2 + (A.one_minus_b2 * g) * g;
-            const float denom = sqrtf(v) / bc2s + A.eps;
-            p = p - step_size * (m / denom);
-            S.m[i] = m; S.v[i] = v; S.p[i] = p;
-        }
-        if (S.zero_grad) S.g[j] = 0.0f;
-        if (S.ema) { const float e = S.ema[i]; S.ema[i] = e - (e - p) * A.ema_keep; }
-    }
-}
-
-// ---- workspace --------------------------------------------------------------------------------------------------------------------
-struct Layout32 {
-    uint64_t total;
-    uint64_t g_table, hyper, pk;
-    uint64_t nears, fars, noises, rays, pts, march, set_stride;
-    uint64_t dcol_out, dh0;
-    uint64_t enc_in, def_hidden, def_out, xdef, grid_out, dy_dx, h1, hout, sigmas, col_in, col_hidden, col_out;
-    uint64_t weights_sum, depth, image, sq_err;
-    uint64_t col_bwd, dcol_in, dh, dh1, denc, dx, ddef, def_bwd;
-    uint64_t g_deform, g_sigma0, g_sigma1, g_color, dw_partial;
-};
-
-// packed floats of one product: tiles x steps x 64
-constexpr uint64_t pk_floats(uint32_t rows, uint32_t steps) { return (uint64_t)((rows + 31u) / 32u) * steps * 64u; }
-// forward chain: first layer (in / 2 steps), L - 1 hidden, last (1 tile); backward chain: last^T (8 steps), L - 1 hidden^T, first^T if dX
-constexpr uint64_t chain_fwd_floats(uint32_t in, uint32_t W, uint32_t L) { return pk_floats(W, in / 2) + (L - 1) * pk_floats(W, W / 2) + pk_floats(16, W / 2); }
-constexpr uint64_t chain_bwd_floats(uint32_t in, uint32_t W, uint32_t L, bool dx) { return pk_floats(W, 8) + (L - 1) * pk_floats(W, W / 2) + (dx ? pk_floats(in, W / 2) : 0); }
-constexpr uint64_t kPkDefF = 0, kPkDefB = kPkDefF + chain_fwd_floats(kDefIn32, kDefW, kDefL);
-constexpr uint64_t kPkSigF = kPkDefB + chain_bwd_floats(kDefIn32, kDefW, kDefL, false);
-constexpr uint64_t kPkSigB = kPkSigF + chain_fwd_floats(kSigIn, kSigW, 1);
-constexpr uint64_t kPkColF = kPkSigB + chain_bwd_floats(kSigIn, kSigW, 1, true);
-constexpr uint64_t kPkColB = kPkColF + chain_fwd_floats(kColIn, kColW, kColL);
-constexpr uint64_t kPkTotal = kPkColB + chain_bwd_floats(kColIn, kColW, kColL, true);
-constexpr uint32_t kDwTotal = kDefFlat + kSigW * kSigIn + kSigOut * kSigW + kColFlat;
-
-Layout32 make_layout32(uint32_t N, uint32_t M, uint32_t max_steps, uint64_t table_entries) {
-    Layout32 L{};
-    uint64_t at = 0;
-    auto take = [&](uint64_t bytes) { const uint64_t o = at; at = (at + bytes + 255u) & ~(uint64_t)255u; return o; };
-    const uint64_t m = M, n = N;
-    L.g_table = take(table_entries * 4);
-    L.hyper = take(sizeof(Hyper));
-    L.pk = take(kPkTotal * 4);
-    L.nears = take(n * 4);  L.fars = take(n * 4);  L.noises = take(n * 4);  L.rays = take(n * 12);
-    L.pts = take(m * 32);
-    L.march = take(sdn_march_rays_train_scratch_bytes(N, max_steps));
-    L.set_stride = at - L.nears;
-    at += L.set_stride;
-    L.dcol_out = take(m * 64);  L.dh0 = take(m * 4);              // zero-filled by every step (one fill: dh0 follows dcol_out)
-    L.enc_in = take(m * kDefIn32 * 4);  L.def_hidden = take(m * kDefL * kDefW * 4);  L.def_out = take(m * 64);
-    L.xdef = take(m * 12);  L.grid_out = take(m * kLevels * 8);  L.dy_dx = take(m * kLevels * 24);
-    L.h1 = take(m * kSigW * 4);  L.hout = take(m * kSigOut * 4);  L.sigmas = take(m * 4);
-    L.col_in = take(m * kColIn * 4);  L.col_hidden = take(m * kColL * kColW * 4);  L.col_out = take(m * 64);
-    L.weights_sum = take(n * 4);  L.depth = take(n * 4);  L.image = take(n * 12);  L.sq_err = take(n * 4);
-    L.col_bwd = take(m * kColL * kColW * 4);  L.dcol_in = take(m * kColIn * 4);
-    L.dh = take(m * kSigOut * 4);  L.dh1 = take(m * kSigW * 4);  L.denc = take(m * kLevels * 8);  L.dx = take(m * 12);
-    L.ddef = take(m * 64);  L.def_bwd = take(m * kDefL * kDefW * 4);
-    L.g_deform = take(kDefFlat * 4);  L.g_sigma0 = take(kSigW * kSigIn * 4);  L.g_sigma1 = take(kSigOut * kSigW * 4);  L.g_color = take(kColFlat * 4);
-    L.dw_partial = take((uint64_t)sdn_div_up(M, kDwChunk) * kDwTotal * 4);
-    L.total = at;
-    return L;
-}
-
 // the 13 weight-gradient products (deformation MLP first: the canonical frame launches only the rest)
-uint32_t dw32_jobs(const Layout32 &L, unsigned char *ws, uint32_t M, bool with_deform, Dw32Args &A) {
+uint32_t dw32_jobs(const Layout &L, unsigned char *ws, uint32_t M, bool with_deform, Dw32Args &A) {
     auto F = [&](uint64_t off) { return (float *)(ws + off); };
     const size_t mw = (size_t)M * kDefW, mc = (size_t)M * kColW;
     Dw32 j[13];
     uint32_t n = 0;
     if (with_deform) {
-        j[n++] = {F(L.def_bwd), F(L.enc_in), F(L.g_deform), kDefW, kDefIn32, kDefW, kDefIn32, 0};
+        j[n++] = {F(L.def_bwd), F(L.enc_in), F(L.g_deform), kDefW, kDefIn, kDefW, kDefIn, 0};
         for (uint32_t l = 1; l < kDefL; l++)
-            j[n++] = {F(L.def_bwd) + l * mw, F(L.def_hidden) + (l - 1) * mw, F(L.g_deform) + kDefW * kDefIn32 + (l - 1) * kDefW * kDefW, kDefW, kDefW, kDefW, kDefW, 0};
-        j[n++] = {F(L.ddef), F(L.def_hidden) + (kDefL - 1) * mw, F(L.g_deform) + kDefW * kDefIn32 + (kDefL - 1) * kDefW * kDefW, 16, kDefW, 16, kDefW, 0};
+            j[n++] = {F(L.def_bwd) + l * mw, F(L.def_hidden) + (l - 1) * mw, F(L.g_deform) + kDefW * kDefIn + (l - 1) * kDefW * kDefW, kDefW, kDefW, kDefW, kDefW, 0};
+        j[n++] = {F(L.ddef), F(L.def_hidden) + (kDefL - 1) * mw, F(L.g_deform) + kDefW * kDefIn + (kDefL - 1) * kDefW * kDefW, 16, kDefW, 16, kDefW, 0};
     }
     j[n++] = {F(L.dh1), F(L.grid_out), F(L.g_sigma0), kSigW, 0, kSigW, kSigIn, 1};
     j[n++] = {F(L.dh), F(L.h1), F(L.g_sigma1), kSigOut, kSigW, kSigOut, kSigW, 0};
@@ -1507,7 +1325,7 @@ uint32_t dw32_jobs(const Layout32 &L, unsigned char *ws, uint32_t M, bool with_d
 }
 
 // both directions of the three MLPs from the fp32 parameters (params 1 .. 13), one launch
-void pack32_jobs(const SdnTrainStep *s, const Layout32 &L, unsigned char *ws, Pack32Args &A) {
+void pack32_jobs(const SdnTrainStep *s, const Layout &L, unsigned char *ws, Pack32Args &A) {
     float *pk = (float *)(ws + L.pk);
     uint32_t n = 0, thr = 0;
     auto add = [&](uint32_t pi, uint64_t &at, uint32_t out_rows, uint32_t steps, int transpose, int acc, uint32_t rows_w, uint32_t cols_w, uint32_t split) {
@@ -1522,7 +1340,7 @@ void pack32_jobs(const SdnTrainStep *s, const Layout32 &L, unsigned char *ws, Pa
     const uint32_t NS = 0xFFFFFFFFu;
     // deformation: fwd first [128, 80 (76)], hidden [128,128] x 6, last [16 (3), 128]; bwd last^T, hidden^T (7 .. 2), no first^T
     uint64_t at = kPkDefF;
-    add(1, at, kDefW, kDefIn32 / 2, 0, 0, kDefW, kDefCols, NS);
+    add(1, at, kDefW, kDefIn / 2, 0, 0, kDefW, kDefCols, NS);
     for (uint32_t l = 1; l < kDefL; l++) add(1 + l, at, kDefW, kDefW / 2, 0, 1, kDefW, kDefW, NS);
     add(8, at, 16, kDefW / 2, 0, 1, 3, kDefW, NS);
     at = kPkDefB;
@@ -1552,80 +1370,18 @@ uint32_t pack32_threads(const Pack32Args &A) {
     return J.begin + J.tiles * J.steps * 64u;
 }
 
-uint32_t build_segments32(const SdnTrainStep *s, const Layout32 &L, Adam32Args &A) {
-    unsigned char *ws = (unsigned char *)s->workspace;
-    auto F = [&](uint64_t off) { return (float *)(ws + off); };
-    struct Place { uint64_t g; uint32_t off, rows, cols, ld, lr, group; };
-    Place pl[SDN_TRAIN_N_PARAMS];
-    const uint32_t table_n = (uint32_t)s->grid_offsets[kLevels] * 2u;
-    pl[0] = {L.g_table, 0, table_n / 2, 2, 2, 0, 0};
-    pl[1] = {L.g_deform, 0, kDefW, kDefCols, kDefIn32, 1, 1};
-    for (uint32_t i = 1; i < kDefL; i++) pl[1 + i] = {L.g_deform, kDefW * kDefIn32 + (i - 1) * kDefW * kDefW, kDefW, kDefW, kDefW, 1, 1};
-    pl[8] = {L.g_deform, kDefW * kDefIn32 + (kDefL - 1) * kDefW * kDefW, 3, kDefW, kDefW, 1, 1};
-    pl[9] = {L.g_sigma0, 0, kSigW, kSigIn, kSigIn, 1, 0};
-    pl[10] = {L.g_sigma1, 0, kSigOut, kSigW, kSigW, 1, 0};
-    pl[11] = {L.g_color, 0, kColW, kColCols, kColIn, 1, 0};
-    pl[12] = {L.g_color, kColW * kColIn, kColW, kColW, kColW, 1, 0};
-    pl[13] = {L.g_color, kColW * kColIn + kColW * kColW, 3, kColW, kColW, 1, 0};
-    uint32_t blk = 0;
-    for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) {
-        const SdnTrainParam &q = s->params[i];
-        AdamSeg32 &S = A.seg[i];
-        S.p = q.param; S.m = q.exp_avg; S.v = q.exp_avg_sq; S.ema = q.ema;
-        S.g = F(pl[i].g) + pl[i].off;
-        S.n = pl[i].rows * pl[i].cols; S.cols = pl[i].cols; S.ld = pl[i].ld; S.split = i == 11 ? 16u : 0xFFFFFFFFu;
-        S.lr_idx = pl[i].lr; S.group = pl[i].group; S.zero_grad = i == 0; S.frozen = 0; S.blk_begin = blk;
-        blk += sdn_div_up(S.n, 1024u);
-    }
-    A.nseg = SDN_TRAIN_N_PARAMS;
-    return blk;
-}
-
-bool step_ok32(const SdnTrainStep *s) {
-    if (!s || !s->workspace || ((uintptr_t)s->workspace & 255u)) return false;
-    if (s->mode < 0 || s->mode > 1) return false;                                  // no optimizer-only mode (data parallelism)
-    if (s->table_stream || s->table_ready || s->table_done) return false;         // no overlapped table pass
-    if (s->phase < 0 || s->phase > 2) return false;
-    if (s->phase != 2 && (!s->rays_o || !s->rays_d || !s->bitfield || !s->aabb || !s->counter)) return false;
-    if (s->phase != 1 && (!s->target || !s->loss_out)) return false;
-    if (s->N == 0 || s->M == 0 || s->max_steps == 0 || s->bound <= 0 || s->grid_offsets[kLevels] <= 0) return false;
-    for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) if (!s->params[i].param) return false;
-    if (s->mode == 0) {
-        if (!s->adam_steps) return false;
-        for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) {
-            const bool frozen = s->deform_frozen && i >= 1 && i <= (int)kDefL + 1;
-            if (!frozen && (!s->params[i].exp_avg || !s->params[i].exp_avg_sq)) return false;
-        }
-    }
-    const uint64_t expect[SDN_TRAIN_N_PARAMS] = {(uint64_t)s->grid_offsets[kLevels] * 2, kDefW * kDefCols, kDefW * kDefW, kDefW * kDefW, kDefW * kDefW, kDefW * kDefW,
-                                                 kDefW * kDefW, kDefW * kDefW, 3 * kDefW, kSigW * kSigIn, kSigOut * kSigW, kColW * kColCols, kColW * kColW, 3 * kColW};
-    for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) if (s->params[i].n != expect[i]) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" {
 
 int sdn_train_layout_f32(uint32_t N, uint32_t M, uint32_t max_steps, const int32_t *grid_offsets, SdnTrainLayout *out) {
-    if (!grid_offsets || !out || N == 0 || M == 0 || max_steps == 0 || grid_offsets[kLevels] <= 0) return SDN_E_BADARG;
-    const Layout32 L = make_layout32(N, M, max_steps, (uint64_t)grid_offsets[kLevels] * 2);
-    *out = SdnTrainLayout{};
-    out->total_bytes = L.total;
-    // no parameter copies in fp32: the kernels read the parameters themselves (w_* stay 0)
-    out->g_table = L.g_table; out->g_deform = L.g_deform; out->g_sigma0 = L.g_sigma0; out->g_sigma1 = L.g_sigma1; out->g_color = L.g_color;
-    out->xyzs = L.pts; out->dirs = L.pts + (uint64_t)M * 12; out->deltas = L.pts + (uint64_t)M * 24; out->rays = L.rays;
-    out->sample_set_stride = L.set_stride;
-    out->sigmas = L.sigmas; out->weights_sum = L.weights_sum; out->depth = L.depth; out->image = L.image;
-    out->found_inf = L.hyper + offsetof(Hyper, found_inf);
-    return 0;
+    return fill_layout(N, M, max_steps, grid_offsets, out, true);
 }
 
 int sdn_train_refresh_f32(const SdnTrainStep *s, void *stream) {
-    if (!s || !s->workspace || ((uintptr_t)s->workspace & 255u) || s->N == 0 || s->M == 0 || s->max_steps == 0 || s->grid_offsets[kLevels] <= 0)
-        return SDN_E_BADARG;
+    if (!workspace_ok(s) || s->N == 0 || s->M == 0 || s->max_steps == 0 || s->grid_offsets[kLevels] <= 0) return SDN_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    const Layout32 L = make_layout32(s->N, s->M, s->max_steps, (uint64_t)s->grid_offsets[kLevels] * 2);
+    const Layout L = step_layout(s, true);
     unsigned char *ws = (unsigned char *)s->workspace;
     if (hipMemsetAsync(ws + L.g_table, 0, (uint64_t)s->grid_offsets[kLevels] * 8, st) != hipSuccess || hipMemsetAsync(ws + L.hyper, 0, sizeof(Hyper), st) != hipSuccess)
         return sdn_launch_status();
@@ -1633,10 +1389,10 @@ int sdn_train_refresh_f32(const SdnTrainStep *s, void *stream) {
 }
 
 int sdn_train_step_f32(const SdnTrainStep *s, void *stream) {
-    if (!step_ok32(s)) return SDN_E_BADARG;
+    if (!step_ok(s, true)) return SDN_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t N = s->N, M = s->M;
-    const Layout32 L = make_layout32(N, M, s->max_steps, (uint64_t)s->grid_offsets[kLevels] * 2);
+    const Layout L = step_layout(s, true);
     unsigned char *ws = (unsigned char *)s->workspace;
     auto F = [&](uint64_t off) { return (float *)(ws + off); };
     Hyper *hyper = (Hyper *)(ws + L.hyper);
@@ -1644,19 +1400,10 @@ int sdn_train_step_f32(const SdnTrainStep *s, void *stream) {
     const int no_deform_grad = zero_deform || s->deform_frozen;
     const int freeze_deform = zero_deform || s->deform_frozen;
     int rc;
-    #define SDN_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
     const uint64_t set_off = s->sample_set ? L.set_stride : 0;
     float *xyzs = F(L.pts + set_off), *dirs = xyzs + (size_t)M * 3, *deltas = xyzs + (size_t)M * 6;
     const int32_t *ray_table = (const int32_t *)(ws + L.rays + set_off);
-    if (s->phase != 2) {
-        // ---- rays -> samples: the fp16 step's phase 0 / 1 (nothing of it has a dtype) ----------------------------------------------
-        hipLaunchKernelGGL(k_train_rays, dim3(sdn_div_up(N, 256u)), dim3(256), 0, st, F(L.noises + set_off), s->noises, N, s->noise_seed, s->perturb, s->counter);
-        SDN_TRY(sdn_near_far_from_aabb(s->rays_o, s->rays_d, s->aabb, N, s->min_near, F(L.nears + set_off), F(L.fars + set_off), st));
-        if (hipMemsetAsync(ws + L.pts + set_off, 0, (uint64_t)M * 32, st) != hipSuccess) return sdn_launch_status();
-        SDN_TRY(sdn_int::march_rays_train(s->rays_o, s->rays_d, s->bitfield, s->bound, s->dt_gamma, s->max_steps, N, s->cascade, s->grid_size, M,
-                                          F(L.nears + set_off), F(L.fars + set_off), xyzs, dirs, deltas, (int32_t *)(ws + L.rays + set_off), s->counter,
-                                          F(L.noises + set_off), ws + L.march + set_off, s->cull_grid, st));
-    }
+    if (s->phase != 2) SDN_TRY(march_samples(s, L, set_off, st));
     if (s->phase == 1) return sdn_launch_status();
     const float *table = s->params[0].param;
     float *g_table = F(L.g_table);
@@ -1672,20 +1419,21 @@ int sdn_train_step_f32(const SdnTrainStep *s, void *stream) {
     const dim3 waves(sdn_div_up(M, 32u));
 
     // ---- forward (network.py:123-169 in fp32) -------------------------------------------------------------------------------------------
-    hipLaunchKernelGGL(k_f32_encode, dim3(sdn_div_up(M * 16u, 256u)), dim3(256), 0, st, xyzs, M, s->time, F(L.enc_in));
-    hipLaunchKernelGGL((k_f32_chain_fwd<kDefIn32, kDefW / 32, kDefL, false>), waves, dim3(64), 0, st, F(L.enc_in), pk + kPkDefF, M, F(L.def_hidden), F(L.def_out));
-    hipLaunchKernelGGL(k_f32_xdef, dim3(sdn_div_up(M * 3u, 256u)), dim3(256), 0, st, xyzs, F(L.def_out), M, zero_deform, s->bound, F(L.xdef));
+    hipLaunchKernelGGL(k_train_encode<float>, dim3(sdn_div_up(M * 16u, 256u)), dim3(256), 0, st, xyzs, M, s->time, F(L.enc_in), nullptr, nullptr, 0u);
+    hipLaunchKernelGGL((k_f32_chain_fwd<kDefIn, kDefW / 32, kDefL, false>), waves, dim3(64), 0, st, F(L.enc_in), pk + kPkDefF, M, F(L.def_hidden), F(L.def_out));
+    hipLaunchKernelGGL(k_train_xdef<float>, dim3(sdn_div_up(M * 3u, 256u)), dim3(256), 0, st, xyzs, F(L.def_out), M, zero_deform, s->bound, F(L.xdef));
     SDN_TRY(sdn_grid_encode_forward(F(L.xdef), table, s->grid_offsets, F(L.grid_out), M, 3, 2, kLevels, s->grid_S, s->grid_H,
                                     no_deform_grad ? nullptr : F(L.dy_dx), 1, 0, 0, SDN_F32, st));
     hipLaunchKernelGGL((k_f32_chain_fwd<kSigIn, kSigW / 32, 1, true>), waves, dim3(64), 0, st, F(L.grid_out), pk + kPkSigF, M, F(L.h1), F(L.hout));
     hipLaunchKernelGGL(k_f32_sigma_post, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, F(L.hout), dirs, M, s->density_scale, F(L.sigmas), F(L.col_in));
     hipLaunchKernelGGL((k_f32_chain_fwd<kColIn, kColW / 32, kColL, false>), waves, dim3(64), 0, st, F(L.col_in), pk + kPkColF, M, F(L.col_hidden), F(L.col_out));
     // ---- compositing, loss and their gradients, one wave per ray -------------------------------------------------------------------------
-    const Composite32 ca{F(L.sigmas), deltas, F(L.col_out), F(L.hout), ray_table, s->bg_color, s->target, F(L.weights_sum), F(L.depth), F(L.image),
-                         s->image_out, F(L.sq_err), F(L.dcol_out), F(L.dh0), M, N, s->T_thresh, s->bg_value, s->density_scale};
-    hipLaunchKernelGGL(k_f32_composite_fwd, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
+    const CompositeArgs<Fp32Net> ca{F(L.sigmas), deltas, F(L.col_out), F(L.hout), ray_table, s->bg_color, s->target, nullptr, F(L.weights_sum), F(L.depth),
+                                    F(L.image), s->image_out, F(L.sq_err), F(L.dcol_out), F(L.dh0), M, N, s->T_thresh, s->bg_value,
+                                    s->density_scale};
+    hipLaunchKernelGGL(k_train_composite_fwd<Fp32Net>, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
     hipLaunchKernelGGL(k_train_loss, dim3(1), dim3(1024), 0, st, F(L.sq_err), N, s->loss_out);
-    hipLaunchKernelGGL(k_f32_composite_bwd, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
+    hipLaunchKernelGGL(k_train_composite_bwd<Fp32Net>, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
 
     // ---- backward through the field ----------------------------------------------------------------------------------------------------
     hipLaunchKernelGGL((k_f32_chain_bwd<kColW / 32, kColL, 1, false>), waves, dim3(64), 0, st, F(L.dcol_out), pk + kPkColB, F(L.col_hidden), M,
@@ -1699,7 +1447,7 @@ int sdn_train_step_f32(const SdnTrainStep *s, void *stream) {
         SDN_TRY(sdn_grid_encode_backward(F(L.denc), F(L.xdef), s->grid_offsets, g_table, M, 3, 2, kLevels, s->grid_S, s->grid_H,
                                          no_deform_grad ? nullptr : F(L.dy_dx), no_deform_grad ? nullptr : F(L.dx), 1, 0, 0, SDN_F32, st));
     if (!no_deform_grad) {
-        hipLaunchKernelGGL(k_f32_deform_grad, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, F(L.dx), M, s->bound, F(L.ddef));
+        hipLaunchKernelGGL(k_train_deform_grad<float>, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, F(L.dx), M, s->bound, F(L.ddef));
         hipLaunchKernelGGL((k_f32_chain_bwd<kDefW / 32, kDefL, 0, false>), waves, dim3(64), 0, st, F(L.ddef), pk + kPkDefB, F(L.def_hidden), M,
                            F(L.def_bwd), (float *)nullptr);
     } else if (hipMemsetAsync(ws + L.g_deform, 0, kDefFlat * 4, st) != hipSuccess) {      // no gradient: zeros, not last step's values
@@ -1713,16 +1461,13 @@ int sdn_train_step_f32(const SdnTrainStep *s, void *stream) {
     if (s->mode == 1) return sdn_launch_status();
 
     // ---- optimizer: Adam on the unscaled gradients, every step counts (the disabled GradScaler) -------------------------------------------
-    const Prologue32 pr{hyper, s->adam_steps, s->beta1, s->beta2, s->lr_table, s->lr_net, !freeze_deform};
-    hipLaunchKernelGGL(k_f32_prologue, dim3(1), dim3(1), 0, st, pr);
-    Adam32Args A{};
-    const uint32_t blocks = build_segments32(s, L, A);
-    if (freeze_deform) for (uint32_t i = 1; i <= kDefL + 1; i++) A.seg[i].frozen = 1;
-    A.hyper = hyper;
-    A.one_minus_b1 = (float)(1.0 - s->beta1); A.b2 = (float)s->beta2; A.one_minus_b2 = (float)(1.0 - s->beta2); A.eps = (float)s->eps;
-    A.ema_keep = 1.0f - s->ema_decay;
-    hipLaunchKernelGGL(k_f32_adam, dim3(blocks), dim3(256), 0, st, A);
-    #undef SDN_TRY
+    Prologue pr{};                     // (no scaler: loss scale, growth tracker and found_inf are not read)
+    pr.hyper = hyper; pr.steps = s->adam_steps; pr.beta1 = s->beta1; pr.beta2 = s->beta2; pr.lr_table = s->lr_table; pr.lr_net = s->lr_net;
+    pr.deform_active = !freeze_deform;
+    hipLaunchKernelGGL(k_train_prologue<false>, dim3(1), dim3(1), 0, st, pr);
+    AdamArgs<float> A{};
+    const uint32_t blocks = adam_args(s, L, hyper, freeze_deform, A);
+    hipLaunchKernelGGL(k_train_adam<float>, dim3(blocks), dim3(256), 0, st, A);
     return sdn_launch_status();
 }
 
