@@ -80,8 +80,9 @@ def _pack_layer(W, n_mt, kmaps):
     return blocks.reshape(-1, 64, 8)
 
 
-def pack_weights(model):
-    """All Linear weights of the field network in the kernel's block order: [240, 64, 8] float16."""
+def layer_plan(model):
+    """(W [out, in] float32, m-tile count, k-maps) of the twelve Linear layers in the kernels' stage order D0 | D1..D6 | D7 S0 S1 C0 C1 C2
+    (D0 without the 13 time-encoding columns: they become the bias row `bias0`)."""
     g = lambda m: m.weight.detach().float().cpu().numpy()  # noqa: E731
     dn, sn, cn = model.deform_net, model.sigma_net, model.color_net
     assert len(dn) == 8 and len(sn) == 2 and len(cn) == 3, "fused kernel is built for the dnerf network shape"
@@ -89,32 +90,148 @@ def pack_weights(model):
     assert g(cn[0]).shape == (64, 31) and g(cn[1]).shape == (64, 64) and g(cn[2]).shape == (3, 64)
     hidden128 = [_acc_kmap(t, s) for t in range(4) for s in range(2)]
     hidden64 = [_acc_kmap(t, s) for t in range(2) for s in range(2)]
-    parts = [_pack_layer(g(dn[0])[:, :63], 4, [_d0_kmap(s) for s in range(4)])]
-    parts += [_pack_layer(g(dn[l]), 4, hidden128) for l in range(1, 7)]
-    parts.append(_pack_layer(g(dn[7]), 1, hidden128))
-    parts.append(_pack_layer(g(sn[0]), 2, [_s0_kmap(s) for s in range(2)]))
-    parts.append(_pack_layer(g(sn[1]), 1, hidden64))
-    parts.append(_pack_layer(g(cn[0]), 2, [_c0_kmap(s) for s in range(2)]))
-    parts.append(_pack_layer(g(cn[1]), 2, hidden64))
-    parts.append(_pack_layer(g(cn[2]), 1, hidden64))
-    packed = np.concatenate(parts, axis=0)
+    yield g(dn[0])[:, :63], 4, [_d0_kmap(s) for s in range(4)]
+    for l in range(1, 7):
+        yield g(dn[l]), 4, hidden128
+    yield g(dn[7]), 1, hidden128
+    yield g(sn[0]), 2, [_s0_kmap(s) for s in range(2)]
+    yield g(sn[1]), 1, hidden64
+    yield g(cn[0]), 2, [_c0_kmap(s) for s in range(2)]
+    yield g(cn[1]), 2, hidden64
+    yield g(cn[2]), 1, hidden64
+
+
+def pack_weights(model):
+    """All Linear weights of the field network in the kernel's block order: [240, 64, 8] float16."""
+    packed = np.concatenate([_pack_layer(*layer) for layer in layer_plan(model)], axis=0)
     assert packed.shape[0] == int(sdn_backend.lib.sdn_field_weight_blocks()), packed.shape
     return packed
 
 
-class FusedField:
+def time_slice_index(t, T):
+    """Occupancy-grid time slice of time value `t` among `T` slices, in the reference's float32 arithmetic (dnerf/renderer.py:285)."""
+    return int(min(max(np.floor(np.float32(t) * np.float32(T)), 0), T - 1))
+
+
+class FusedFieldBase:
+    """What the fp16 field (`FusedField`) and the fp32 one (`fused_f32.FusedFieldF32`) share: the constants of a time stamp cached by
+    VALUE, the output buffers, the geometry.  A subclass supplies its rounding rule (`_bias0`, `time_bias`), its packed weights
+    (`_packed`), its table (`_bind_table`, `load_table`), its launches (`__call__`, `query_cells`) and `ctx_kind`, the value of
+    `SdnRenderCtx.field_f32` that selects its kernel in the native loops."""
+
+    def __init__(self, model, time, max_points=None):
+        enc = model.encoder
+        assert enc.gridtype == "tiled" and not enc.align_corners and enc.interpolation == "linear" and enc.num_levels == 16 and enc.level_dim == 2
+        self.model = model
+        self.weights = self._packed().to(enc.embeddings.device).contiguous()
+        self.S = float(np.log2(enc.per_level_scale))
+        self.H = int(enc.base_resolution)
+        self._bind_table(enc)
+        self.bound = float(model.bound)
+        self.density_scale = float(model.density_scale)
+        self._time_cache, self._group_cache = {}, {}
+        self.set_time(time)
+        self._buf = None
+        if max_points:
+            self._alloc(max_points)
+
+    @staticmethod
+    def time_value(time):
+        """`time` (python number, or the reference's [B,1] tensor: one host read) as the float32 value the network sees."""
+        v = float(time.reshape(-1)[0]) if isinstance(time, torch.Tensor) else float(time)
+        return float(np.float32(v))
+
+    def time_constants(self, time):
+        """The constants one time stamp contributes to a frame, cached by VALUE: (bias0 [128] f32 -- the time encoding's
+        contribution W0[:,63:76] . freq(t, 6) to the first deform layer, in the subclass's precision --, zero_deform flag (t == 0: the
+        canonical frame, dnerf/network.py:139-141), index of the occupancy-grid time slice)."""
+        t = self.time_value(time)
+        hit = self._time_cache.get(t)
+        if hit is None:
+            with torch.no_grad(), torch.autocast("cuda", enabled=False):
+                enc_t = freq_encode(torch.tensor([[t]], dtype=torch.float32, device=self.weights.device), 6, 13).reshape(13)
+                bias0 = self._bias0(self.model.deform_net[0].weight.detach(), enc_t)
+            hit = (bias0, int(t == 0.0), time_slice_index(t, self.model.time_size))
+            if len(self._time_cache) >= 4096:
+                self._time_cache.clear()
+            self._time_cache[t] = hit
+        return hit
+
+    def invalidate_time_cache(self):
+        """Call after the first deform layer's weights changed (training): cached biases were computed from the old weights."""
+        self._time_cache.clear()
+
+    def set_time(self, time):
+        """Selects the time stamp `__call__` evaluates at (a frame loop passes times per frame instead)."""
+        self.bias0, self.zero_deform, self.t_idx = self.time_constants(time)
+
+    def set_time_if_changed(self, value):
+        """`set_time` for a caller that hands over `time_value(...)` on every call (NeRFNetwork's fused dispatch)."""
+        if self.__dict__.get("_time_set") != value:
+            self.set_time(value)
+            self._time_set = value
+
+    def group_constants(self, times):
+        """(bias0 [F,128] contiguous, zero_deform bit mask, slice indices) for the F frames of a frame group; cached by value."""
+        key = tuple(self.time_value(t) for t in times)
+        hit = self._group_cache.get(key)
+        if hit is None:
+            parts = [self.time_constants(t) for t in key]
+            bias = torch.stack([p[0] for p in parts]).contiguous()
+            mask = sum(p[1] << f for f, p in enumerate(parts))
+            hit = (bias, mask, [p[2] for p in parts])
+            if len(self._group_cache) >= 1024:
+                self._group_cache.clear()
+            self._group_cache[key] = hit
+        return hit
+
+    def refresh(self):
+        """Re-pack the (trained) weights and re-read the table; call after optimizer steps."""
+        self.weights.copy_(self._packed())
+        self.load_table(self.model.encoder.embeddings.detach())
+        self._time_cache.clear()
+        self._group_cache.clear()
+
+    def query_cells(self, out, bias0, zero_deform, cas_bound, cells=None, cell_count=None, n=None, noise=None, seed=0):
+        """out[cell] = density_scale * sigma for the listed (or the first n) cells of one occupancy slice (CELLS variant of the kernel)."""
+        entry, name, table_dtype = self._cells_kernel()
+        if cells is not None:
+            n = cells.shape[0]
+        with sdn_backend.timed(name, n):
+            check(entry(ptr(cells, torch.int32, "cells"), ptr(cell_count), n, ptr(noise, torch.float32, "noise"), int(seed) & 0xFFFFFFFF,
+                        self.model.grid_size, float(cas_bound), ptr(self.weights), ptr(bias0, torch.float32, "bias0"),
+                        ptr(self.table, table_dtype, "embeddings"), self.offsets_host.ctypes.data, self.S, self.H, self.bound,
+                        self.density_scale, int(zero_deform), ptr(out, torch.float32, "out"), stream()), name)
+        return out
+
+    def _alloc(self, M):
+        dev = self.weights.device
+        self._buf = (torch.empty(M, dtype=torch.float32, device=dev), torch.empty(M, 3, dtype=torch.float32, device=dev))
+
+    def _outputs(self, M):
+        if self._buf is None or self._buf[0].shape[0] < M:
+            self._alloc(M)
+        return self._buf[0][:M], self._buf[1][:M]
+
+
+class FusedField(FusedFieldBase):
     """Callable (xyzs [M,3], dirs [M,3]) -> (sigmas [M] f32, rgbs [M,3] f32) with the reference's -O numerics."""
+
+    ctx_kind = 0
 
     def __init__(self, model, time, fp16=True, max_points=None, table_layout=None):
         if not fp16:
             raise NotImplementedError("the fused field kernel implements the -O (fp16) configuration; use the op-by-op network for fp32")
         if not available():
             raise sdn_backend.SdnError("libsdn_hip was built without the fused field kernel")
-        enc = model.encoder
-        assert enc.gridtype == "tiled" and not enc.align_corners and enc.interpolation == "linear" and enc.num_levels == 16 and enc.level_dim == 2
-        dev = enc.embeddings.device
-        self.model = model
-        self.weights = torch.from_numpy(pack_weights(model)).to(dev).contiguous()
+        self.layout = table_layout or os.environ.get("SDN_FIELD_TABLE", "quad")
+        assert self.layout in ("quad", "pad"), self.layout
+        super().__init__(model, time, max_points)
+
+    def _packed(self):
+        return torch.from_numpy(pack_weights(self.model))
+
+    def _bind_table(self, enc):
         # fp16 copy of the table (grid.py:43-44 under autocast) in a layout of the kernel's own (csrc/field.hip, kLayout*):
         #   "quad" (default): one 16-byte block per row r of a level = rows {r, r+1, r+s1, r+s1+1} mod the level's size -- the four (x, y)
         #       corners of a cell -- so a level costs TWO gathers instead of four: the phase is bound by the rate at which a CU takes
@@ -123,13 +240,10 @@ class FusedField:
         #       every gather is two consecutive rows even when x is the level's last row (`(index + 1) % hashmap_size` == 0,
         #       gridencoder.cu:66-84): four 8-byte gathers per level, no clamp / wrap bookkeeping.
         # Either is recognised by the kernel from the offsets that come with it (level sizes == 2 / 1 mod 8).
-        self.layout = table_layout or os.environ.get("SDN_FIELD_TABLE", "quad")
-        assert self.layout in ("quad", "pad"), self.layout
+        dev = enc.embeddings.device
         off = enc.offsets.cpu().numpy().astype(np.int64)
         self._ref_offsets = np.ascontiguousarray(off.astype(np.int32))
         self._level_rows = [(int(off[l]), int(off[l + 1])) for l in range(16)]
-        self.S = float(np.log2(enc.per_level_scale))
-        self.H = int(enc.base_resolution)
         if self.layout == "quad":
             self.offsets_host = np.ascontiguousarray((off + 2 * np.arange(17)).astype(np.int32))
             self.table = torch.empty(int(self.offsets_host[-1]), 4, 2, dtype=torch.float16, device=dev)
@@ -137,13 +251,6 @@ class FusedField:
             self.offsets_host = np.ascontiguousarray((off + np.arange(17)).astype(np.int32))
             self.table = torch.empty(int(self.offsets_host[-1]), 2, dtype=torch.float16, device=dev)
         self.load_table(enc.embeddings)
-        self.bound = float(model.bound)
-        self.density_scale = float(model.density_scale)
-        self._time_cache, self._group_cache = {}, {}
-        self.set_time(time)
-        self._buf = None
-        if max_points:
-            self._alloc(max_points)
 
     @torch.no_grad()
     def load_table(self, embeddings):
@@ -162,63 +269,22 @@ class FusedField:
             self.table[dst:dst + (b - a)].copy_(embeddings[a:b])
             self.table[dst + (b - a)].copy_(embeddings[a])
 
+    # bias0 in -O numerics: fp16-rounded operands, fp32 sum -- for one time stamp, and for the T slices of a density update at once
+    # (two matrix expressions whose fp32 summation order may differ: kept side by side, not derived from one another)
     @staticmethod
-    def time_value(time):
-        """`time` (python number, or the reference's [B,1] tensor: one host read) as the float32 value the network sees."""
-        v = float(time.reshape(-1)[0]) if isinstance(time, torch.Tensor) else float(time)
-        return float(np.float32(v))
+    def _bias0(w0, enc_t):
+        return (w0[:, 63:76].to(torch.float16).float() @ enc_t.to(torch.float16).float()).contiguous()
 
-    def time_constants(self, time):
-        """The constants one time stamp contributes to a frame, cached by VALUE: (bias0 [128] f32 -- the time encoding's
-        contribution W0[:,63:76] . freq(t, 6) to the first deform layer, fp16 operands, fp32 sum --, zero_deform flag (t == 0: the
-        canonical frame, dnerf/network.py:139-141), index of the occupancy-grid time slice (dnerf/renderer.py:285))."""
-        t = self.time_value(time)
-        hit = self._time_cache.get(t)
-        if hit is None:
-            dev = self.weights.device
-            with torch.no_grad(), torch.autocast("cuda", enabled=False):
-                enc_t = freq_encode(torch.tensor([[t]], dtype=torch.float32, device=dev), 6, 13).reshape(13)
-                w = self.model.deform_net[0].weight.detach()[:, 63:76]
-                bias0 = (w.to(torch.float16).float() @ enc_t.to(torch.float16).float()).contiguous()
-            T = self.model.time_size
-            t_idx = int(min(max(np.floor(np.float32(t) * np.float32(T)), 0), T - 1))
-            hit = (bias0, int(t == 0.0), t_idx)
-            if len(self._time_cache) >= 4096:
-                self._time_cache.clear()
-            self._time_cache[t] = hit
-        return hit
-
-    def invalidate_time_cache(self):
-        """Call after the first deform layer's weights changed (training): cached biases were computed from the old weights."""
-        self._time_cache.clear()
-
-    def set_time(self, time):
-        """Selects the time stamp `__call__` evaluates at (a frame loop passes times per frame instead)."""
-        self.bias0, self.zero_deform, self.t_idx = self.time_constants(time)
-
-    def group_constants(self, times):
-        """(bias0 [F,128] contiguous, zero_deform bit mask, slice indices) for the F frames of a frame group; cached by value."""
-        key = tuple(self.time_value(t) for t in times)
-        hit = self._group_cache.get(key)
-        if hit is None:
-            parts = [self.time_constants(t) for t in key]
-            bias = torch.stack([p[0] for p in parts]).contiguous()
-            mask = sum(p[1] << f for f, p in enumerate(parts))
-            hit = (bias, mask, [p[2] for p in parts])
-            if len(self._group_cache) >= 1024:
-                self._group_cache.clear()
-            self._group_cache[key] = hit
-        return hit
-
-    def _alloc(self, M):
-        dev = self.weights.device
-        self._buf = (torch.empty(M, dtype=torch.float32, device=dev), torch.empty(M, 3, dtype=torch.float32, device=dev))
+    def time_bias(self, times):
+        """[T] (perturbed) times -> bias0 [T,128]."""
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):   # (the trainer calls update_extra_state under autocast)
+            enc_t = freq_encode(times.reshape(-1, 1).float(), 6, 13)
+            w = self.model.deform_net[0].weight.detach()[:, 63:76]
+            return (enc_t.to(torch.float16).float() @ w.to(torch.float16).float().t()).contiguous()
 
     def __call__(self, xyzs, dirs, live_idx=None, live_count=None):
         M = xyzs.shape[0]
-        if self._buf is None or self._buf[0].shape[0] < M:
-            self._alloc(M)
-        sigmas, rgbs = self._buf[0][:M], self._buf[1][:M]
+        sigmas, rgbs = self._outputs(M)
         c = self.__dict__.get("_const")
         if c is None or c[0] is not self.weights or c[1] is not self.table or c[2] is not self.offsets_host:
             # (validated addresses of what does not change between calls: the reference-shaped loops are bound by host time)
@@ -230,6 +296,9 @@ class FusedField:
                                                         self.density_scale, self.zero_deform, ptr(sigmas), ptr(rgbs), stream()),
                   "field_forward_f16")
         return sigmas, rgbs
+
+    def _cells_kernel(self):
+        return sdn_backend.lib.sdn_density_query_cells_f16, "density_query_cells_f16", torch.float16
 
 
 class DensityGridUpdater:
@@ -255,9 +324,7 @@ class DensityGridUpdater:
             else:
                 field = FusedField(model, t0, fp16=True)
         self.field = field
-        self.fp32 = not isinstance(field, FusedField)
-        if self.fp32 and getattr(field, "variant", "mfma32") != "mfma32":
-            raise sdn_backend.SdnError("the fp32 density query reads the fp32-MFMA kernel's weight packing (FusedFieldF32(variant='mfma32'))")
+        self.fp32 = field.ctx_kind != 0
         n = model.grid_size ** 3
         self.tmp = torch.empty(n, dtype=torch.float32, device=dev)
         self.sum = torch.zeros(1, dtype=torch.float64, device=dev)
@@ -265,46 +332,17 @@ class DensityGridUpdater:
         self.seed = 0x5EA1D
 
     def refresh(self):
-        """Re-pack the (trained) weights and the fp16 table; call after optimizer steps."""
-        f, enc = self.field, self.model.encoder
-        sdn_backend.await_pending_write(enc.embeddings)     # (the fp32 queries read the table in place)
-        if self.fp32:
-            f.refresh()
-            return
-        f.weights.copy_(torch.from_numpy(pack_weights(self.model)))
-        f.load_table(enc.embeddings.detach())
-        f.invalidate_time_cache()
-        f._group_cache.clear()
+        """Re-pack the (trained) weights and the field's table; call after optimizer steps."""
+        sdn_backend.await_pending_write(self.model.encoder.embeddings)     # (the fp32 queries read the table in place)
+        self.field.refresh()
 
     def time_bias(self, times):
-        """[T] (perturbed) times -> bias0 [T,128], the expression of FusedField.set_time for every slice at once."""
-        with torch.no_grad(), torch.autocast("cuda", enabled=False):   # (the trainer calls update_extra_state under autocast)
-            enc_t = freq_encode(times.reshape(-1, 1).float(), 6, 13)
-            w = self.model.deform_net[0].weight.detach()[:, 63:76]
-            if self.fp32:
-                return (enc_t @ w.float().t()).contiguous()
-            return (enc_t.to(torch.float16).float() @ w.to(torch.float16).float().t()).contiguous()
+        """[T] (perturbed) times -> bias0 [T,128], the field's `set_time` expression for every slice at once."""
+        return self.field.time_bias(times)
 
-    def query_cells(self, out, bias0, zero_deform, cas_bound, cells=None, cell_count=None, n=None, noise=None, seed=0):
-        """out[cell] = density_scale * sigma for the listed (or the first n) cells of one slice."""
-        f = self.field
-        if cells is not None:
-            n = cells.shape[0]
-        if self.fp32:
-            with sdn_backend.timed("density_query_cells_f32", n):
-                check(sdn_backend.lib.sdn_density_query_cells_f32(ptr(cells, torch.int32, "cells"), ptr(cell_count), n, ptr(noise, torch.float32, "noise"),
-                                                                  int(seed) & 0xFFFFFFFF, self.model.grid_size, float(cas_bound), ptr(f.weights),
-                                                                  ptr(bias0, torch.float32, "bias0"), ptr(f.table, torch.float32, "embeddings"),
-                                                                  f.offsets_host.ctypes.data, f.S, f.H, f.bound, f.density_scale, int(zero_deform),
-                                                                  ptr(out, torch.float32, "out"), stream()), "density_query_cells_f32")
-            return out
-        with sdn_backend.timed("density_query_cells_f16", n):
-            check(sdn_backend.lib.sdn_density_query_cells_f16(ptr(cells, torch.int32, "cells"), ptr(cell_count), n, ptr(noise, torch.float32, "noise"),
-                                                              int(seed) & 0xFFFFFFFF, self.model.grid_size, float(cas_bound), ptr(f.weights),
-                                                              ptr(bias0, torch.float32, "bias0"), ptr(f.table), f.offsets_host.ctypes.data,
-                                                              f.S, f.H, f.bound, f.density_scale, int(zero_deform), ptr(out, torch.float32, "out"),
-                                                              stream()), "density_query_cells_f16")
-        return out
+    def query_cells(self, *args, **kwargs):
+        """`field.query_cells`: out[cell] = density_scale * sigma for the listed (or the first n) cells of one slice."""
+        return self.field.query_cells(*args, **kwargs)
 
     @torch.no_grad()
     def partial_cells(self):
@@ -347,18 +385,18 @@ class DensityGridUpdater:
         if partial:
             cells, counts = self.partial_cells()
         self.seed = (self.seed * 1664525 + 1013904223) & 0xFFFFFFFF
-        grid = m.density_grid
+        grid, query = m.density_grid, self.field.query_cells
         for t in range(T):
             for cas in range(C):
                 cas_bound = min(2 ** cas, m.bound)
                 nz = None if noise is None else noise[t, cas]
                 if full:
-                    self.query_cells(self.tmp, bias[t, cas], zero[t][cas], cas_bound, n=H3, noise=nz, seed=self.seed + 64 * t + cas)
+                    query(self.tmp, bias[t, cas], zero[t][cas], cas_bound, n=H3, noise=nz, seed=self.seed + 64 * t + cas)
                 else:
                     self.tmp.fill_(-1.0)
                     if partial:
-                        self.query_cells(self.tmp, bias[t, cas], zero[t][cas], cas_bound, cells=cells[t, cas], cell_count=counts[t, cas:cas + 1],
-                                         noise=nz, seed=self.seed + 64 * t + cas)
+                        query(self.tmp, bias[t, cas], zero[t][cas], cas_bound, cells=cells[t, cas], cell_count=counts[t, cas:cas + 1],
+                              noise=nz, seed=self.seed + 64 * t + cas)
                 check(sdn_backend.lib.sdn_density_grid_ema(ptr(grid[t, cas]), ptr(self.tmp), H3, float(decay), ptr(self.sum), stream()),
                       "density_grid_ema")
         check(sdn_backend.lib.sdn_density_grid_pack(ptr(grid), grid.numel(), ptr(self.sum), float(m.density_thresh), ptr(self.mean),

@@ -16,6 +16,7 @@ Two evaluation paths:
     the fp32 fused kernel (csrc/field_f32.hip, 1e-4 from the op-by-op fp32 network) when `model.fused_inference_f32 = True`.
 """
 import os
+import weakref
 
 import torch
 import torch.nn as nn
@@ -184,96 +185,72 @@ class NeRFNetwork(NeRFRenderer):
             self.__dict__["_fused_params"] = ps
         return tuple([(p.data_ptr(), p._version) for p in ps])
 
-    def _forward_fused32(self, x, d, t):
-        """The fp32 network in one launch: sigma [M], rgb [M,3], deform [M,3] (zeros on the canonical frame), all float32, within 1e-4 of
-        the op-by-op evaluation (tests/test_gpu_field_f32.py)."""
-        sdn_backend.await_pending_write(self.encoder.embeddings)     # (read in place below: a table pass still running elsewhere)
-        epoch = self._parameter_epoch()
-        cache = self.__dict__.get("_fused_cache32")
-        if cache is None or cache[0] != epoch[1:] or cache[2][0] != epoch[0][0]:
-            from . import fused_f32
-            # (weights packed once per parameter version; the embedding table is read where it is, so its in-place updates need nothing)
-            field = fused_f32.FusedFieldF32(self, t)
-            field.density_scale = 1.0
-            cache = (epoch[1:], field, epoch[0])
-            self.__dict__["_fused_cache32"] = cache
-        field = cache[1]
+    def _fused_time_value(self, field, t):
+        """`t` as the float32 value the network sees, by VALUE: one host read of t per distinct tensor content, where the reference's
+        `if t == 0` reads it on every call (network.py:140).  A loop hands the same tensor to every iteration: its value is kept while
+        the tensor object and its version counter stand (torch-level writes bump the counter; a write behind torch's back -- raw
+        pointer, DLPack -- needs a fresh tensor).  (The tensor OBJECT, not its address: a new tensor the allocator placed at a recycled
+        address is another object.)"""
         seen = self.__dict__.get("_fused_time")
         if not isinstance(t, torch.Tensor) or seen is None or seen[0]() is not t or seen[1] != t._version:
             value = field.time_value(t)
             if isinstance(t, torch.Tensor):
-                import weakref
                 self.__dict__["_fused_time"] = (weakref.ref(t), t._version, value)
-        else:
-            value = seen[2]
-        if field.__dict__.get("_time_set") != value:
-            field.set_time(value)
-            field._time_set = value
-        live = self._live_of(x)
-        M = x.shape[0]
-        if live is not None:
-            flat = torch.zeros(7 * M, dtype=torch.float32, device=x.device)      # one fill for the three outputs' skipped slots
-            field._buf = (flat[:M], flat[M:4 * M].view(M, 3))
-            deform = flat[4 * M:].view(M, 3)
-            sig, rgb = field(x, d.contiguous(), live[0], live[1], deform=deform)
-            field._buf = None
-            return sig, rgb, deform
-        field._buf = None
-        deform = torch.empty(M, 3, dtype=torch.float32, device=x.device)
-        sig, rgb = field(x.contiguous(), d.contiguous(), deform=deform)
-        return sig, rgb, deform
+            return value
+        return seen[2]
 
-    def _forward_fused(self, x, d, t):
-        """sigma [M] f32 (trunc_exp, density_scale NOT applied: the caller multiplies, dnerf/renderer.py:368), rgb [M,3] (the fp16 values
-        of torch.sigmoid on the half logits, held in f32), deform = None (callers of the inference branch discard it)."""
-        epoch = self._parameter_epoch()
-        cache = self.__dict__.get("_fused_cache")
-        if cache is None or cache[0] != epoch[1:]:
-            from . import fused
-            # (the fp16 table cast of grid.py:43-44 and the packed weights are made once per parameter version, not once per call)
-            field = fused.FusedField(self, t, fp16=True)
-            field.density_scale = 1.0
-            cache = (epoch[1:], field, epoch[0])
-            self.__dict__["_fused_cache"] = cache
-        elif cache[2] != epoch[0]:
-            cache[1].load_table(self.encoder.embeddings.detach())
-            cache = (cache[0], cache[1], epoch[0])
-            self.__dict__["_fused_cache"] = cache
-        field = cache[1]
-        # by VALUE: one host read of t per distinct tensor content, where the reference's `if t == 0` reads it on every call
-        # (network.py:140).  A loop hands the same tensor to every iteration: its value is kept while the tensor's address and version
-        # counter stand (torch-level writes bump the counter; a write behind torch's back -- raw pointer, DLPack -- needs a fresh tensor).
-        # (the tensor OBJECT, not its address: a new tensor the allocator placed at a recycled address is another object)
-        seen = self.__dict__.get("_fused_time")
-        if not isinstance(t, torch.Tensor) or seen is None or seen[0]() is not t or seen[1] != t._version:
-            value = field.time_value(t)
-            if isinstance(t, torch.Tensor):
-                import weakref
-                self.__dict__["_fused_time"] = (weakref.ref(t), t._version, value)
+    def _forward_fused(self, x, d, t, mode):
+        """The whole network in one launch.  mode 16 (-O): sigma [M] f32 (trunc_exp, density_scale NOT applied: the caller multiplies,
+        dnerf/renderer.py:368), rgb [M,3] (the fp16 values of torch.sigmoid on the half logits, held in f32), deform = None (callers of
+        the inference branch discard it).  mode 32: sigma [M], rgb [M,3], deform [M,3] (zeros on the canonical frame), all float32,
+        within 1e-4 of the op-by-op evaluation (tests/test_gpu_field_f32.py)."""
+        if mode == 16:
+            epoch = self._parameter_epoch()
+            cache = self.__dict__.get("_fused_cache")
+            if cache is None or cache[0] != epoch[1:]:
+                from . import fused
+                # (the fp16 table cast of grid.py:43-44 and the packed weights are made once per parameter version, not once per call)
+                field = fused.FusedField(self, t, fp16=True)
+                field.density_scale = 1.0
+                cache = self.__dict__["_fused_cache"] = (epoch[1:], field, epoch[0])
+            elif cache[2] != epoch[0]:      # only the embeddings moved
+                cache[1].load_table(self.encoder.embeddings.detach())
+                cache = self.__dict__["_fused_cache"] = (cache[0], cache[1], epoch[0])
         else:
-            value = seen[2]
-        if cache[1].__dict__.get("_time_set") != value:
-            field.set_time(value)
-            field._time_set = value
+            sdn_backend.await_pending_write(self.encoder.embeddings)     # (read in place below: a table pass still running elsewhere)
+            epoch = self._parameter_epoch()
+            cache = self.__dict__.get("_fused_cache32")
+            if cache is None or cache[0] != epoch[1:] or cache[2][0] != epoch[0][0]:
+                from . import fused_f32
+                # (weights packed once per parameter version; the embedding table is read where it is, so its in-place updates need nothing)
+                field = fused_f32.FusedFieldF32(self, t)
+                field.density_scale = 1.0
+                cache = self.__dict__["_fused_cache32"] = (epoch[1:], field, epoch[0])
+        field = cache[1]
+        field.set_time_if_changed(self._fused_time_value(field, t))
         # (Evaluating only the slots that hold a sample from a list built HERE -- a kernel over the zero direction vectors of the empty
         #  slots -- was measured and dropped, 2.73 -> 3.08 ms per frame; the list the marcher builds as it goes costs no pass.)
-        live = self._live_of(x) if self.fused_live_lists_f16 else None
+        live = self._live_of(x) if mode == 32 or self.fused_live_lists_f16 else None
+        M = x.shape[0]
         if live is not None:
-            M = x.shape[0]
-            flat = torch.zeros(4 * M, dtype=torch.float32, device=x.device)
-            field._buf = (flat[:M], flat[M:].view(M, 3))
-            sig, rgb = field(x, d.contiguous(), live[0], live[1])
+            flat = torch.zeros((7 if mode == 32 else 4) * M, dtype=torch.float32, device=x.device)    # one fill for the outputs' skipped slots
+            field._buf = (flat[:M], flat[M:4 * M].view(M, 3))
+            deform = flat[4 * M:].view(M, 3) if mode == 32 else None
+            idx, count = live[0], live[1]
+        else:
+            field._buf = None          # fresh output tensors per call (caching allocator, no launch): the caller owns them, as on the op-by-op path
+            deform = torch.empty(M, 3, dtype=torch.float32, device=x.device) if mode == 32 else None
+            x, idx, count = x.contiguous(), None, None
+        sig, rgb = field(x, d.contiguous(), idx, count, deform=deform) if mode == 32 else field(x, d.contiguous(), idx, count)
+        if live is not None:
             field._buf = None
-            return sig, rgb, None
-        field._buf = None          # fresh output tensors per call (caching allocator, no launch): the caller owns them, as on the op-by-op path
-        sig, rgb = field(x.contiguous(), d.contiguous())
-        return sig, rgb, None
+        return sig, rgb, deform
 
     def forward(self, x, d, t):
         """x [M,3] in [-bound,bound], d [M,3] unit, t [1,1] -> sigma [M], rgb [M,3], deform [M,3]  (network.py:123-169)."""
         mode = self._fused_inference_ok(x, d)
         if mode:
-            return self._forward_fused(x, d, t) if mode == 16 else self._forward_fused32(x, d, t)
+            return self._forward_fused(x, d, t, mode)
         deform = self._deform(x, t)
         if t == 0:  # canonical frame: no deformation (device compare => host sync, as in the reference :140)
             deform = torch.zeros_like(x)

@@ -23,6 +23,8 @@ import torch
 
 import sdn_backend as _sdn
 
+from .fused import time_slice_index
+
 _PARAM_NAMES = (["encoder.embeddings"] + [f"deform_net.{i}.weight" for i in range(8)] + [f"sigma_net.{i}.weight" for i in range(2)]
                 + [f"color_net.{i}.weight" for i in range(3)])
 
@@ -313,8 +315,7 @@ class NativeTrainStep:
     def _fill_scene(self, r, time_value, local_step):
         """Everything of the argument record that marching needs (phase 0 / 1)."""
         m = self.model
-        T = m.time_size
-        t_idx = int(min(max(np.floor(np.float32(time_value) * np.float32(T)), 0), T - 1))   # dnerf/renderer.py:285
+        t_idx = time_slice_index(time_value, m.time_size)
         r.bitfield = m.density_bitfield[t_idx].data_ptr()
         r.cull_grid = self._cull_grid(t_idx)
         r.counter = m.step_counter[local_step % 16].data_ptr()
