@@ -83,15 +83,11 @@ int sdn_density_query_cells_f16(const int32_t *cells, const uint32_t *cell_count
                                 uint32_t grid_size, float cas_bound, const void *weights, const float *bias0, const void *table,
                                 const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale, int zero_deform,
                                 float *tmp_slice, void *stream) {
-    if (n == 0) return 0;
-    if (!weights || !bias0 || !table || !offsets_host || !tmp_slice) return SDN_E_BADARG;
-    if ((cells == nullptr) != (cell_count == nullptr)) return SDN_E_BADARG;
-    if (grid_size < 2 || grid_size > 1024 || !(cas_bound > 0)) return SDN_E_BADARG;
-    // without a list, slot p IS the Morton index: n may not exceed the grid
-    if (!cells && (uint64_t)n > (uint64_t)grid_size * grid_size * grid_size) return SDN_E_BADARG;
-    if (((uintptr_t)weights & 15u) != 0 || ((uintptr_t)table & 3u) != 0) return SDN_E_BADARG;
-    return sdn_int::field_cells_f16(cells, cell_count, n, noise, seed, grid_size, cas_bound, weights, bias0, table, offsets_host, S, H, bound,
-                                    density_scale, zero_deform, tmp_slice, (hipStream_t)stream);
+    return sdn_int::field_cells_checked(0, {.f = {.live_idx = (const uint32_t *)cells, .live_count = cell_count, .M = n, .weights = weights, .bias0 = bias0,
+                                                  .table = table, .offsets_host = offsets_host, .S = S, .H = H, .bound = bound,
+                                                  .density_scale = density_scale, .zero_deform = zero_deform ? 1 : 0, .sigmas = tmp_slice},
+                                            .noise = noise, .seed = seed, .grid_size = grid_size, .cas_bound = cas_bound},
+                                        stream);
 }
 
 int sdn_density_grid_ema(float *density_grid, const float *tmp_grid, uint64_t n, float decay, double *sum, void *stream) {

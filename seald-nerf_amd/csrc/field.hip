@@ -35,6 +35,7 @@
 #include <stdlib.h>
 
 #include "sdn_common.h"
+#include "sdn_internal.h"
 #include "cell_points.h"
 #include "grid_common.h"
 #include "sh_eval.h"
@@ -709,22 +710,27 @@ static int g_field_pp = -1;   // 1: large launches take the persistent ping-pong
 static int g_field_pp_wgs = 0;   // workgroups of a persistent launch; 0 = one per CU
 constexpr uint32_t kPPMinTilesPerCU = 4;   // launches of at least this many 256-point tiles per CU take the persistent kernel
 
-// launch used by both the C entry point and the device-driven render loop (render.hip)
-int field_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state,
-                      uint32_t M, const void *weights, const float *bias0, const void *table, const int32_t *offsets_host, float S,
-                      uint32_t H, float bound, float density_scale, int zero_deform, float *sigmas, float *rgbs, uint32_t expect_points,
-                      const uint8_t *slot_frame, uint32_t n_frames, hipStream_t st) {
-    TiledLevels lv;
-    int rc = fill_tiled_levels(lv, offsets_host, S, H);
+// the kernels' argument records of one call (cell fields zero: field_cells_f16 sets its own)
+static int fill_field_args(FieldArgs &a, TiledLevels &lv, const FieldCall &f) {
+    int rc = fill_tiled_levels(lv, f.offsets_host, f.S, f.H);
     if (rc) return rc;
-    FieldArgs a;
-    a.xyzs = xyzs; a.dirs = dirs; a.live_idx = live_idx; a.live_count = live_count; a.state = state; a.M = M;
-    a.weights = (const unsigned char *)weights; a.bias0 = bias0; a.table = (const __half *)table;
-    a.sigmas = sigmas; a.rgbs = rgbs; a.bound = bound; a.density_scale = density_scale; a.zero_deform = zero_deform;
-    a.inv_2bound = exact_reciprocal(2 * bound);
-    a.slot_frame = slot_frame; a.n_frames = slot_frame ? (n_frames > 16u ? 16u : n_frames) : 1u;
+    a.xyzs = f.xyzs; a.dirs = f.dirs; a.live_idx = f.live_idx; a.live_count = f.live_count; a.state = f.state; a.M = f.M;
+    a.weights = (const unsigned char *)f.weights; a.bias0 = f.bias0; a.table = (const __half *)f.table;
+    a.sigmas = f.sigmas; a.rgbs = f.rgbs; a.bound = f.bound; a.density_scale = f.density_scale; a.zero_deform = f.zero_deform;
+    a.inv_2bound = exact_reciprocal(2 * f.bound);
+    a.slot_frame = f.slot_frame; a.n_frames = field_n_frames(f);
     a.cell_noise = nullptr; a.cell_seed = 0; a.cell_inv = a.cell_span = a.cell_half = 0;
     a.pp_soft = 0;
+    return 0;
+}
+
+// launch used by both the C entry point and the device-driven render loop (render.hip)
+int field_forward_f16(const FieldCall &f, hipStream_t st) {
+    TiledLevels lv;
+    FieldArgs a;
+    int rc = fill_field_args(a, lv, f);
+    if (rc) return rc;
+    const uint32_t M = f.M, expect_points = f.expect_points;
     const uint32_t wgs = sdn_div_up(M, (uint32_t)kPointsPerWG);
     static int cus = 0;
     if (cus == 0) {
@@ -747,7 +753,7 @@ int field_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live
         if (pin == 1) small = false;
         if (pin == 2) small = true;
     }
-    const int layout = table_layout(offsets_host);
+    const int layout = table_layout(f.offsets_host);
     // persistent ping-pong form (field_pp.inc): one 16-wave workgroup per CU walking tile pairs, for launches of at least two rounds of
     // the CUs (SDN_FIELD_PP=0 keeps every launch on the one-tile-per-workgroup kernels: measurements only)
     if (g_field_pp < 0) {
@@ -786,24 +792,16 @@ int field_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live
 }
 
 // sigma * density_scale of jittered occupancy-grid cell centres -> tmp_grid slice (density.hip drives the whole update)
-int field_cells_f16(const int32_t *cells, const uint32_t *cell_count, uint32_t n, const float *noise, uint32_t seed, uint32_t grid_size,
-                    float cas_bound, const void *weights, const float *bias0, const void *table, const int32_t *offsets_host, float S,
-                    uint32_t H, float bound, float density_scale, int zero_deform, float *tmp_slice, hipStream_t st) {
+int field_cells_f16(const FieldCells &q, hipStream_t st) {
     TiledLevels lv;
-    int rc = fill_tiled_levels(lv, offsets_host, S, H);
-    if (rc) return rc;
     FieldArgs a;
-    a.xyzs = nullptr; a.dirs = nullptr; a.live_idx = (const uint32_t *)cells; a.live_count = cell_count; a.state = nullptr; a.M = n;
-    a.weights = (const unsigned char *)weights; a.bias0 = bias0; a.table = (const __half *)table;
-    a.sigmas = tmp_slice; a.rgbs = nullptr; a.bound = bound; a.density_scale = density_scale; a.zero_deform = zero_deform ? 1 : 0;
-    a.inv_2bound = exact_reciprocal(2 * bound);
-    a.slot_frame = nullptr;
-    a.cell_noise = noise; a.cell_seed = seed;
-    a.n_frames = 1; a.pp_soft = 0;
-    const float half_grid = cas_bound / (float)grid_size;
-    a.cell_inv = 1.0f / (float)(grid_size - 1); a.cell_span = cas_bound - half_grid; a.cell_half = half_grid;
-    const uint32_t wgs = sdn_div_up(n, (uint32_t)kPointsPerWG);
-    const int layout = table_layout(offsets_host);
+    int rc = fill_field_args(a, lv, q.f);
+    if (rc) return rc;
+    a.cell_noise = q.noise; a.cell_seed = q.seed;
+    const float half_grid = q.cas_bound / (float)q.grid_size;
+    a.cell_inv = 1.0f / (float)(q.grid_size - 1); a.cell_span = q.cas_bound - half_grid; a.cell_half = half_grid;
+    const uint32_t wgs = sdn_div_up(q.f.M, (uint32_t)kPointsPerWG);
+    const int layout = table_layout(q.f.offsets_host);
     if (layout == kLayoutRef) return SDN_E_UNSUPPORTED;   // the density query is only built for the derived layouts
     if (layout == kLayoutQuad) {
         if (wgs <= 256u) hipLaunchKernelGGL((k_field_f16<2, 8, true, kLayoutQuad>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
@@ -881,12 +879,10 @@ int sdn_debug_field_stamps(unsigned long long *out) {
 int sdn_field_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count, uint32_t M,
                           const void *weights, const float *bias0, const void *table, const int32_t *offsets_host, float S, uint32_t H,
                           float bound, float density_scale, int zero_deform, float *sigmas, float *rgbs, void *stream) {
-    if (M == 0) return 0;
-    if (!xyzs || !dirs || !weights || !bias0 || !table || !offsets_host || !sigmas || !rgbs) return SDN_E_BADARG;
-    if ((live_idx == nullptr) != (live_count == nullptr)) return SDN_E_BADARG;
-    if (((uintptr_t)weights & 15u) != 0 || ((uintptr_t)table & 3u) != 0) return SDN_E_BADARG;
-    return sdn_int::field_forward_f16(xyzs, dirs, live_idx, live_count, nullptr, M, weights, bias0, table, offsets_host, S, H, bound,
-                                      density_scale, zero_deform ? 1 : 0, sigmas, rgbs, 0u, nullptr, 1u, (hipStream_t)stream);
+    return sdn_int::field_forward_checked(0, {.xyzs = xyzs, .dirs = dirs, .live_idx = live_idx, .live_count = live_count, .M = M, .weights = weights,
+                                              .bias0 = bias0, .table = table, .offsets_host = offsets_host, .S = S, .H = H, .bound = bound,
+                                              .density_scale = density_scale, .zero_deform = zero_deform ? 1 : 0, .sigmas = sigmas, .rgbs = rgbs},
+                                          stream);
 }
 
 }  // extern "C"

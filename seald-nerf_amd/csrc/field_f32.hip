@@ -212,32 +212,25 @@ __global__ void __launch_bounds__(64 * kWaves, 8 / kWaves) k_field_f32(F32Args P
 }  // namespace
 
 namespace sdn_int {
-int field_forward_f32(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state,
-       uint32_t M, const float *weights, const float *bias0, const float *table, const int32_t *offsets_host, float S,
-       uint32_t H, float bound, float density_scale, int zero_deform, float *sigmas, float *rgbs, float *deform,
-       const uint8_t *slot_frame, uint32_t n_frames, hipStream_t st) {
+int field_forward_f32(const FieldCall &f, hipStream_t st) {
     sdn_f32::LevelParams lp;
     sdn_f32::F32Args a;
-    int rc = sdn_f32::fill_args(a, lp, xyzs, dirs, live_idx, live_count, state, M, weights, bias0, table, offsets_host, S, H, bound, density_scale,
-                                zero_deform, sigmas, rgbs, deform, slot_frame, n_frames);
+    int rc = sdn_f32::fill_args(a, lp, f);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_field_f32<false>, dim3(sdn_div_up(M, (uint32_t)sdn_f32::kPointsPerWG)), dim3(64 * sdn_f32::kWaves), 0, st, a, lp);
+    hipLaunchKernelGGL(k_field_f32<false>, dim3(sdn_div_up(f.M, (uint32_t)sdn_f32::kPointsPerWG)), dim3(64 * sdn_f32::kWaves), 0, st, a, lp);
     return sdn_launch_status();
 }
 
 // sigma * density_scale of jittered occupancy-grid cell centres -> tmp_grid slice, fp32 network (the fp32 twin of field_cells_f16)
-int field_cells_f32(const int32_t *cells, const uint32_t *cell_count, uint32_t n, const float *noise, uint32_t seed, uint32_t grid_size,
-                    float cas_bound, const float *weights, const float *bias0, const float *table, const int32_t *offsets_host, float S,
-                    uint32_t H, float bound, float density_scale, int zero_deform, float *tmp_slice, hipStream_t st) {
+int field_cells_f32(const FieldCells &q, hipStream_t st) {
     sdn_f32::LevelParams lp;
     sdn_f32::F32Args a;
-    int rc = sdn_f32::fill_args(a, lp, nullptr, nullptr, (const uint32_t *)cells, cell_count, nullptr, n, weights, bias0, table, offsets_host, S, H,
-                                bound, density_scale, zero_deform ? 1 : 0, tmp_slice, nullptr, nullptr, nullptr, 1u);
+    int rc = sdn_f32::fill_args(a, lp, q.f);
     if (rc) return rc;
-    a.cell_noise = noise; a.cell_seed = seed;
-    const float half_grid = cas_bound / (float)grid_size;
-    a.cell_inv = 1.0f / (float)(grid_size - 1); a.cell_span = cas_bound - half_grid; a.cell_half = half_grid;
-    hipLaunchKernelGGL(k_field_f32<true>, dim3(sdn_div_up(n, (uint32_t)sdn_f32::kPointsPerWG)), dim3(64 * sdn_f32::kWaves), 0, st, a, lp);
+    a.cell_noise = q.noise; a.cell_seed = q.seed;
+    const float half_grid = q.cas_bound / (float)q.grid_size;
+    a.cell_inv = 1.0f / (float)(q.grid_size - 1); a.cell_span = q.cas_bound - half_grid; a.cell_half = half_grid;
+    hipLaunchKernelGGL(k_field_f32<true>, dim3(sdn_div_up(q.f.M, (uint32_t)sdn_f32::kPointsPerWG)), dim3(64 * sdn_f32::kWaves), 0, st, a, lp);
     return sdn_launch_status();
 }
 }  // namespace sdn_int
@@ -249,12 +242,11 @@ uint32_t sdn_field_weight_floats_f32(void) { return (uint32_t)sdn_f32::kTotalFlo
 int sdn_field_forward_f32(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count, uint32_t M,
                           const float *weights, const float *bias0, const float *table, const int32_t *offsets_host, float S, uint32_t H,
                           float bound, float density_scale, int zero_deform, float *sigmas, float *rgbs, float *deform, void *stream) {
-    if (M == 0) return 0;
-    if (!xyzs || !dirs || !weights || !bias0 || !table || !offsets_host || !sigmas || !rgbs) return SDN_E_BADARG;
-    if ((live_idx == nullptr) != (live_count == nullptr)) return SDN_E_BADARG;
-    if (((uintptr_t)weights & 15u) != 0 || ((uintptr_t)table & 3u) != 0) return SDN_E_BADARG;
-    return sdn_int::field_forward_f32(xyzs, dirs, live_idx, live_count, nullptr, M, weights, bias0, table, offsets_host, S, H, bound,
-                                      density_scale, zero_deform ? 1 : 0, sigmas, rgbs, deform, nullptr, 1u, (hipStream_t)stream);
+    return sdn_int::field_forward_checked(1, {.xyzs = xyzs, .dirs = dirs, .live_idx = live_idx, .live_count = live_count, .M = M, .weights = weights,
+                                              .bias0 = bias0, .table = table, .offsets_host = offsets_host, .S = S, .H = H, .bound = bound,
+                                              .density_scale = density_scale, .zero_deform = zero_deform ? 1 : 0, .sigmas = sigmas, .rgbs = rgbs,
+                                              .deform = deform},
+                                          stream);
 }
 
 // The density-grid query of update_extra_state for a model trained WITHOUT -O: as sdn_density_query_cells_f16 with the fp32 network
@@ -263,14 +255,11 @@ int sdn_density_query_cells_f32(const int32_t *cells, const uint32_t *cell_count
                                 uint32_t grid_size, float cas_bound, const float *weights, const float *bias0, const float *table,
                                 const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale, int zero_deform,
                                 float *tmp_slice, void *stream) {
-    if (n == 0) return 0;
-    if (!weights || !bias0 || !table || !offsets_host || !tmp_slice) return SDN_E_BADARG;
-    if ((cells == nullptr) != (cell_count == nullptr)) return SDN_E_BADARG;
-    if (grid_size < 2 || grid_size > 1024 || !(cas_bound > 0)) return SDN_E_BADARG;
-    if (!cells && (uint64_t)n > (uint64_t)grid_size * grid_size * grid_size) return SDN_E_BADARG;   // without a list, slot p IS the Morton index
-    if (((uintptr_t)weights & 15u) != 0 || ((uintptr_t)table & 3u) != 0) return SDN_E_BADARG;
-    return sdn_int::field_cells_f32(cells, cell_count, n, noise, seed, grid_size, cas_bound, weights, bias0, table, offsets_host, S, H, bound,
-                                    density_scale, zero_deform, tmp_slice, (hipStream_t)stream);
+    return sdn_int::field_cells_checked(1, {.f = {.live_idx = (const uint32_t *)cells, .live_count = cell_count, .M = n, .weights = weights, .bias0 = bias0,
+                                                  .table = table, .offsets_host = offsets_host, .S = S, .H = H, .bound = bound,
+                                                  .density_scale = density_scale, .zero_deform = zero_deform ? 1 : 0, .sigmas = tmp_slice},
+                                            .noise = noise, .seed = seed, .grid_size = grid_size, .cas_bound = cas_bound},
+                                        stream);
 }
 
 }  // extern "C"

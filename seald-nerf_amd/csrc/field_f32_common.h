@@ -24,7 +24,7 @@ constexpr int kWaves = SDN_F32_WAVES;          // waves per workgroup (8: one wo
 constexpr int kPieces = 16384 / (64 * kWaves * 4);   // 16-byte pieces per thread of a 64-KiB stage
 constexpr int kPointsPerWG = 32 * kWaves;
 constexpr int kStageFloats = 16384;   // 64 KiB: one 128 x 128 layer
-constexpr int kMaxFrames = 16;        // frames of a frame group (SDN_MAX_GROUP_FRAMES)
+constexpr int kMaxFrames = SDN_MAX_GROUP_FRAMES;   // frames of a frame group: bias rows the kernels keep in LDS (sdn_int::field_n_frames clamps to it)
 
 // packed weights, in stage order: D0 (32 KiB) | D1 .. D6 (64 KiB each) | tail = D7 S0 S1 C0 C1 C2 (64 KiB), as float counts
 constexpr int kD0 = 0, kD0Floats = 8192;
@@ -127,16 +127,13 @@ __device__ __forceinline__ void stage_commit(float *s_w, const Pre &r) {
     wg_barrier();
 }
 
-inline int fill_args(F32Args &a, LevelParams &lp, const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count,
-                     const int32_t *state, uint32_t M, const float *weights, const float *bias0, const float *table, const int32_t *offsets_host,
-                     float S, uint32_t H, float bound, float density_scale, int zero_deform, float *sigmas, float *rgbs, float *deform,
-                     const uint8_t *slot_frame, uint32_t n_frames) {
-    int rc = sdn_grid::fill_levels(lp, offsets_host, 16u, S, H);
+inline int fill_args(F32Args &a, LevelParams &lp, const sdn_int::FieldCall &f) {
+    int rc = sdn_grid::fill_levels(lp, f.offsets_host, 16u, f.S, f.H);
     if (rc) return rc;
-    a.xyzs = xyzs; a.dirs = dirs; a.live_idx = live_idx; a.live_count = live_count; a.state = state; a.M = M;
-    a.weights = weights; a.bias0 = bias0; a.table = table; a.sigmas = sigmas; a.rgbs = rgbs; a.deform = deform;
-    a.bound = bound; a.density_scale = density_scale; a.zero_deform = zero_deform;
-    a.slot_frame = slot_frame; a.n_frames = slot_frame ? (n_frames > (uint32_t)kMaxFrames ? (uint32_t)kMaxFrames : (n_frames ? n_frames : 1u)) : 1u;
+    a.xyzs = f.xyzs; a.dirs = f.dirs; a.live_idx = f.live_idx; a.live_count = f.live_count; a.state = f.state; a.M = f.M;
+    a.weights = (const float *)f.weights; a.bias0 = f.bias0; a.table = (const float *)f.table; a.sigmas = f.sigmas; a.rgbs = f.rgbs; a.deform = f.deform;
+    a.bound = f.bound; a.density_scale = f.density_scale; a.zero_deform = f.zero_deform;
+    a.slot_frame = f.slot_frame; a.n_frames = sdn_int::field_n_frames(f);
     a.cell_noise = nullptr; a.cell_seed = 0; a.cell_inv = a.cell_span = a.cell_half = 0;
     return 0;
 }

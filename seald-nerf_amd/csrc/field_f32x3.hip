@@ -259,16 +259,12 @@ __global__ void __launch_bounds__(64 * kWaves, 8 / kWaves) k_field_f32x3(F32Args
 }  // namespace
 
 namespace sdn_int {
-int field_forward_f32x3(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state,
-       uint32_t M, const float *weights, const float *bias0, const float *table, const int32_t *offsets_host, float S,
-       uint32_t H, float bound, float density_scale, int zero_deform, float *sigmas, float *rgbs, float *deform,
-       const uint8_t *slot_frame, uint32_t n_frames, hipStream_t st) {
+int field_forward_f32x3(const FieldCall &f, hipStream_t st) {
     sdn_f32::LevelParams lp;
     sdn_f32::F32Args a;
-    int rc = sdn_f32::fill_args(a, lp, xyzs, dirs, live_idx, live_count, state, M, weights, bias0, table, offsets_host, S, H, bound, density_scale,
-                                zero_deform, sigmas, rgbs, deform, slot_frame, n_frames);
+    int rc = sdn_f32::fill_args(a, lp, f);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_field_f32x3, dim3(sdn_div_up(M, (uint32_t)sdn_f32::kPointsPerWG)), dim3(64 * sdn_f32::kWaves), 0, st, a, lp);
+    hipLaunchKernelGGL(k_field_f32x3, dim3(sdn_div_up(f.M, (uint32_t)sdn_f32::kPointsPerWG)), dim3(64 * sdn_f32::kWaves), 0, st, a, lp);
     return sdn_launch_status();
 }
 }  // namespace sdn_int
@@ -279,12 +275,11 @@ extern "C" {
 int sdn_field_forward_f32x3(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count, uint32_t M,
                           const float *weights, const float *bias0, const float *table, const int32_t *offsets_host, float S, uint32_t H,
                           float bound, float density_scale, int zero_deform, float *sigmas, float *rgbs, float *deform, void *stream) {
-    if (M == 0) return 0;
-    if (!xyzs || !dirs || !weights || !bias0 || !table || !offsets_host || !sigmas || !rgbs) return SDN_E_BADARG;
-    if ((live_idx == nullptr) != (live_count == nullptr)) return SDN_E_BADARG;
-    if (((uintptr_t)weights & 15u) != 0 || ((uintptr_t)table & 3u) != 0) return SDN_E_BADARG;
-    return sdn_int::field_forward_f32x3(xyzs, dirs, live_idx, live_count, nullptr, M, weights, bias0, table, offsets_host, S, H, bound,
-                                      density_scale, zero_deform ? 1 : 0, sigmas, rgbs, deform, nullptr, 1u, (hipStream_t)stream);
+    return sdn_int::field_forward_checked(2, {.xyzs = xyzs, .dirs = dirs, .live_idx = live_idx, .live_count = live_count, .M = M, .weights = weights,
+                                              .bias0 = bias0, .table = table, .offsets_host = offsets_host, .S = S, .H = H, .bound = bound,
+                                              .density_scale = density_scale, .zero_deform = zero_deform ? 1 : 0, .sigmas = sigmas, .rgbs = rgbs,
+                                              .deform = deform},
+                                          stream);
 }
 
 }  // extern "C"

@@ -1711,108 +1711,132 @@ __global__ void __launch_bounds__(256) k_loop_finish(uint32_t N, const float *__
     depth_out[n] = fmaxf(depth[n] - nears[n], 0.0f) / (fars[n] - nears[n]);
 }
 
+// k_march_rays' arguments by name, for the one function that picks its instantiation (the public marcher and the loop's share it)
+struct MarchRays {
+    uint32_t threads = 0;                  // lanes to launch
+    uint32_t n_alive = 0, n_step = 0;      // 0, 0: the kernel reads them from `state`
+    const int32_t *rays_alive = nullptr, *rays_alive_b = nullptr, *state = nullptr;
+    const float *rays_t = nullptr, *rays_o = nullptr, *rays_d = nullptr, *fars = nullptr, *noises = nullptr;
+    float bound = 0, dt_gamma = 0;
+    uint32_t max_steps = 0, C = 0, H = 0, M_pad = 0;
+    const uint8_t *grid = nullptr;
+    float *xyzs = nullptr, *dirs = nullptr, *deltas = nullptr;
+    const uint32_t *cull = nullptr;
+    uint32_t *live_idx = nullptr, *live_count = nullptr;
+    FrameSel fs;
+    const float *jump = nullptr;           // only used with a cull grid
+};
+int launch_k_march_rays(const MarchRays &m, hipStream_t st) {
+    const dim3 g(sdn_div_up(m.threads, 256u)), b(256);
+    if (fast_config(m.bound, m.C, m.H)) {
+        const uint32_t *cull = (m.cull && m.H != 128) ? nullptr : m.cull;  // the cull grid is built for the 128^3 grid only
+        hipLaunchKernelGGL(k_march_rays<true>, g, b, 0, st, m.n_alive, m.n_step, m.rays_alive, m.rays_t, m.rays_o, m.rays_d, m.bound, m.dt_gamma,
+                           m.max_steps, m.C, m.H, m.grid, m.fars, m.xyzs, m.dirs, m.deltas, m.noises, m.M_pad, cull, m.live_idx, m.live_count, m.state,
+                           m.rays_alive_b, m.fs, cull ? m.jump : (const float *)nullptr);
+    } else {
+        hipLaunchKernelGGL(k_march_rays<false>, g, b, 0, st, m.n_alive, m.n_step, m.rays_alive, m.rays_t, m.rays_o, m.rays_d, m.bound, m.dt_gamma,
+                           m.max_steps, m.C, m.H, m.grid, m.fars, m.xyzs, m.dirs, m.deltas, m.noises, m.M_pad, (const uint32_t *)nullptr, m.live_idx,
+                           m.live_count, m.state, m.rays_alive_b, m.fs, (const float *)nullptr);
+    }
+    return sdn_launch_status();
+}
+
+// byte offsets into the training marcher's scratch: scan workspace | cull grid of the time slice | t of every sample [N, max_steps]
+struct TrainScratch { uint64_t cull, sample_t; };
+TrainScratch train_scratch(uint32_t N) {
+    const uint64_t words = (uint64_t)N + sdn_div_up(N, kScanBlock) + 4u;   // num_steps, block totals, bases
+    const uint64_t head = (words * sizeof(uint32_t) + 15u) & ~(uint64_t)15u;
+    const uint64_t cull_bytes = ((uint64_t)(kCullWords + 8u) * sizeof(uint32_t) + 15u) & ~(uint64_t)15u;
+    return {head, head + cull_bytes};
+}
+
 }  // namespace
 
 namespace sdn_int {
 
-int loop_begin(uint32_t N, uint32_t max_steps, const float *nears, int32_t *alive_a, float *rays_t, float *weights_sum, float *depth,
-               float *image, int32_t *state, int32_t *live_counts, uint32_t n_counters, void *mailbox, uint32_t frame_tag, float *rays_tend,
-               hipStream_t st) {
-    const uint32_t threads = N > n_counters ? N : n_counters;
-    hipLaunchKernelGGL(k_loop_init, dim3(sdn_div_up(threads, 256u)), dim3(256), 0, st, N, max_steps, nears, alive_a, rays_t, weights_sum, depth,
-                       image, state, live_counts, n_counters, (unsigned long long)(uintptr_t)mailbox, frame_tag, rays_tend);
+int loop_begin(const SdnRenderCtx &c, void *mailbox, uint32_t frame_tag, hipStream_t st) {
+    const uint32_t threads = c.N > c.n_counters ? c.N : c.n_counters;
+    hipLaunchKernelGGL(k_loop_init, dim3(sdn_div_up(threads, 256u)), dim3(256), 0, st, c.N, c.max_steps, c.nears, c.alive_a, c.rays_t, c.weights_sum,
+                       c.depth, c.image, c.state, c.live_counts, c.n_counters, (unsigned long long)(uintptr_t)mailbox, frame_tag, c.rays_tend);
     return sdn_launch_status();
 }
 
 // Culled start (see k_cull_start): after loop_begin and after the context's cull grid(s) are in place.  Returns 0 without doing
 // anything when the configuration has no exact cull test (not the FAST configuration, no cull grid, no t_end cache).
-int loop_cull_start(uint32_t N, const float *rays_o, const float *rays_d, const float *nears, const float *fars, float bound, float dt_gamma,
-                    uint32_t C, uint32_t H, const uint32_t *cull, const FrameSel &fs, int32_t *alive_a, int32_t *alive_b, float *rays_tend,
-                    int32_t *state, uint32_t *block_totals, int32_t *n_out, int32_t *trace, uint32_t max_steps, float *jump, hipStream_t st) {
-    if (!cull || !rays_tend || H != 128 || !fast_config(bound, C, H)) return 0;
-    hipLaunchKernelGGL(k_cull_start, dim3(sdn_div_up(N, 256u)), dim3(256), 0, st, N, rays_o, rays_d, nears, fars, cull, fs, alive_a, rays_tend, bound,
-                       dt_gamma, max_steps, C, H, jump, block_totals);
-    const uint32_t nb = sdn_div_up(N, kScanBlock);
-    hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(kScanBlock), 0, st, (const int32_t *)alive_a, N, (const uint32_t *)block_totals, alive_b, n_out,
-                       (const int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr, 4u);
-    hipLaunchKernelGGL(k_cull_advance, dim3(1), dim3(64), 0, st, state, (const int32_t *)n_out, trace);
+int loop_cull_start(const SdnRenderCtx &c, hipStream_t st) {
+    const uint32_t *cull = loop_cull(c);
+    if (!cull || !c.rays_tend || c.H != 128 || !fast_config(c.bound, c.C, c.H)) return 0;
+    uint32_t *block_totals = (uint32_t *)c.block_totals;
+    hipLaunchKernelGGL(k_cull_start, dim3(sdn_div_up(c.N, 256u)), dim3(256), 0, st, c.N, c.rays_o, c.rays_d, c.nears, c.fars, cull, frame_sel(c), c.alive_a,
+                       c.rays_tend, c.bound, c.dt_gamma, c.max_steps, c.C, c.H, jump_buffer(c), block_totals);
+    const uint32_t nb = sdn_div_up(c.N, kScanBlock);
+    hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(kScanBlock), 0, st, (const int32_t *)c.alive_a, c.N, (const uint32_t *)block_totals, c.alive_b,
+                       snap_n_out(c), (const int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr, 4u);
+    hipLaunchKernelGGL(k_cull_advance, dim3(1), dim3(64), 0, st, c.state, (const int32_t *)snap_n_out(c), c.trace);
     return sdn_launch_status();
 }
 
-int loop_march(uint32_t bound_alive, const int32_t *alive_a, const int32_t *alive_b, const float *rays_t, const float *rays_o,
-               const float *rays_d, float bound, float dt_gamma, uint32_t max_steps, uint32_t C, uint32_t H, const uint8_t *grid,
-               const float *fars, float *xyzs, float *dirs, float *deltas, const uint32_t *cull, uint32_t *live_idx,
-               uint32_t *live_counts, const int32_t *state, const FrameSel &fs, hipStream_t st, const float *jump) {
-    const dim3 g(sdn_div_up(bound_alive + 128u, 256u)), b(256);
-    if (fast_config(bound, C, H)) {
-        if (cull && H != 128) cull = nullptr;
-        hipLaunchKernelGGL(k_march_rays<true>, g, b, 0, st, 0u, 0u, alive_a, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, fars,
-                           xyzs, dirs, deltas, (const float *)nullptr, 0u, cull, live_idx, live_counts, state, alive_b, fs, cull ? jump : (const float *)nullptr);
-    } else {
-        hipLaunchKernelGGL(k_march_rays<false>, g, b, 0, st, 0u, 0u, alive_a, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, fars,
-                           xyzs, dirs, deltas, (const float *)nullptr, 0u, (const uint32_t *)nullptr, live_idx, live_counts, state, alive_b, fs,
-                           (const float *)nullptr);
-    }
-    return sdn_launch_status();
+// the loop's marcher on the alive list (n_alive / n_step from the loop record); jump: the culled start's targets, or nullptr
+static int march(const SdnRenderCtx &c, uint32_t bound_alive, const float *jump, hipStream_t st) {
+    MarchRays m;
+    m.threads = bound_alive + 128u;
+    m.rays_alive = c.alive_a; m.rays_alive_b = c.alive_b; m.rays_t = c.rays_t; m.rays_o = c.rays_o; m.rays_d = c.rays_d;
+    m.bound = c.bound; m.dt_gamma = c.dt_gamma; m.max_steps = c.max_steps; m.C = c.C; m.H = c.H; m.grid = c.bitfield; m.fars = c.fars;
+    m.xyzs = c.xyzs; m.dirs = c.dirs; m.deltas = c.deltas; m.cull = loop_cull(c); m.live_idx = c.live_idx; m.live_count = live_counters(c);
+    m.state = c.state; m.fs = frame_sel(c); m.jump = jump;
+    return launch_k_march_rays(m, st);
 }
 
-int loop_composite_compact(uint32_t bound_alive, float T_thresh, int32_t *alive_a, int32_t *alive_b, float *rays_t, const float *sigmas,
-                           const float *rgbs, const float *deltas, float *weights_sum, float *depth, float *image, int32_t *state,
-                           uint32_t *block_totals, int32_t *n_out, int32_t *trace, int32_t *snap, hipStream_t st, bool freeze) {
+int loop_march(const SdnRenderCtx &c, uint32_t bound_alive, hipStream_t st) { return march(c, bound_alive, jump_buffer(c), st); }
+
+int loop_composite_compact(const SdnRenderCtx &c, uint32_t bound_alive, hipStream_t st, bool freeze) {
     const dim3 g(sdn_div_up(bound_alive, 256u)), b(256);
+    uint32_t *block_totals = (uint32_t *)c.block_totals;
+    int32_t *snap = snap_ring(c);
+    hipLaunchKernelGGL(k_composite_rays, g, b, 0, st, 0u, 0u, c.T_thresh, c.alive_a, c.rays_t, c.sigmas, c.rgbs, c.deltas, c.weights_sum, c.depth, c.image,
+                       (const int32_t *)c.state, c.alive_b, block_totals);          // (+ survivors per 256 rays: no separate count launch)
     if (bound_alive > 65536u) {
         // many rays (the first one or two iterations): every scatter workgroup would re-sum thousands of 256-ray totals;
         // use the 1024-ray count / scatter pair and a separate one-thread advance instead.  (Measured again in round 3 with the fused pair up
         // to 131 072 / 262 144 / 524 288 rays: 0.449 / 0.451 / 0.451 ms per frame against 0.441 -- every workgroup of the fused scatter pays a
         // device-scope fence for the last-workgroup election.)
         static_assert(kScanBlock == 1024, "the compositing kernel's 256-ray survivor counts are summed four to a scatter block");
-        hipLaunchKernelGGL(k_composite_rays, g, b, 0, st, 0u, 0u, T_thresh, alive_a, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image,
-                           (const int32_t *)state, alive_b, block_totals);          // (+ survivors per 256 rays: no separate count launch)
         const uint32_t nb = sdn_div_up(bound_alive, kScanBlock);
-        hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(kScanBlock), 0, st, (const int32_t *)alive_a, 0u, (const uint32_t *)block_totals,
-                           alive_b, snap + 8, (const int32_t *)state, (const int32_t *)alive_b, alive_a, 4u);
-        hipLaunchKernelGGL(k_loop_advance, dim3(1), dim3(64), 0, st, state, (const int32_t *)(snap + 8), trace, snap, freeze ? 1 : 0);
+        hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(kScanBlock), 0, st, (const int32_t *)c.alive_a, 0u, (const uint32_t *)block_totals,
+                           c.alive_b, snap_n_out(c), (const int32_t *)c.state, (const int32_t *)c.alive_b, c.alive_a, 4u);
+        hipLaunchKernelGGL(k_loop_advance, dim3(1), dim3(64), 0, st, c.state, (const int32_t *)snap_n_out(c), c.trace, snap, freeze ? 1 : 0);
         return sdn_launch_status();
     }
-    hipLaunchKernelGGL(k_composite_rays, g, b, 0, st, 0u, 0u, T_thresh, alive_a, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image,
-                       (const int32_t *)state, alive_b, block_totals);
     // n_out doubles as the ticket counter (zero between launches)
-    hipLaunchKernelGGL(k_scatter_advance, g, b, 0, st, alive_a, alive_b, (const uint32_t *)block_totals, state, n_out, trace, snap, freeze ? 1 : 0);
+    hipLaunchKernelGGL(k_scatter_advance, g, b, 0, st, c.alive_a, c.alive_b, (const uint32_t *)block_totals, c.state, c.n_out, c.trace, snap, freeze ? 1 : 0);
     return sdn_launch_status();
 }
 
-
-int loop_steady_begin(uint32_t bound_alive, const int32_t *alive_a, const int32_t *alive_b, const float *rays_t, const float *rays_o,
-                      const float *rays_d, float bound, float dt_gamma, uint32_t max_steps, uint32_t C, uint32_t H, const uint8_t *grid,
-                      const float *fars, float *xyzs, float *dirs, float *deltas, const uint32_t *cull, uint32_t *live_idx,
-                      uint32_t *live_counts, int32_t *state, const FrameSel &fs, hipStream_t st, bool frozen_already) {
-    if (!frozen_already) hipLaunchKernelGGL(k_steady_begin, dim3(1), dim3(64), 0, st, state);
-    return loop_march(bound_alive, alive_a, alive_b, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, fars, xyzs, dirs, deltas,
-                      cull, live_idx, live_counts, state, fs, st, nullptr);
+int loop_steady_begin(const SdnRenderCtx &c, uint32_t bound_alive, hipStream_t st, bool frozen_already) {
+    if (!frozen_already) hipLaunchKernelGGL(k_steady_begin, dim3(1), dim3(64), 0, st, c.state);
+    return march(c, bound_alive, nullptr, st);
 }
 
-int loop_composite_march(uint32_t bound_list, float T_thresh, int32_t *alive_a, int32_t *alive_b, float *rays_t, const float *rays_o,
-                         const float *rays_d, float bound, float dt_gamma, uint32_t max_steps, uint32_t C, uint32_t H, const uint8_t *grid,
-                         const float *fars, const float *sigmas, const float *rgbs, float *xyzs, float *dirs, float *deltas,
-                         float *weights_sum, float *depth, float *image, const uint32_t *cull, uint32_t *live_idx, uint32_t *live_counts,
-                         int32_t *state, int32_t *ticket, int32_t *trace, int32_t *snap, const FrameSel &fs, hipStream_t st) {
+int loop_composite_march(const SdnRenderCtx &c, uint32_t bound_list, hipStream_t st) {
     const dim3 g(sdn_div_up(bound_list, 256u)), b(256);
-    if (fast_config(bound, C, H)) {
-        if (cull && H != 128) cull = nullptr;
-        hipLaunchKernelGGL(k_composite_march<true>, g, b, 0, st, T_thresh, alive_a, alive_b, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H,
-                           grid, fars, sigmas, rgbs, xyzs, dirs, deltas, weights_sum, depth, image, cull, live_idx, live_counts, state, ticket,
-                           trace, snap, fs);
+    const FrameSel fs = frame_sel(c);
+    int32_t *snap = snap_ring(c);
+    if (fast_config(c.bound, c.C, c.H)) {
+        const uint32_t *cull = loop_cull(c);
+        if (cull && c.H != 128) cull = nullptr;
+        hipLaunchKernelGGL(k_composite_march<true>, g, b, 0, st, c.T_thresh, c.alive_a, c.alive_b, c.rays_t, c.rays_o, c.rays_d, c.bound, c.dt_gamma,
+                           c.max_steps, c.C, c.H, c.bitfield, c.fars, c.sigmas, c.rgbs, c.xyzs, c.dirs, c.deltas, c.weights_sum, c.depth, c.image, cull,
+                           c.live_idx, live_counters(c), c.state, c.n_out, c.trace, snap, fs);   // (n_out: the ticket counter)
     } else {
-        hipLaunchKernelGGL(k_composite_march<false>, g, b, 0, st, T_thresh, alive_a, alive_b, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C,
-                           H, grid, fars, sigmas, rgbs, xyzs, dirs, deltas, weights_sum, depth, image, (const uint32_t *)nullptr, live_idx,
-                           live_counts, state, ticket, trace, snap, fs);
+        hipLaunchKernelGGL(k_composite_march<false>, g, b, 0, st, c.T_thresh, c.alive_a, c.alive_b, c.rays_t, c.rays_o, c.rays_d, c.bound, c.dt_gamma,
+                           c.max_steps, c.C, c.H, c.bitfield, c.fars, c.sigmas, c.rgbs, c.xyzs, c.dirs, c.deltas, c.weights_sum, c.depth, c.image,
+                           (const uint32_t *)nullptr, c.live_idx, live_counters(c), c.state, c.n_out, c.trace, snap, fs);
     }
     return sdn_launch_status();
 }
 
-int loop_finish(uint32_t N, const float *nears, const float *fars, const float *weights_sum, const float *depth, const float *image, float bg,
-                float *image_out, float *depth_out, hipStream_t st) {
-    hipLaunchKernelGGL(k_loop_finish, dim3(sdn_div_up(N, 256u)), dim3(256), 0, st, N, nears, fars, weights_sum, depth, image, bg, image_out,
+int loop_finish(const SdnRenderCtx &c, float bg, float *image_out, float *depth_out, hipStream_t st) {
+    hipLaunchKernelGGL(k_loop_finish, dim3(sdn_div_up(c.N, 256u)), dim3(256), 0, st, c.N, c.nears, c.fars, c.weights_sum, c.depth, c.image, bg, image_out,
                        depth_out);
     return sdn_launch_status();
 }
@@ -1848,14 +1872,14 @@ int build_cull_group(const FrameSel &fs, uint32_t *cull_bits, hipStream_t st) {
     return sdn_launch_status();
 }
 
-FrameSel frame_sel(const SdnRenderCtx *c) {
+FrameSel frame_sel(const SdnRenderCtx &c) {
     FrameSel fs;
-    if (c->n_group_frames > 1) {
-        fs.n_frames = c->n_group_frames;
-        fs.rays_per_frame = c->rays_per_frame;
+    if (c.n_group_frames > 1) {
+        fs.n_frames = c.n_group_frames;
+        fs.rays_per_frame = c.rays_per_frame;
         fs.cull_stride = sdn_cull_grid_bytes() / 4u;
-        for (uint32_t f = 0; f < c->n_group_frames && f < SDN_MAX_GROUP_FRAMES; f++) fs.grid[f] = c->frame_bitfield[f];
-        fs.slot_frame = c->slot_frame;
+        for (uint32_t f = 0; f < c.n_group_frames && f < SDN_MAX_GROUP_FRAMES; f++) fs.grid[f] = c.frame_bitfield[f];
+        fs.slot_frame = c.slot_frame;
     }
     return fs;
 }
@@ -1906,13 +1930,8 @@ int sdn_packbits(const float *grid, uint32_t N, float density_thresh, uint8_t *b
     return sdn_launch_status();
 }
 
-static uint64_t train_scratch_words(uint32_t N) { return (uint64_t)N + sdn_div_up(N, kScanBlock) + 4u; }   // num_steps, block totals, bases
-
 uint64_t sdn_march_rays_train_scratch_bytes(uint32_t N, uint32_t max_steps) {
-    // scan workspace | cull grid of the time slice | t of every sample [N, max_steps]
-    const uint64_t head = (train_scratch_words(N) * sizeof(uint32_t) + 15u) & ~(uint64_t)15u;
-    const uint64_t cull = ((uint64_t)(kCullWords + 8u) * sizeof(uint32_t) + 15u) & ~(uint64_t)15u;
-    return head + cull + (uint64_t)N * max_steps * sizeof(float);
+    return train_scratch(N).sample_t + (uint64_t)N * max_steps * sizeof(float);
 }
 
 int sdn_march_rays_train(const float *rays_o, const float *rays_d, const uint8_t *grid, float bound, float dt_gamma,
@@ -1938,16 +1957,16 @@ int sdn_int::march_rays_train(const float *rays_o, const float *rays_d, const ui
     const uint32_t nb = sdn_div_up(N, kScanBlock);
     uint32_t *block_totals = num_steps + N;
     uint32_t *base_out = block_totals + nb;
-    const uint64_t head = (train_scratch_words(N) * sizeof(uint32_t) + 15u) & ~(uint64_t)15u;
-    const uint64_t cull_bytes = ((uint64_t)(kCullWords + 8u) * sizeof(uint32_t) + 15u) & ~(uint64_t)15u;
-    const uint32_t *cull = (const uint32_t *)((unsigned char *)scratch + head);
-    float *sample_t = (float *)((unsigned char *)scratch + head + cull_bytes);
+    const TrainScratch off = train_scratch(N);
+    uint32_t *own_cull = (uint32_t *)((unsigned char *)scratch + off.cull);
+    const uint32_t *cull = own_cull;
+    float *sample_t = (float *)((unsigned char *)scratch + off.sample_t);
     const bool fast = fast_config(bound, C, H);
     const bool use_cull = fast && H == 128;
     if (use_cull && prebuilt_cull) {
         cull = (const uint32_t *)prebuilt_cull;
     } else if (use_cull) {
-        int rc = sdn_int::build_cull(grid, (uint32_t *)((unsigned char *)scratch + head), st, false);   // (the scratch has no room for the image)
+        int rc = sdn_int::build_cull(grid, own_cull, st, false);   // (the scratch has no room for the image)
         if (rc) return rc;
     }
     if (fast && dt_gamma == 0.0f && H <= 256u)   // constant step: one WAVE per ray (k_march_train_count_wave), same samples bit for bit
@@ -2026,19 +2045,12 @@ static int launch_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *r
     if ((live_idx == nullptr) != (live_count == nullptr)) return SDN_E_BADARG;
     const uint32_t base = n_alive * n_step;
     if (M_pad < base) M_pad = base;
-    const uint32_t threads = n_alive + (M_pad - base);  // one lane per alive ray + one per tail slot
-    const dim3 g(sdn_div_up(threads, 256u)), b(256);
-    if (fast_config(bound, C, H)) {
-        if (cull && H != 128) cull = nullptr;  // the cull grid is built for the 128^3 grid only
-        hipLaunchKernelGGL(k_march_rays<true>, g, b, 0, st, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H,
-                           grid, fars, xyzs, dirs, deltas, noises, M_pad, cull, live_idx, live_count, (const int32_t *)nullptr,
-                           (const int32_t *)nullptr, FrameSel(), (const float *)nullptr);
-    } else {
-        hipLaunchKernelGGL(k_march_rays<false>, g, b, 0, st, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H,
-                           grid, fars, xyzs, dirs, deltas, noises, M_pad, (const uint32_t *)nullptr, live_idx, live_count,
-                           (const int32_t *)nullptr, (const int32_t *)nullptr, FrameSel(), (const float *)nullptr);
-    }
-    return sdn_launch_status();
+    MarchRays m;
+    m.threads = n_alive + (M_pad - base);  // one lane per alive ray + one per tail slot
+    m.n_alive = n_alive; m.n_step = n_step; m.rays_alive = rays_alive; m.rays_t = rays_t; m.rays_o = rays_o; m.rays_d = rays_d;
+    m.bound = bound; m.dt_gamma = dt_gamma; m.max_steps = max_steps; m.C = C; m.H = H; m.grid = grid; m.fars = fars;
+    m.xyzs = xyzs; m.dirs = dirs; m.deltas = deltas; m.noises = noises; m.M_pad = M_pad; m.cull = cull; m.live_idx = live_idx; m.live_count = live_count;
+    return launch_k_march_rays(m, st);
 }
 
 int sdn_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t, const float *rays_o,
@@ -2064,11 +2076,7 @@ int sdn_build_cull_grid(const uint8_t *bitfield, uint32_t H, uint8_t *cull_grid,
     if (!bitfield || !cull_grid) return SDN_E_BADARG;
     if (H != 128) return SDN_E_UNSUPPORTED;
     if (((uintptr_t)bitfield & 7u) != 0 || ((uintptr_t)cull_grid & 15u) != 0) return SDN_E_BADARG;
-    hipLaunchKernelGGL(k_cull_meta_init, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t *)cull_grid, 1u, 0u);
-    hipLaunchKernelGGL(k_build_cull_grid, dim3(kCullRes * kCullRes * kCullRes / 256), dim3(256), 0, (hipStream_t)stream, bitfield,
-                       (uint32_t *)cull_grid, FrameSel());
-    hipLaunchKernelGGL(k_build_fine_image, dim3(kFineCacheCells / 256), dim3(256), 0, (hipStream_t)stream, bitfield, (uint32_t *)cull_grid, FrameSel());
-    return sdn_launch_status();
+    return sdn_int::build_cull(bitfield, (uint32_t *)cull_grid, (hipStream_t)stream);
 }
 
 int sdn_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *rays_alive, float *rays_t, const float *sigmas,

@@ -22,20 +22,16 @@ int render_begin(const SdnRenderCtx *c, void *mailbox, uint32_t frame_tag, hipSt
         int rc0 = sdn_near_far_from_aabb(c->rays_o, c->rays_d, c->aabb, c->N, c->min_near, (float *)c->nears, (float *)c->fars, st);
         if (rc0) return rc0;
     }
-    int rc = loop_begin(c->N, c->max_steps, c->nears, c->alive_a, c->rays_t, c->weights_sum, c->depth, c->image, c->state, c->live_counts,
-                        c->n_counters, mailbox, frame_tag, c->rays_tend, st);
+    int rc = loop_begin(*c, mailbox, frame_tag, st);
     if (rc) return rc;
-    if (c->H == 128 && c->C == 1) {
+    if (has_loop_cull(*c)) {
         const uint32_t nf = c->n_group_frames > 1 ? c->n_group_frames : 1u;
         bool kept = true;
         for (uint32_t f = 0; f < nf; f++) kept = kept && c->frame_cull[f] != nullptr;
         if (kept) rc = copy_cull(c->frame_cull, nf, (uint32_t *)c->cull_bits, st);
-        else rc = c->n_group_frames > 1 ? build_cull_group(frame_sel(c), (uint32_t *)c->cull_bits, st) : build_cull(c->bitfield, (uint32_t *)c->cull_bits, st);
+        else rc = c->n_group_frames > 1 ? build_cull_group(frame_sel(*c), (uint32_t *)c->cull_bits, st) : build_cull(c->bitfield, (uint32_t *)c->cull_bits, st);
         // iteration 0 on the rays that pass the exact cull test (same samples, same trace; raymarching.hip k_cull_start)
-        if (!rc && c->rays_tend)
-            rc = loop_cull_start(c->N, c->rays_o, c->rays_d, c->nears, c->fars, c->bound, c->dt_gamma, c->C, c->H, (const uint32_t *)c->cull_bits, frame_sel(c),
-                                 c->alive_a, c->alive_b, (float *)c->rays_tend, c->state, (uint32_t *)c->block_totals, c->trace + 2 * (size_t)c->n_counters + 8,
-                                 c->trace, c->max_steps, c->sigmas, st);   // (sigmas: unused until the first field launch -- holds the per-ray jump targets)
+        if (!rc && c->rays_tend) rc = loop_cull_start(*c, st);
     }
     return rc;
 }
@@ -53,53 +49,45 @@ int sdn_render_time_kernel(int which) {
     return 0;
 }
 
-int sdn_render_finish(const SdnRenderCtx *c, float bg_color, float *image_out, float *depth_out, void *stream);
-int sdn_render_step_f16_ev(const SdnRenderCtx *c, uint32_t bound_alive, void *ev_field_begin, void *ev_field_end, void *stream);
-
 // SealD edit hooks of an iteration (no-ops without ctx->seal): samples back to their origin before the field network, colours of
 // the mapped samples after it.  m_slots bounds the slots the marcher wrote this iteration.
-static int seal_map(const SdnRenderCtx *c, uint32_t m_slots, hipStream_t st) {
-    const SdnSealBox *s = c->seal;
+static int seal_map(const SdnRenderCtx &c, uint32_t m_slots, hipStream_t st) {
+    const SdnSealBox *s = c.seal;
     if (!s) return 0;
-    if (!c->seal_mask) return SDN_E_BADARG;
+    if (!c.seal_mask) return SDN_E_BADARG;
     if (s->has_map_source) {
         if (!s->scratch) return SDN_E_BADARG;
-        return sdn_seal_bbox_map_source(c->xyzs, c->dirs, m_slots, s->bounds, s->n_bounds, s->tris, s->n_tris, s->test_dir, s->tinv, s->rinv,
-                                        s->scale, s->center, s->source_bound, s->map_source, (uint32_t *)((char *)s->scratch + 16), c->seal_mask,
-                                        c->live_idx, (const uint32_t *)c->live_counts, c->state, st);
+        return sdn_seal_bbox_map_source(c.xyzs, c.dirs, m_slots, s->bounds, s->n_bounds, s->tris, s->n_tris, s->test_dir, s->tinv, s->rinv,
+                                        s->scale, s->center, s->source_bound, s->map_source, (uint32_t *)((char *)s->scratch + 16), c.seal_mask,
+                                        c.live_idx, sdn_int::live_counters(c), c.state, st);
     }
-    return sdn_seal_bbox_map(c->xyzs, c->dirs, m_slots, s->bounds, s->n_bounds, s->tris, s->n_tris, s->test_dir, s->tinv, s->rinv, s->scale,
-                             s->center, c->seal_mask, st);
+    return sdn_seal_bbox_map(c.xyzs, c.dirs, m_slots, s->bounds, s->n_bounds, s->tris, s->n_tris, s->test_dir, s->tinv, s->rinv, s->scale,
+                             s->center, c.seal_mask, st);
 }
-static int seal_color(const SdnRenderCtx *c, uint32_t m_slots, hipStream_t st) {
-    const SdnSealBox *s = c->seal;
+static int seal_color(const SdnRenderCtx &c, uint32_t m_slots, hipStream_t st) {
+    const SdnSealBox *s = c.seal;
     if (!s) return 0;
     int rc = 0;
-    if (s->modify_hsv) rc = sdn_seal_modify_hsv(c->rgbs, c->seal_mask, m_slots, s->hsv[0], s->hsv[1], s->hsv[2], st);    // map_color's order: hsv, then rgb
+    if (s->modify_hsv) rc = sdn_seal_modify_hsv(c.rgbs, c.seal_mask, m_slots, s->hsv[0], s->hsv[1], s->hsv[2], st);    // map_color's order: hsv, then rgb
     if (!rc && s->modify_rgb) {
         if (!s->scratch) return SDN_E_BADARG;
-        rc = sdn_seal_modify_rgb(c->rgbs, c->seal_mask, m_slots, s->rgb[0], s->rgb[1], s->rgb[2], s->rgb_light_offset, s->scratch, c->live_idx,
-                                 (const uint32_t *)c->live_counts, c->state, st);
+        rc = sdn_seal_modify_rgb(c.rgbs, c.seal_mask, m_slots, s->rgb[0], s->rgb[1], s->rgb[2], s->rgb_light_offset, s->scratch, c.live_idx,
+                                 sdn_int::live_counters(c), c.state, st);
     }
     return rc;
 }
 
 // the fused field network on this iteration's samples (live list, count on the device): the `-O` kernel, or the fp32 one (ctx->field_f32)
-static int launch_field(const SdnRenderCtx *c, uint32_t m_bound, uint32_t expect_points, hipStream_t st) {
-    if (c->field_f32 == 2)
-        return sdn_int::field_forward_f32x3(c->xyzs, c->dirs, c->live_idx, (const uint32_t *)c->live_counts, c->state, m_bound,
-                                            (const float *)c->field_weights, c->field_bias0, (const float *)c->grid_table, c->grid_offsets, c->grid_S,
-                                            c->grid_H, c->bound, c->density_scale, c->zero_deform, c->sigmas, c->rgbs, nullptr,
-                                            c->n_group_frames > 1 ? c->slot_frame : nullptr, c->n_group_frames > 1 ? c->n_group_frames : 1u, st);
-    if (c->field_f32)
-        return sdn_int::field_forward_f32(c->xyzs, c->dirs, c->live_idx, (const uint32_t *)c->live_counts, c->state, m_bound,
-                                          (const float *)c->field_weights, c->field_bias0, (const float *)c->grid_table, c->grid_offsets, c->grid_S,
-                                          c->grid_H, c->bound, c->density_scale, c->zero_deform, c->sigmas, c->rgbs, nullptr,
-                                          c->n_group_frames > 1 ? c->slot_frame : nullptr, c->n_group_frames > 1 ? c->n_group_frames : 1u, st);
-    return sdn_int::field_forward_f16(c->xyzs, c->dirs, c->live_idx, (const uint32_t *)c->live_counts, c->state, m_bound, c->field_weights,
-                                      c->field_bias0, c->grid_table, c->grid_offsets, c->grid_S, c->grid_H, c->bound, c->density_scale,
-                                      c->zero_deform, c->sigmas, c->rgbs, expect_points, c->n_group_frames > 1 ? c->slot_frame : nullptr,
-                                      c->n_group_frames > 1 ? c->n_group_frames : 1u, st);
+static int launch_field(const SdnRenderCtx &c, uint32_t m_bound, uint32_t expect_points, hipStream_t st) {
+    const bool group = c.n_group_frames > 1;
+    return sdn_int::field_forward(c.field_f32,
+                                  {.xyzs = c.xyzs, .dirs = c.dirs, .live_idx = c.live_idx, .live_count = sdn_int::live_counters(c), .state = c.state,
+                                   .M = m_bound, .weights = c.field_weights, .bias0 = c.field_bias0, .table = c.grid_table,
+                                   .offsets_host = c.grid_offsets, .S = c.grid_S, .H = c.grid_H, .bound = c.bound,
+                                   .density_scale = c.density_scale, .zero_deform = c.zero_deform, .sigmas = c.sigmas, .rgbs = c.rgbs,
+                                   .expect_points = expect_points, .slot_frame = group ? c.slot_frame : nullptr,
+                                   .n_frames = group ? c.n_group_frames : 1u},
+                                  st);
 }
 
 static bool ctx_ok(const SdnRenderCtx *c) {
@@ -130,29 +118,24 @@ int sdn_render_step_f16_ev(const SdnRenderCtx *c, uint32_t bound_alive, void *ev
     if (!c || bound_alive == 0) return SDN_E_BADARG;
     if (bound_alive > c->N) bound_alive = c->N;
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t *cull = (c->H == 128 && c->C == 1) ? (const uint32_t *)c->cull_bits : nullptr;
     const bool time_march = g_timed_kernel.load() == 1;
     if (time_march && ev_field_begin) (void)hipEventRecord((hipEvent_t)ev_field_begin, st);
-    int rc = sdn_int::loop_march(bound_alive, c->alive_a, c->alive_b, c->rays_t, c->rays_o, c->rays_d, c->bound, c->dt_gamma, c->max_steps,
-                                 c->C, c->H, c->bitfield, c->fars, c->xyzs, c->dirs, c->deltas, cull, c->live_idx,
-                                 (uint32_t *)c->live_counts, c->state, sdn_int::frame_sel(c), st, c->rays_tend ? c->sigmas : nullptr);
+    int rc = sdn_int::loop_march(*c, bound_alive, st);
     if (time_march && ev_field_end) (void)hipEventRecord((hipEvent_t)ev_field_end, st);
     if (time_march) ev_field_begin = ev_field_end = nullptr;
     if (rc) return rc;
     // n_alive * n_step <= N always (n_step <= N / n_alive), and <= 8 * bound_alive
     uint64_t m_bound = (uint64_t)bound_alive * 8u;
     if (m_bound > c->N) m_bound = c->N;
-    rc = seal_map(c, (uint32_t)m_bound, st);
+    rc = seal_map(*c, (uint32_t)m_bound, st);
     if (rc) return rc;
     if (ev_field_begin) (void)hipEventRecord((hipEvent_t)ev_field_begin, st);
-    rc = launch_field(c, (uint32_t)m_bound, 0u, st);
+    rc = launch_field(*c, (uint32_t)m_bound, 0u, st);
     if (ev_field_end) (void)hipEventRecord((hipEvent_t)ev_field_end, st);
     if (rc) return rc;
-    rc = seal_color(c, (uint32_t)m_bound, st);
+    rc = seal_color(*c, (uint32_t)m_bound, st);
     if (rc) return rc;
-    return sdn_int::loop_composite_compact(bound_alive, c->T_thresh, c->alive_a, c->alive_b, c->rays_t, c->sigmas, c->rgbs, c->deltas,
-                                           c->weights_sum, c->depth, c->image, c->state, (uint32_t *)c->block_totals, c->n_out, c->trace,
-                                           c->trace + 2 * (size_t)c->n_counters, st);
+    return sdn_int::loop_composite_compact(*c, bound_alive, st);
 }
 
 // Whole-frame driver: begin + iterations + finish in one call, so the per-iteration host work is a handful of HIP API
@@ -214,11 +197,9 @@ struct FrameRun {
         }
         return sdn_int::render_begin(c, mail_dev, tag, st);
     }
-    const uint32_t *cull() const { return (c->H == 128 && c->C == 1) ? (const uint32_t *)c->cull_bits : nullptr; }
 
     // enqueue iteration `it` and the asynchronous read-back of its survivor count
     int enqueue() {
-        int32_t *snap_dev = c->trace + 2 * (size_t)c->n_counters;
         void *e0 = (ev_field && it < max_field_events) ? ev_field[2 * it] : nullptr;
         void *e1 = (ev_field && it < max_field_events) ? ev_field[2 * it + 1] : nullptr;
         int rc;
@@ -227,32 +208,25 @@ struct FrameRun {
         } else {
             uint64_t m_bound = (uint64_t)bound * 8u;
             if (m_bound > c->N) m_bound = c->N;
-            rc = seal_map(c, (uint32_t)m_bound, st);
+            rc = seal_map(*c, (uint32_t)m_bound, st);
             if (rc) return rc;
             const bool time_march = g_timed_kernel.load() == 1;
             void *m0 = time_march ? e0 : nullptr, *m1 = time_march ? e1 : nullptr;
             if (time_march) e0 = e1 = nullptr;
             if (e0) (void)hipEventRecord((hipEvent_t)e0, st);
-            rc = launch_field(c, (uint32_t)m_bound, last_alive * 8u, st);
+            rc = launch_field(*c, (uint32_t)m_bound, last_alive * 8u, st);
             if (e1) (void)hipEventRecord((hipEvent_t)e1, st);
-            if (!rc) rc = seal_color(c, (uint32_t)m_bound, st);
+            if (!rc) rc = seal_color(*c, (uint32_t)m_bound, st);
             if (!rc && m0) (void)hipEventRecord((hipEvent_t)m0, st);
             if (!rc && recompact) {
                 // composite this iteration on the frozen list, compact it, freeze the shorter list and march the next iteration on it
-                rc = sdn_int::loop_composite_compact(bound, c->T_thresh, c->alive_a, c->alive_b, c->rays_t, c->sigmas, c->rgbs, c->deltas, c->weights_sum,
-                                                     c->depth, c->image, c->state, (uint32_t *)c->block_totals, c->n_out, c->trace, snap_dev, st, true);
+                rc = sdn_int::loop_composite_compact(*c, bound, st, true);
                 const uint32_t nb = last_alive < bound ? last_alive : bound;     // the new list: at most the rays alive when this iteration began
-                if (!rc)
-                    rc = sdn_int::loop_steady_begin(nb, c->alive_a, c->alive_b, c->rays_t, c->rays_o, c->rays_d, c->bound, c->dt_gamma, c->max_steps, c->C,
-                                                    c->H, c->bitfield, c->fars, c->xyzs, c->dirs, c->deltas, cull(), c->live_idx, (uint32_t *)c->live_counts,
-                                                    c->state, sdn_int::frame_sel(c), st, true);
+                if (!rc) rc = sdn_int::loop_steady_begin(*c, nb, st, true);
                 bound = list_bound = nb;
                 recompact = false;
             } else if (!rc)
-                rc = sdn_int::loop_composite_march(bound, c->T_thresh, c->alive_a, c->alive_b, c->rays_t, c->rays_o, c->rays_d, c->bound,
-                                                   c->dt_gamma, c->max_steps, c->C, c->H, c->bitfield, c->fars, c->sigmas, c->rgbs, c->xyzs,
-                                                   c->dirs, c->deltas, c->weights_sum, c->depth, c->image, cull(), c->live_idx,
-                                                   (uint32_t *)c->live_counts, c->state, c->n_out, c->trace, snap_dev, sdn_int::frame_sel(c), st);
+                rc = sdn_int::loop_composite_march(*c, bound, st);
             if (!rc && m1) (void)hipEventRecord((hipEvent_t)m1, st);
         }
         if (rc) return rc;
@@ -260,7 +234,7 @@ struct FrameRun {
         const uint32_t slot = it & 3u;
         hipError_t e = hipEventRecord((hipEvent_t)ev_main[slot], st);
         if (e == hipSuccess) e = hipStreamWaitEvent(side, (hipEvent_t)ev_main[slot], 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(host_snap + 2 * slot, snap_dev + 2 * slot, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, side);
+        if (e == hipSuccess) e = hipMemcpyAsync(host_snap + 2 * slot, sdn_int::snap_ring(*c) + 2 * slot, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, side);
         if (e == hipSuccess) e = hipEventRecord((hipEvent_t)ev_copy[slot], side);
         return (int)e;
     }
@@ -316,9 +290,7 @@ struct FrameRun {
                 bound = (uint32_t)n_prev;
                 if ((uint64_t)n_prev * 8u <= c->N) {
                     // iteration `it` (enqueued, normal mode) ends with a compacted list; freeze it and march iteration it+1
-                    int rc = sdn_int::loop_steady_begin(bound, c->alive_a, c->alive_b, c->rays_t, c->rays_o, c->rays_d, c->bound, c->dt_gamma,
-                                                        c->max_steps, c->C, c->H, c->bitfield, c->fars, c->xyzs, c->dirs, c->deltas, cull(),
-                                                        c->live_idx, (uint32_t *)c->live_counts, c->state, sdn_int::frame_sel(c), st);
+                    int rc = sdn_int::loop_steady_begin(*c, bound, st);
                     if (rc) return rc;
                     steady = true;
                     list_bound = bound;
@@ -513,8 +485,7 @@ int sdn_host_mailbox_free(void *p) { return p ? (int)hipHostFree(p) : 0; }
 
 int sdn_render_finish(const SdnRenderCtx *c, float bg_color, float *image_out, float *depth_out, void *stream) {
     if (!c || !image_out || !depth_out) return SDN_E_BADARG;
-    return sdn_int::loop_finish(c->N, c->nears, c->fars, c->weights_sum, c->depth, c->image, bg_color, image_out, depth_out,
-                                (hipStream_t)stream);
+    return sdn_int::loop_finish(*c, bg_color, image_out, depth_out, (hipStream_t)stream);
 }
 
 }  // extern "C"
