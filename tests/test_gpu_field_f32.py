@@ -61,14 +61,15 @@ def test_fp32_fused_field_vs_oracle_and_op_by_op_network(small_scene, t, variant
     assert float(s.max()) > 1.0 and 0.0 < float(c.min()) and float(c.max()) < 1.0
 
 
-def test_fp32_fused_field_live_list_leaves_other_slots_alone(small_scene):
+@pytest.mark.parametrize("variant", ["split", "mfma32"])
+def test_fp32_fused_field_live_list_leaves_other_slots_alone(small_scene, variant):
     from dnerf_amd.fused_f32 import FusedFieldF32
     from dnerf_amd.bench_scene import _probe_points
     sc = small_scene
     n = 3000
     x = torch.from_numpy(_probe_points(sc.bitfield, n, 9)).cuda()
     d = torch.nn.functional.normalize(torch.randn(n, 3, device="cuda"), dim=1).contiguous()
-    f = FusedFieldF32(sc.model, 0.4)
+    f = FusedFieldF32(sc.model, 0.4, variant=variant)
     s_all, c_all = f(x, d)
     s_all, c_all = s_all.clone(), c_all.clone()
     idx = torch.randperm(n, device="cuda")[:1111].to(torch.int32).contiguous()
