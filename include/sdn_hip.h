@@ -342,8 +342,29 @@ int sdn_ffmlp_backward(const void *grad, const void *inputs, const void *weights
  * ------------------------------------------------------------------------- */
 /* All pointers are device pointers owned by the caller except grid_offsets (17 host ints, copied by value).
  * Buffer sizes: per-ray arrays N; sample arrays M_cap >= N + 128 rows; live_counts n_counters >= max_steps + 8;
- * state 16 ints; trace 2 * n_counters + 16 (ints 2 * n_counters .. +8 are a 4-deep ring of {alive rays entering the next iteration, iteration
+ * state 16 ints (SdnLoopRecord below); trace 2 * n_counters + 16 (ints 2 * n_counters .. +8 are a 4-deep ring of {alive rays entering the next iteration, iteration
  * number} snapshots for asynchronous read-back, the int after them a survivor-count scratch word); block_totals ceil(N / 256) + 1; n_out 1 int, zero on entry (ticket counter); cull_bits sdn_cull_grid_bytes(). */
+/* The loop record: the 16 ints of SdnRenderCtx::state.  Device memory, initialised by sdn_render_begin and from then on written only by
+ * the loop's kernels, one writer at a time (a one-thread kernel, or the workgroup of a launch that draws the last ticket); every loop kernel
+ * and the fused field read their sizes from it, so no iteration needs a host round trip.  The host may read it after the frame. */
+typedef struct SdnLoopRecord {
+    int32_t n_alive;        /* rays entering the current iteration (length of the compacted alive list); 0: the loop is over, launches are no-ops */
+    int32_t n_step;         /* samples per ray of the current iteration: max(min(N / n_alive, 8), 1) */
+    int32_t steps_done;     /* sum of n_step over the iterations done; the loop ends once it reaches max_steps */
+    int32_t iteration;      /* iterations done = index of the current one: live_counts[iteration] is its sample count, trace holds
+                             * {n_alive, n_step} of every iteration before it */
+    int32_t side;           /* ping-pong side: 0 = the alive list is alive_a, 1 = alive_b */
+    int32_t N;              /* rays of the frame (or frame group) */
+    int32_t max_steps;
+    int32_t advance_calls;  /* advances so far, those of no-op iterations included: slot (calls & 3) of the snapshot ring / mailbox is next */
+    int32_t frozen_len;     /* steady mode: length of the frozen (no longer compacted) alive list, dead entries = -1 included; 0 outside it */
+    int32_t survivors;      /* steady mode: survivor count the workgroups of a composite+march launch add up; zero between launches */
+    int32_t mailbox_lo, mailbox_hi;   /* device-visible pointer of the host mailbox (coherent host memory), 0 = none */
+    int32_t frame_tag;      /* tag of the frame in the mailbox words, so that a stale word of an earlier frame is not taken for this one's */
+    int32_t tend_lo, tend_hi;         /* pointer of the per-ray t_end cache (SdnRenderCtx::rays_tend), 0 = none */
+    int32_t culled_start;   /* 1: iteration 0 runs on the culled list (sdn_render_begin's culled start); the trace logs N for it */
+} SdnLoopRecord;
+
 /* Arguments of sdn_seal_bbox_map(_source) / sdn_seal_modify_hsv / sdn_seal_modify_rgb as one record (host memory except `tris`), for SdnRenderCtx.seal. */
 typedef struct SdnSealBox {
     float bounds[24];          /* n_bounds x {lo xyz, hi xyz} */
@@ -438,8 +459,8 @@ typedef struct SdnRenderCtx {
  * the cull grid of `bitfield`. */
 int sdn_render_begin(const SdnRenderCtx *ctx, void *stream);
 /* Enqueues one loop iteration (march -> fused field -> composite -> compact -> advance).  bound_alive: any upper bound of
- * the current number of alive rays (N is always valid; tighter bounds launch fewer idle workgroups).  The record is
- * state = {n_alive, n_step, steps done, iteration, side, N, max_steps, -}; an iteration with n_alive == 0 is a no-op. */
+ * the current number of alive rays (N is always valid; tighter bounds launch fewer idle workgroups).  `state` is an
+ * SdnLoopRecord; an iteration with n_alive == 0 is a no-op. */
 int sdn_render_step_f16(const SdnRenderCtx *ctx, uint32_t bound_alive, void *stream);
 /* Same, recording the two given hipEvent_t (may be NULL) on `stream` immediately before / after the fused-field launch, so
  * a caller can time the dominant kernel in place (bench.py's roofline). */
@@ -494,7 +515,7 @@ int sdn_seal_bbox_map(float *xyzs, float *dirs, uint32_t M, const float *bounds,
 /* The same with the seal config's `mapSource` option (seal_utils.py:238-240,269-273): in a call that maps at least one sample -- the
  * reference returns early otherwise, :251-252 -- every unmapped sample strictly inside source_bound {lo xyz, hi xyz} (host) moves to
  * map_source [3] (host).  flag: one device word owned by the caller, zeroed once (the kernels only raise it to a per-call tag).
- * "The call's samples" are the M slots, or -- live_idx / live_count (/ state: the count is live_count[state[3]]) given -- the listed
+ * "The call's samples" are the M slots, or -- live_idx / live_count (/ state: the count is live_count[SdnLoopRecord::iteration]) given -- the listed
  * slots: the device-driven loop's sample buffers may hold stale slots of earlier iterations beyond the live ones. */
 int sdn_seal_bbox_map_source(float *xyzs, float *dirs, uint32_t M, const float *bounds, uint32_t n_bounds, const float *tris,
                              uint32_t n_tris, const float *test_dir, const float *tinv, const float *rinv, const float *scale,

@@ -90,7 +90,7 @@ struct FieldArgs {
     const float *dirs;        // [M,3]
     const uint32_t *live_idx; // [<=M] slot indices to evaluate, or nullptr = all M slots
     const uint32_t *live_count;
-    const int32_t *state;     // device-driven loop: the count is live_count[state[3]] (one counter per iteration), else nullptr
+    const int32_t *state;     // device-driven loop: the count is live_count[SdnLoopRecord::iteration] (one counter per iteration), else nullptr
     uint32_t M;
     const unsigned char *weights;  // kBlkTotal KiB, fragment order
     const float *bias0;       // [128] time-encoding contribution to the first deform layer
@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
         s_lv[l][0] = make_uint4(lv.offset[l], lv.s1[l], lv.s2[l], lv.hsize[l]);
         s_lv[l][1] = make_uint4(lv.mask[l], __float_as_uint(lv.scale[l]), 0u, 0u);
     }
-    const uint32_t count = P.state ? P.live_count[P.state[3]] : (P.live_idx ? *P.live_count : P.M);
+    const uint32_t count = P.state ? P.live_count[sdn_loop(P.state)->iteration] : (P.live_idx ? *P.live_count : P.M);
     if (blockIdx.x * (uint32_t)kPointsPerWG >= count) return;  // workgroup-uniform: nothing to do, no barrier touched
     const uint32_t n = lane & 31u, h = lane >> 5;
     const uint32_t i = blockIdx.x * (uint32_t)kPointsPerWG + wave * 32u + n;

@@ -70,7 +70,7 @@ __device__ __forceinline__ bool load_point(const F32Args &P, Point &p) {
     p.lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     p.h = p.lane >> 5; p.n = p.lane & 31u;
-    const uint32_t count = P.state ? P.live_count[P.state[3]] : (P.live_idx ? *P.live_count : P.M);
+    const uint32_t count = P.state ? P.live_count[sdn_loop(P.state)->iteration] : (P.live_idx ? *P.live_count : P.M);
     if (blockIdx.x * (uint32_t)kPointsPerWG >= count) return false;
     const uint32_t i = blockIdx.x * (uint32_t)kPointsPerWG + wave * 32u + p.n;
     p.valid = i < count;

@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(64 * kPPWaves) k_field_pp_f16(FieldArgs P, Til
         s_lv[l][0] = make_uint4(lv.offset[l], lv.s1[l], lv.s2[l], lv.hsize[l]);
         s_lv[l][1] = make_uint4(lv.mask[l], __float_as_uint(lv.scale[l]), 0u, 0u);
     }
-    const uint32_t count = P.state ? P.live_count[P.state[3]] : (P.live_idx ? *P.live_count : P.M);
+    const uint32_t count = P.state ? P.live_count[sdn_loop(P.state)->iteration] : (P.live_idx ? *P.live_count : P.M);
     const uint32_t n_tiles = (count + kPPTile - 1u) / kPPTile;
     if (blockIdx.x >= n_tiles) return;                                   // workgroup-uniform, before any barrier
     // G workgroups share the tiles (the launch is sized before the live count is known).  Optional (pp_soft bit 31 clear): the fewest

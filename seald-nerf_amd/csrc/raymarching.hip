@@ -289,6 +289,39 @@ __global__ void __launch_bounds__(256) k_build_fine_image(const uint8_t *__restr
     img[i] = blocks[morton3D_8bit((uint32_t)cx, (uint32_t)cy, (uint32_t)cz)];
 }
 
+// The range of the cull scan: ds, the parameter step of one cull cell along the ray, and the part [s0, s1] of [t, far] to scan.  Marked
+// cells only exist inside their bounding box (origin b*0, extent bn*, in cull cells): only the part of [t, far] that can be inside it is
+// scanned (slab test, widened by one scan step against rounding), not the whole chord of the unit cube.  may == false: the ray meets
+// no marked cell (nothing is marked, or the segment misses the box).
+struct CullRange { bool may; float s0, s1, ds; };
+__device__ __forceinline__ CullRange cull_scan_range(float ox, float oy, float oz, float dx, float dy, float dz, float t, float far,
+                                                     int bx0, int by0, int bz0, int bnx, int bny, int bnz) {
+    CullRange r;
+    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+    r.ds = (2.0f / kCullRes) / fmaxf(len, 1e-12f);
+    r.s0 = t; r.s1 = far;
+    r.may = !(bnx <= 0 || bny <= 0 || bnz <= 0);              // nothing is marked: nothing is occupied
+    if (r.may) {
+        const float cw = 2.0f / kCullRes;
+        const float lo[3] = {(float)bx0 * cw - 1.0f, (float)by0 * cw - 1.0f, (float)bz0 * cw - 1.0f};
+        const float hi[3] = {(float)(bx0 + bnx) * cw - 1.0f, (float)(by0 + bny) * cw - 1.0f, (float)(bz0 + bnz) * cw - 1.0f};
+        const float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz};
+        #pragma unroll
+        for (int a = 0; a < 3; a++) {
+            if (d[a] != 0.0f) {
+                const float q = 1.0f / d[a];
+                const float ta = (lo[a] - o[a]) * q, tb = (hi[a] - o[a]) * q;
+                r.s0 = fmaxf(r.s0, fminf(ta, tb) - r.ds);
+                r.s1 = fminf(r.s1, fmaxf(ta, tb) + r.ds);
+            } else if (o[a] < lo[a] - cw || o[a] > hi[a] + cw) {
+                r.may = false;                                 // parallel to the slab and outside it
+            }
+        }
+        if (!(r.s0 <= r.s1)) r.may = false;
+    }
+    return r;
+}
+
 // Scans the remaining segment [t, far] once per cull-cell width.  Returns false if no marked cell is met (the ray
 // cannot produce a sample).  Otherwise t_end receives a parameter beyond which no marked cell is met any more: the
 // marcher may stop there -- the reference would only step through empty voxels from there to `far`.
@@ -298,32 +331,11 @@ __device__ __forceinline__ bool ray_may_hit(const uint32_t *cull_bits, float ox,
                                             float t, float far, float &t_end, int bx0, int by0, int bz0, int bnx, int bny, int bnz,
                                             float *t_safe = nullptr) {
     if (t_safe) *t_safe = -__FLT_MAX__;
-    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    const float ds = (2.0f / kCullRes) / fmaxf(len, 1e-12f);  // parameter step = one cull cell along the ray
     t_end = far;
-    if (bnx <= 0 || bny <= 0 || bnz <= 0) return false;       // nothing is marked: nothing is occupied
-    // Marked cells only exist inside their bounding box: scan just the part of [t, far] that can be inside it (slab test,
-    // widened by one scan step against rounding), not the whole chord of the unit cube.
-    const float cw = 2.0f / kCullRes;
-    float s0 = t, s1 = far;
-    {
-        const float lo[3] = {(float)bx0 * cw - 1.0f, (float)by0 * cw - 1.0f, (float)bz0 * cw - 1.0f};
-        const float hi[3] = {(float)(bx0 + bnx) * cw - 1.0f, (float)(by0 + bny) * cw - 1.0f, (float)(bz0 + bnz) * cw - 1.0f};
-        const float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz};
-        #pragma unroll
-        for (int a = 0; a < 3; a++) {
-            if (d[a] != 0.0f) {
-                const float r = 1.0f / d[a];
-                const float ta = (lo[a] - o[a]) * r, tb = (hi[a] - o[a]) * r;
-                s0 = fmaxf(s0, fminf(ta, tb) - ds);
-                s1 = fminf(s1, fmaxf(ta, tb) + ds);
-            } else if (o[a] < lo[a] - cw || o[a] > hi[a] + cw) {
-                return false;                                  // parallel to the slab and outside it
-            }
-        }
-    }
-    if (!(s0 <= s1)) return false;
-    float s = s0;
+    const CullRange r = cull_scan_range(ox, oy, oz, dx, dy, dz, t, far, bx0, by0, bz0, bnx, bny, bnz);
+    if (!r.may) return false;
+    const float ds = r.ds, s1 = r.s1;
+    float s = r.s0;
     bool hit = false;
     // bounded: a unit-cube diagonal is 2*sqrt(3) / (2/32) = 56 cells; anything longer (degenerate direction, huge far)
     // falls through to "may hit, no early end" and takes the ordinary marcher
@@ -523,22 +535,32 @@ __global__ void __launch_bounds__(256) k_march_train_count(const float *__restri
 // waves busy for as long as its longest ray.  Occupancy bits and cull marks are read from global memory (L2-resident, 256 KiB +
 // 4 KiB): a probe round is one parallel load, an LDS image per 4-ray workgroup would cost more than it saves.
 // ---------------------------------------------------------------------------------------------------------------------------
+// The closed form of the lattice L_0 = t, L_(k+1) = fl(L_k + dt).  While L stays in one binade every L_k is a multiple of the binade's
+// ulp U, so fl(L_k + dt) = L_k + c with the SAME c = round(dt / U) U for every k -- unless dt / U sits exactly between two integers (a tie
+// rounds to even, which depends on L_k).  Then L_k = t + k c exactly (k c and the sum are multiples of U below 2^24 U).  Returns whether
+// that holds at t, with the step c and t's biased exponent eb (which must be below eb_ceiling); staying inside the binade for as many
+// steps as it looks at is the caller's to check.
+__device__ __forceinline__ bool lattice_closed_form(float t, float dt, uint32_t eb_ceiling, float &c, uint32_t &eb) {
+    const float first = t + dt;
+    c = first - t;                                                  // exact (Sterbenz-like: both multiples of U, |c| << t)
+    const float err = dt - c;                                       // rounding error of t + dt (FastTwoSum, exact for t >= dt)
+    eb = __float_as_uint(t) >> 23;                                  // sign bit clear: t > 0
+    const bool normal = t >= dt && dt > 0.0f && eb > 30u && eb < eb_ceiling;
+    const float half_ulp = __uint_as_float((eb - 24u) << 23), c_cap = __uint_as_float((eb - 5u) << 23);   // U / 2, 2^18 U
+    return normal && fabsf(err) != half_ulp && c < c_cap;
+}
+
 __device__ __forceinline__ float lane_lattice(float base, float dt, uint32_t lane, float &next_base, float &closed_step) {
     // L_{lane} of the lattice starting at base, by `lane` successive additions (float addition is not associative: the values
     // must come from the recurrence); also returns L_64.
-    // Closed form for the common case.  While L stays in one binade every L_k is a multiple of the binade's ulp U, so
-    // fl(L_k + dt) = L_k + c with the SAME c = round(dt / U) U for every k -- unless dt / U sits exactly between two integers (a tie
-    // rounds to even, which depends on L_k).  Then L_k = base + k c exactly (k c and the sum are multiples of U below 2^24 U).  All
-    // conditions are wave-uniform; anything else (binade crossing inside the window, a tie, a tiny base) takes the recurrence.
+    // Closed form for the common case (lattice_closed_form, and no binade crossing inside the window).  All conditions are
+    // wave-uniform; anything else (binade crossing inside the window, a tie, a tiny base) takes the recurrence.
     {
-        const float first = base + dt;
-        const float c = first - base;                               // exact (Sterbenz-like: both multiples of U, |c| << base)
-        const float err = dt - c;                                   // rounding error of base + dt (FastTwoSum, exact for base >= dt)
+        float c;
+        uint32_t eb;
+        const bool closed = lattice_closed_form(base, dt, 255u, c, eb);
         const float last = base + 64.0f * c;
-        const uint32_t eb = __float_as_uint(base) >> 23, el = __float_as_uint(last) >> 23;     // sign bit clear: t > 0
-        const bool normal = base >= dt && dt > 0.0f && eb > 30u && eb < 255u;
-        const float half_ulp = __uint_as_float((eb - 24u) << 23), c_cap = __uint_as_float((eb - 5u) << 23);   // U / 2, 2^18 U
-        if (normal && eb == el && fabsf(err) != half_ulp && c < c_cap) {
+        if (closed && eb == (__float_as_uint(last) >> 23)) {
             next_base = last;
             closed_step = c;                                        // L_k = base + k c holds for k = 0 .. 64
             return base + (float)lane * c;
@@ -574,33 +596,13 @@ __global__ void __launch_bounds__(256) k_march_train_count_wave(const float *__r
         const int *meta = reinterpret_cast<const int *>(cull + kCullWords);
         const int bx0 = meta[0], by0 = meta[1], bz0 = meta[2];
         const int bnx = meta[3] - bx0 + 1, bny = meta[4] - by0 + 1, bnz = meta[5] - bz0 + 1;
-        const float len = sqrtf(m.dx * m.dx + m.dy * m.dy + m.dz * m.dz);
-        const float ds = (2.0f / kCullRes) / fmaxf(len, 1e-12f);
-        const float cw = 2.0f / kCullRes;
-        float s0 = t0, s1 = far;
-        bool may = !(bnx <= 0 || bny <= 0 || bnz <= 0);
-        if (may) {
-            const float lo[3] = {(float)bx0 * cw - 1.0f, (float)by0 * cw - 1.0f, (float)bz0 * cw - 1.0f};
-            const float hi[3] = {(float)(bx0 + bnx) * cw - 1.0f, (float)(by0 + bny) * cw - 1.0f, (float)(bz0 + bnz) * cw - 1.0f};
-            const float o[3] = {m.ox, m.oy, m.oz}, d[3] = {m.dx, m.dy, m.dz};
-            #pragma unroll
-            for (int a = 0; a < 3; a++) {
-                if (d[a] != 0.0f) {
-                    const float r = 1.0f / d[a];
-                    const float ta = (lo[a] - o[a]) * r, tb = (hi[a] - o[a]) * r;
-                    s0 = fmaxf(s0, fminf(ta, tb) - ds);
-                    s1 = fminf(s1, fmaxf(ta, tb) + ds);
-                } else if (o[a] < lo[a] - cw || o[a] > hi[a] + cw) {
-                    may = false;
-                }
-            }
-            if (!(s0 <= s1)) may = false;
-        }
-        if (!may) {
+        const CullRange r = cull_scan_range(m.ox, m.oy, m.oz, m.dx, m.dy, m.dz, t0, far, bx0, by0, bz0, bnx, bny, bnz);
+        const float ds = r.ds, s1 = r.s1;
+        if (!r.may) {
             go = false;
         } else {
             bool hit = false, ended = false;
-            float base = s0;
+            float base = r.s0;
             for (int round = 0; round < 2 && !ended; round++) {   // 96 scan positions: lanes 0..63, then 0..31
                 float nb, unused_step;
                 const float s = lane_lattice(base, ds, lane, nb, unused_step);
@@ -906,6 +908,21 @@ __global__ void __launch_bounds__(256) k_composite_train_fwd(const float *__rest
     image[(size_t)index * 3] = r; image[(size_t)index * 3 + 1] = g; image[(size_t)index * 3 + 2] = b;
 }
 
+// One step of the inference compositing recurrence (raymarching.cu:862-887) on a ray's accumulators: the sample of density sigma, step
+// dt and colour c, whose parameter lies dt_after behind the previous one.  Returns T, the transmittance IN FRONT of the sample, for the
+// caller's stop test; the two early exits (dt == 0 before the step, T < T_thresh after it) stay with the callers.
+struct CompositeAcc { float t, weight_sum, d, r, g, b; };
+__device__ __forceinline__ float composite_step(CompositeAcc &a, float sigma, float dt, float dt_after, float cr, float cg, float cb) {
+    const float alpha = 1.0f - sdn_exp_cr(-sigma * dt);
+    const float T = 1 - a.weight_sum;
+    const float weight = alpha * T;
+    a.weight_sum += weight;
+    a.t += dt_after;
+    a.d += weight * a.t;
+    a.r += weight * cr; a.g += weight * cg; a.b += weight * cb;
+    return T;
+}
+
 // The INFERENCE compositing arithmetic (kernel_composite_rays, raymarching.cu:819-905: transmittance as 1 - weights_sum, the stop
 // test on the transmittance IN FRONT of a sample, t running from the ray's near bound) over ALL samples of a ray at once, in the
 // (offset, count) layout of march_rays_train.  With a ray's samples listed up front the iteration loop of the inference branch
@@ -919,25 +936,18 @@ __global__ void __launch_bounds__(256) k_composite_whole_rays(const float *__res
     const uint32_t n = threadIdx.x + blockIdx.x * blockDim.x;
     if (n >= N) return;
     const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
-    float weight_sum = 0, d = 0, r = 0, g = 0, b = 0;
+    CompositeAcc a = {0, 0, 0, 0, 0, 0};
     if (num_steps != 0 && offset + num_steps <= M) {
         const float *s = sigmas + offset, *c = rgbs + (size_t)offset * 3, *dl = deltas + (size_t)offset * 2;
-        float t = nears[index];
+        a.t = nears[index];
         for (uint32_t step = 0; step < num_steps; step++) {
             if (dl[0] == 0) break;
-            const float alpha = 1.0f - sdn_exp_cr(-s[0] * dl[0]);
-            const float T = 1 - weight_sum;
-            const float weight = alpha * T;
-            weight_sum += weight;
-            t += dl[1];
-            d += weight * t;
-            r += weight * c[0]; g += weight * c[1]; b += weight * c[2];
-            if (T < T_thresh) break;
+            if (composite_step(a, s[0], dl[0], dl[1], c[0], c[1], c[2]) < T_thresh) break;
             s++; c += 3; dl += 2;
         }
     }
-    weights_sum[index] = weight_sum; depth[index] = d;
-    image[(size_t)index * 3] = r; image[(size_t)index * 3 + 1] = g; image[(size_t)index * 3 + 2] = b;
+    weights_sum[index] = a.weight_sum; depth[index] = a.d;
+    image[(size_t)index * 3] = a.r; image[(size_t)index * 3 + 1] = a.g; image[(size_t)index * 3 + 2] = a.b;
 }
 
 // raymarching.cu:602-682
@@ -987,10 +997,7 @@ __global__ void __launch_bounds__(256) k_composite_train_bwd(const float *__rest
 // marked cell -- is a property of the ray, not of where the scan started, so the device loop computes it on a ray's first
 // march and later iterations only compare (kTendUnset: not computed yet; kTendDead: the ray cannot produce a sample).
 constexpr float kTendUnset = -2.0f, kTendDead = -1.0f;
-// device loop: the cache's base pointer travels in the loop record (state[13], state[14]; 0 = no cache)
-__device__ __forceinline__ float *state_tend(const int32_t *__restrict__ state) {
-    return reinterpret_cast<float *>(((unsigned long long)(uint32_t)state[14] << 32) | (uint32_t)state[13]);
-}
+// device loop: the cache's base pointer travels in the loop record (sdn_loop_tend; nullptr = no cache)
 template <bool FAST>
 __device__ __forceinline__ uint32_t march_ray(MarcherT<FAST> &m, const OccCache &oc, float t, float far, uint32_t n_step, float *px, float *pd,
                                               float *pl, float *tend = nullptr, uint8_t *psf = nullptr, uint32_t frame = 0,
@@ -1050,9 +1057,56 @@ __device__ __forceinline__ uint32_t block_min_256(uint32_t v, uint32_t *lds4) {
     __syncthreads();
     return min(min(lds4[0], lds4[1]), min(lds4[2], lds4[3]));
 }
+// Number of threads of the 256-thread workgroup whose flag is set, in every thread.  Contains a barrier; lds4 must not be in use.
+__device__ __forceinline__ uint32_t block_count_256(bool flag, uint32_t *lds4) {
+    const unsigned long long m = __ballot(flag);
+    if ((threadIdx.x & 63u) == 0) lds4[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    return lds4[0] + lds4[1] + lds4[2] + lds4[3];
+}
+__device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t *lds4) {
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    __syncthreads();  // protects lds4 against the previous use
+    if ((threadIdx.x & 63u) == 0) lds4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return lds4[0] + lds4[1] + lds4[2] + lds4[3];
+}
 constexpr uint32_t kNoFrame = 0xFFFFFFFFu;
 __device__ __forceinline__ const uint8_t *frame_grid_uniform(const FrameSel &fs, uint32_t frame_uniform) {
     return fs.grid[__builtin_amdgcn_readfirstlane(frame_uniform)];
+}
+
+// A marching lane's ray: origin, direction and far bound.  The marching kernels fetch them BEFORE their workgroup's barriers and LDS
+// fill, so that the loads land under those instead of behind them.
+struct RayIn { float o[3] = {0, 0, 0}, d[3] = {0, 0, 1}, far = 0; };
+__device__ __forceinline__ void ray_in_fetch(RayIn &r, int index, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                             const float *__restrict__ fars) {
+    r.o[0] = rays_o[(size_t)index * 3]; r.o[1] = rays_o[(size_t)index * 3 + 1]; r.o[2] = rays_o[(size_t)index * 3 + 2];
+    r.d[0] = rays_d[(size_t)index * 3]; r.d[1] = rays_d[(size_t)index * 3 + 1]; r.d[2] = rays_d[(size_t)index * 3 + 2];
+    r.far = fars[index];
+}
+
+// The frame rounds of a marching workgroup (see above): one round per frame present among its marching lanes -- exactly one without a
+// frame group -- in which the workgroup loads that frame's LDS occupancy caches and the lanes of that frame call
+// march(oc, grid_f, frame, grouped).  Contains barriers: every thread of the workgroup must call it (marches: this lane has a ray to
+// march, index: its ray).  s_cull4 / s_fine / s_min4: the kernel's LDS for the caches and the frame minimum.
+template <bool FAST, typename March>
+__device__ __forceinline__ void frame_rounds(const FrameSel &fs, bool marches, int index, const uint8_t *__restrict__ grid,
+                                             const uint32_t *__restrict__ cull, uint4 *s_cull4, unsigned long long *s_fine, uint32_t *s_min4,
+                                             March march) {
+    const bool grouped = fs.n_frames > 1;  // kernel-uniform
+    const uint32_t frame = (grouped && marches) ? (uint32_t)index / fs.rays_per_frame : (grouped ? kNoFrame : 0u);
+    uint32_t fcur = grouped ? block_min_256(frame, s_min4) : 0u;
+    while (fcur != kNoFrame) {
+        const uint8_t *grid_f = grouped ? frame_grid_uniform(fs, fcur) : grid;   // (fcur is workgroup-uniform)
+        const uint32_t *cull_f = (grouped && cull) ? cull + (size_t)fcur * fs.cull_stride : cull;
+        OccCache oc;
+        occ_cache_load<FAST>(cull_f, grid_f, s_cull4, s_fine, oc);
+        if (marches && frame == fcur) march(oc, grid_f, frame, grouped);
+        if (!grouped) break;
+        fcur = block_min_256((frame != kNoFrame && frame > fcur) ? frame : kNoFrame, s_min4);   // (the barriers inside also fence the LDS caches)
+    }
 }
 
 // Appends the slots n*n_step .. +step of every lane to the live list: one atomicAdd per wave, prefix by wave shuffles.
@@ -1082,9 +1136,8 @@ __device__ __forceinline__ void live_append(uint32_t step, uint32_t n, uint32_t 
 __device__ __forceinline__ bool composite_ray(int index, uint32_t n_step, float T_thresh, const float *s, const float *c, const float *dl,
                                               float *__restrict__ rays_t, float *__restrict__ weights_sum, float *__restrict__ depth,
                                               float *__restrict__ image, float *t_out = nullptr) {
-    float t = rays_t[index];
-    float weight_sum = weights_sum[index], d = depth[index];
-    float r = image[(size_t)index * 3], g = image[(size_t)index * 3 + 1], b = image[(size_t)index * 3 + 2];
+    CompositeAcc a = {rays_t[index], weights_sum[index], depth[index], image[(size_t)index * 3], image[(size_t)index * 3 + 1],
+                      image[(size_t)index * 3 + 2]};
     uint32_t step = 0;
     if (n_step == 8) {
         float sv[8], cv[24], dv[16];
@@ -1099,35 +1152,22 @@ __device__ __forceinline__ bool composite_ray(int index, uint32_t n_step, float 
         for (int k = 0; k < 8; k++) {
             if (open && dv[2 * k] == 0) open = false;
             if (open) {
-                const float alpha = 1.0f - sdn_exp_cr(-sv[k] * dv[2 * k]);
-                const float T = 1 - weight_sum;
-                const float weight = alpha * T;
-                weight_sum += weight;
-                t += dv[2 * k + 1];
-                d += weight * t;
-                r += weight * cv[3 * k]; g += weight * cv[3 * k + 1]; b += weight * cv[3 * k + 2];
-                if (T < T_thresh) open = false; else step++;
+                if (composite_step(a, sv[k], dv[2 * k], dv[2 * k + 1], cv[3 * k], cv[3 * k + 1], cv[3 * k + 2]) < T_thresh) open = false;
+                else step++;
             }
         }
     } else {
         while (step < n_step) {
             if (dl[0] == 0) break;
-            const float alpha = 1.0f - sdn_exp_cr(-s[0] * dl[0]);
-            const float T = 1 - weight_sum;
-            const float weight = alpha * T;
-            weight_sum += weight;
-            t += dl[1];
-            d += weight * t;
-            r += weight * c[0]; g += weight * c[1]; b += weight * c[2];
-            if (T < T_thresh) break;
+            if (composite_step(a, s[0], dl[0], dl[1], c[0], c[1], c[2]) < T_thresh) break;
             s++; c += 3; dl += 2; step++;
         }
     }
     const bool survives = !(step < n_step);
-    if (survives) rays_t[index] = t;
-    if (t_out) *t_out = t;
-    weights_sum[index] = weight_sum; depth[index] = d;
-    image[(size_t)index * 3] = r; image[(size_t)index * 3 + 1] = g; image[(size_t)index * 3 + 2] = b;
+    if (survives) rays_t[index] = a.t;
+    if (t_out) *t_out = a.t;
+    weights_sum[index] = a.weight_sum; depth[index] = a.d;
+    image[(size_t)index * 3] = a.r; image[(size_t)index * 3 + 1] = a.g; image[(size_t)index * 3 + 2] = a.b;
     return survives;
 }
 
@@ -1147,15 +1187,16 @@ __global__ void __launch_bounds__(256) k_march_rays(uint32_t n_alive, uint32_t n
                                                     const uint32_t *__restrict__ cull, uint32_t *__restrict__ live_idx,
                                                     uint32_t *__restrict__ live_count, const int32_t *__restrict__ state,
                                                     const int32_t *__restrict__ rays_alive_b, FrameSel fs, const float *__restrict__ jump) {
-    if (state) {  // device-driven loop: sizes, ping-pong side and the iteration's live counter come from the loop state
-        n_alive = (uint32_t)state[0];
-        n_step = (uint32_t)state[1];
+    const SdnLoopRecord *rec = sdn_loop(state);
+    if (rec) {  // device-driven loop: sizes, ping-pong side and the iteration's live counter come from the loop record
+        n_alive = (uint32_t)rec->n_alive;
+        n_step = (uint32_t)rec->n_step;
         if (n_alive == 0) return;
-        if (state[4]) rays_alive = rays_alive_b;
-        live_count += state[3];
+        if (rec->side) rays_alive = rays_alive_b;
+        live_count += rec->iteration;
         const uint32_t m0 = n_alive * n_step;
         M_pad = m0 + (128u - m0 % 128u);
-        if (!(state[15] && state[3] == 0)) jump = nullptr;   // the per-ray jump targets of k_cull_start hold for the first march only
+        if (!(rec->culled_start && rec->iteration == 0)) jump = nullptr;   // the per-ray jump targets of k_cull_start hold for the first march only
         if (blockIdx.x * 256u >= n_alive + 128u) return;   // workgroup-uniform: beyond the list and its alignment tail (the host sizes the grid by a bound)
     }
     __shared__ uint4 s_cull4[FAST ? 256 : 1];  // 32^3 bits = 4 KiB
@@ -1163,39 +1204,29 @@ __global__ void __launch_bounds__(256) k_march_rays(uint32_t n_alive, uint32_t n
     __shared__ uint32_t s_min4[4];
     const uint32_t n = threadIdx.x + blockIdx.x * blockDim.x;
     const int index = n < n_alive ? rays_alive[n] : -1;
-    const bool grouped = fs.n_frames > 1;  // kernel-uniform
-    const uint32_t frame = (grouped && index >= 0) ? (uint32_t)index / fs.rays_per_frame : (grouped ? kNoFrame : 0u);
     uint32_t step = 0;
     // the ray's inputs are fetched NOW: they land under the workgroup's barriers and its LDS fill instead of behind them
-    float ro[3] = {0, 0, 0}, rdv[3] = {0, 0, 1}, t_ray = 0, far_ray = 0, t_jump = 0, noise = 0;
+    RayIn ray;
+    float t_ray = 0, t_jump = 0, noise = 0;
     if (index >= 0) {
-        ro[0] = rays_o[(size_t)index * 3]; ro[1] = rays_o[(size_t)index * 3 + 1]; ro[2] = rays_o[(size_t)index * 3 + 2];
-        rdv[0] = rays_d[(size_t)index * 3]; rdv[1] = rays_d[(size_t)index * 3 + 1]; rdv[2] = rays_d[(size_t)index * 3 + 2];
-        t_ray = rays_t[index]; far_ray = fars[index];
+        ray_in_fetch(ray, index, rays_o, rays_d, fars);
+        t_ray = rays_t[index];
         if (jump) t_jump = jump[index];
         if (noises) noise = noises[n];
     }
-    uint32_t fcur = grouped ? block_min_256(frame, s_min4) : 0u;
-    while (fcur != kNoFrame) {   // one round per frame present in this workgroup (exactly one without a frame group)
-        const uint8_t *grid_f = grouped ? frame_grid_uniform(fs, fcur) : grid;
-        const uint32_t *cull_f = (grouped && cull) ? cull + (size_t)fcur * fs.cull_stride : cull;
-        OccCache oc;
-        occ_cache_load<FAST>(cull_f, grid_f, s_cull4, s_fine, oc);
-        if (index >= 0 && frame == fcur) {
-            MarcherT<FAST> m;
-            m.init(ro, rdv, bound, dt_gamma, max_steps, C, H, grid_f);
-            float t = t_ray;
-            t += m.step_size(t) * noise;
-            float *tend = state ? state_tend(state) : nullptr;
-            if (tend) tend += index;
-            const float t_walk = jump ? t_jump : t;   // (== t where k_cull_start certified no jump)
-            step = march_ray<FAST>(m, oc, t_walk, far_ray, n_step, xyzs + (size_t)n * n_step * 3, dirs + (size_t)n * n_step * 3,
-                                   deltas + (size_t)n * n_step * 2, tend, grouped ? fs.slot_frame + (size_t)n * n_step : nullptr, frame,
-                                   jump ? &t : nullptr);
-        }
-        if (!grouped) break;
-        fcur = block_min_256((frame != kNoFrame && frame > fcur) ? frame : kNoFrame, s_min4);   // (the barriers inside also fence the LDS caches)
-    }
+    frame_rounds<FAST>(fs, index >= 0, index, grid, cull, s_cull4, s_fine, s_min4,
+                       [&](const OccCache &oc, const uint8_t *grid_f, uint32_t frame, bool grouped) __attribute__((always_inline)) {
+        MarcherT<FAST> m;
+        m.init(ray.o, ray.d, bound, dt_gamma, max_steps, C, H, grid_f);
+        float t = t_ray;
+        t += m.step_size(t) * noise;
+        float *tend = rec ? sdn_loop_tend(*rec) : nullptr;
+        if (tend) tend += index;
+        const float t_walk = jump ? t_jump : t;   // (== t where k_cull_start certified no jump)
+        step = march_ray<FAST>(m, oc, t_walk, ray.far, n_step, xyzs + (size_t)n * n_step * 3, dirs + (size_t)n * n_step * 3,
+                               deltas + (size_t)n * n_step * 2, tend, grouped ? fs.slot_frame + (size_t)n * n_step : nullptr, frame,
+                               jump ? &t : nullptr);
+    });
     if (n >= n_alive) {
         const uint32_t slot = n_alive * n_step + (n - n_alive);  // spare lanes of the last blocks clear the alignment tail
         if (slot < M_pad) {
@@ -1207,12 +1238,6 @@ __global__ void __launch_bounds__(256) k_march_rays(uint32_t n_alive, uint32_t n
     if (live_idx) live_append(step, n, n_step, live_idx, live_count);  // kernel-uniform condition
 }
 
-// Length of the alive list the loop kernels walk: the frozen list of the steady mode (state[8], dead entries = -1 included) when one
-// exists -- the compositing + compaction pass then RE-compacts it (render.hip, FrameRun::enqueue) -- else the compacted list (state[0]).
-__device__ __forceinline__ uint32_t loop_list_len(const int32_t *__restrict__ state) {
-    return state[8] ? (uint32_t)state[8] : (uint32_t)state[0];
-}
-
 // raymarching.cu:819-905
 __global__ void __launch_bounds__(256) k_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *__restrict__ rays_alive,
                                                         float *__restrict__ rays_t, const float *__restrict__ sigmas,
@@ -1221,9 +1246,10 @@ __global__ void __launch_bounds__(256) k_composite_rays(uint32_t n_alive, uint32
                                                         const int32_t *__restrict__ state, int32_t *__restrict__ rays_alive_b,
                                                         uint32_t *__restrict__ block_totals) {
     if (state) {
-        n_alive = loop_list_len(state);
-        n_step = (uint32_t)state[1];
-        if (state[4]) rays_alive = rays_alive_b;
+        const SdnLoopRecord &rec = *sdn_loop(state);
+        n_alive = sdn_loop_list_len(rec);
+        n_step = (uint32_t)rec.n_step;
+        if (rec.side) rays_alive = rays_alive_b;
     }
     const uint32_t n = threadIdx.x + blockIdx.x * blockDim.x;
     bool survives = false;
@@ -1237,10 +1263,8 @@ __global__ void __launch_bounds__(256) k_composite_rays(uint32_t n_alive, uint32
     }
     if (block_totals) {  // kernel-uniform: survivor count of this 256-ray block, for the fused compaction of the device loop
         __shared__ uint32_t s_cnt[4];
-        const unsigned long long m = __ballot(survives);
-        if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-        __syncthreads();
-        if (threadIdx.x == 0) block_totals[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        const uint32_t c = block_count_256(survives, s_cnt);
+        if (threadIdx.x == 0) block_totals[blockIdx.x] = c;
     }
 }
 
@@ -1251,8 +1275,9 @@ __global__ void __launch_bounds__(256) k_composite_rays(uint32_t n_alive, uint32
 __global__ void __launch_bounds__(kScanBlock) k_compact_count(const int32_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ block_totals,
                                                               const int32_t *__restrict__ state, const int32_t *__restrict__ in_b) {
     if (state) {
-        n = loop_list_len(state);
-        if (state[4]) in = in_b;
+        const SdnLoopRecord &rec = *sdn_loop(state);
+        n = sdn_loop_list_len(rec);
+        if (rec.side) in = in_b;
         if (blockIdx.x * kScanBlock >= n) return;  // workgroup-uniform
     }
     __shared__ uint32_t lds[16];
@@ -1268,6 +1293,27 @@ __global__ void __launch_bounds__(kScanBlock) k_compact_count(const int32_t *__r
     }
 }
 
+// Stable scatter of the entries v >= 0 of a workgroup of WAVES waves (one entry per thread, in thread order) to out[prev ...]: rank by
+// wave ballot, per-wave counts through LDS.  Returns the workgroup's number of kept entries.  Contains barriers.
+template <uint32_t WAVES>
+__device__ __forceinline__ uint32_t ranked_scatter(int32_t v, uint32_t prev, int32_t *__restrict__ out, uint32_t *wave_counts /*[WAVES]*/) {
+    const bool keep = v >= 0;
+    const unsigned long long mask = __ballot(keep);
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    const uint32_t below = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    __syncthreads();  // protects wave_counts against the previous use
+    if (lane == 0) wave_counts[wid] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t carry = 0, total = 0;
+    for (uint32_t w = 0; w < WAVES; w++) {
+        const uint32_t c = wave_counts[w];
+        if (w < wid) carry += c;
+        total += c;
+    }
+    if (keep) out[prev + carry + below] = v;
+    return total;
+}
+
 __global__ void __launch_bounds__(kScanBlock) k_compact_scatter(const int32_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_totals,
                                                                 int32_t *__restrict__ out, int32_t *__restrict__ n_out,
                                                                 const int32_t *__restrict__ state, const int32_t *__restrict__ in_b,
@@ -1276,8 +1322,9 @@ __global__ void __launch_bounds__(kScanBlock) k_compact_scatter(const int32_t *_
     // per-256-ray survivor counts k_composite_rays wrote (the device loop skips the count launch)
     uint32_t last_block = gridDim.x - 1;
     if (state) {
-        n = loop_list_len(state);
-        if (state[4]) { in = in_b; out = out_b; }
+        const SdnLoopRecord &rec = *sdn_loop(state);
+        n = sdn_loop_list_len(rec);
+        if (rec.side) { in = in_b; out = out_b; }
         if (n == 0) {
             if (blockIdx.x == 0 && threadIdx.x == 0) n_out[0] = 0;
             return;
@@ -1286,35 +1333,19 @@ __global__ void __launch_bounds__(kScanBlock) k_compact_scatter(const int32_t *_
         if (blockIdx.x > last_block) return;  // workgroup-uniform
     }
     __shared__ uint32_t lds[16];
-    __shared__ uint32_t s_prev;
     uint32_t part = 0;
     for (uint32_t b = threadIdx.x; b < blockIdx.x * totals_per_block; b += kScanBlock) part += block_totals[b];
-    uint32_t prev_total;
-    block_inclusive_scan(part, lds, prev_total);
-    if (threadIdx.x == 0) s_prev = prev_total;
-    __syncthreads();
+    uint32_t prev;   // survivors of the blocks before this one (the scan hands the block's total to every thread)
+    block_inclusive_scan(part, lds, prev);
     const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
-    const int32_t v = i < n ? in[i] : -1;
-    const bool keep = v >= 0;
-    const unsigned long long mask = __ballot(keep);
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    const uint32_t below = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    if (lane == 0) lds[wid] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    uint32_t carry = 0, total = 0;
-    for (uint32_t w = 0; w < (kScanBlock >> 6); w++) {
-        const uint32_t c = lds[w];
-        if (w < wid) carry += c;
-        total += c;
-    }
-    if (keep) out[s_prev + carry + below] = v;
-    if (blockIdx.x == last_block && threadIdx.x == 0) n_out[0] = (int32_t)(s_prev + total);
+    const uint32_t total = ranked_scatter<kScanBlock / 64>(i < n ? in[i] : -1, prev, out, lds);
+    if (blockIdx.x == last_block && threadIdx.x == 0) n_out[0] = (int32_t)(prev + total);
 }
 
 
 // ---------------------------------------------------------------------------
 // device-driven inference loop (dnerf/renderer.py:340-381 without a host round trip per iteration)
-// state: [0] n_alive  [1] n_step  [2] steps done  [3] iteration  [4] ping-pong side  [5] N  [6] max_steps  [7] -
+// The loop record `state` is an SdnLoopRecord (include/sdn_hip.h documents every word); kernels view it through sdn_loop().
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_loop_init(uint32_t N, uint32_t max_steps, const float *__restrict__ nears, int32_t *__restrict__ alive_a,
                                                    float *__restrict__ rays_t, float *__restrict__ weights_sum, float *__restrict__ depth,
@@ -1331,15 +1362,17 @@ __global__ void __launch_bounds__(256) k_loop_init(uint32_t N, uint32_t max_step
     }
     if (n < n_counters) live_counts[n] = 0;
     if (n == 0) {
-        state[0] = (int32_t)N; state[1] = 1; state[2] = 0; state[3] = 0; state[4] = 0;
-        state[5] = (int32_t)N; state[6] = (int32_t)max_steps; state[7] = 0;
-        for (int k = 8; k < 16; k++) state[k] = 0;  // [8] frozen list length of the steady mode, [9] survivor accumulator
-        state[10] = (int32_t)(uint32_t)mailbox;      // [10],[11] host mailbox (device-visible pointer, 0 = none), [12] frame tag
-        state[11] = (int32_t)(uint32_t)(mailbox >> 32);
-        state[12] = (int32_t)frame_tag;
-        const unsigned long long tp = (unsigned long long)(uintptr_t)rays_tend;   // [13],[14] per-ray t_end cache (0 = none)
-        state[13] = (int32_t)(uint32_t)tp;
-        state[14] = (int32_t)(uint32_t)(tp >> 32);
+        SdnLoopRecord &rec = *sdn_loop(state);
+        rec.n_alive = (int32_t)N; rec.n_step = 1; rec.steps_done = 0; rec.iteration = 0; rec.side = 0;
+        rec.N = (int32_t)N; rec.max_steps = (int32_t)max_steps; rec.advance_calls = 0;
+        rec.frozen_len = 0; rec.survivors = 0;
+        rec.mailbox_lo = (int32_t)(uint32_t)mailbox;
+        rec.mailbox_hi = (int32_t)(uint32_t)(mailbox >> 32);
+        rec.frame_tag = (int32_t)frame_tag;
+        const unsigned long long tp = (unsigned long long)(uintptr_t)rays_tend;
+        rec.tend_lo = (int32_t)(uint32_t)tp;
+        rec.tend_hi = (int32_t)(uint32_t)(tp >> 32);
+        rec.culled_start = 0;
     }
 }
 
@@ -1348,29 +1381,71 @@ __global__ void __launch_bounds__(256) k_loop_init(uint32_t N, uint32_t max_step
 // (4 deep, immutable once written: the host may copy it out while the next iteration runs) and, when the frame driver
 // registered a mailbox in coherent host memory, as ONE 64-bit system-scope store {tag : n_alive} the host polls for --
 // no event, no copy, no stream wait on the critical path.  tag = frame_tag << 16 | (call + 1).
-__device__ __forceinline__ void publish_snapshot(int32_t *__restrict__ state, int32_t *__restrict__ snap, int32_t call) {
-    snap[(call & 3) * 2] = state[0];
+__device__ __forceinline__ void publish_snapshot(const SdnLoopRecord &rec, int32_t *__restrict__ snap, int32_t call) {
+    snap[(call & 3) * 2] = rec.n_alive;
     snap[(call & 3) * 2 + 1] = call + 1;
-    const unsigned long long mb = ((unsigned long long)(uint32_t)state[11] << 32) | (uint32_t)state[10];
+    unsigned long long *mb = sdn_loop_mailbox(rec);
     if (mb) {
-        const unsigned long long tag = ((uint32_t)state[12] << 16) | (uint32_t)(call + 1);
-        __hip_atomic_store(reinterpret_cast<unsigned long long *>(mb) + (call & 3), (tag << 32) | (uint32_t)state[0], __ATOMIC_RELEASE,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
+        const unsigned long long tag = ((uint32_t)rec.frame_tag << 16) | (uint32_t)(call + 1);
+        __hip_atomic_store(mb + (call & 3), (tag << 32) | (uint32_t)rec.n_alive, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+// Advances the loop record past the iteration that just ran; one thread, after every reader of the record in the launch is done.
+// Logs the iteration's {n_alive, n_step} in the trace (only iterations that did work), adds its steps, applies `while step < max_steps`
+// and sets the survivors n_new as the next iteration's n_alive; freeze: the steady mode starts with the list as it now stands as
+// its frozen list; then publishes the snapshot.
+// RECOMPACTED: the survivors were compacted to the other side -- the side flips and n_step = max(min(N // n_alive, 8), 1) is set
+// (false: the steady mode, whose frozen list stays where it is and whose n_step stays 8: N / n_new >= 8 holds from its start on).
+// CULLED_LOGS_N: after a culled start the trace logs N for iteration 0, the reference's N-ray iteration (SdnLoopRecord::culled_start).
+template <bool RECOMPACTED, bool CULLED_LOGS_N>
+__device__ __forceinline__ void advance_record(SdnLoopRecord &rec, int32_t *__restrict__ trace, int32_t *__restrict__ snap, int32_t n_new,
+                                               int freeze) {
+    const int32_t it = rec.iteration;
+    const int32_t call = rec.advance_calls;   // no-op iterations included
+    rec.advance_calls = call + 1;
+    if (rec.n_alive > 0) {
+        trace[2 * it] = (CULLED_LOGS_N && it == 0 && rec.culled_start) ? rec.N : rec.n_alive;
+        trace[2 * it + 1] = rec.n_step;
+        rec.steps_done += rec.n_step;
+        rec.iteration = it + 1;
+        if (RECOMPACTED) rec.side ^= 1;
+        if (rec.steps_done >= rec.max_steps) n_new = 0;
+        rec.n_alive = n_new;
+        if (RECOMPACTED && n_new > 0) {
+            const int32_t ns = rec.N / n_new;
+            rec.n_step = ns > 8 ? 8 : (ns < 1 ? 1 : ns);
+        }
+    }
+    if (freeze) { rec.frozen_len = rec.n_alive; rec.survivors = 0; }   // (k_steady_begin folded in)
+    publish_snapshot(rec, snap, call);
+}
+
+// Last-workgroup election of a launch: every workgroup takes a ticket after its last access to what the last one will touch (the
+// caller puts a barrier between those accesses and this call); true in every thread of the workgroup that drew the last ticket,
+// which then sees the other workgroups' writes.  The ticket is reset for the next launch HERE, before the caller's last-workgroup work
+// (every other workgroup of the launch has drawn its ticket by then).  Must be called by the whole workgroup.
+__device__ __forceinline__ bool last_workgroup(int32_t *__restrict__ ticket) {
+    __shared__ int s_last;
+    if (threadIdx.x == 0) {
+        __threadfence();
+        s_last = (atomicAdd(ticket, 1) == (int)gridDim.x - 1);
+    }
+    __syncthreads();
+    if (!s_last) return false;
+    __threadfence();
+    if (threadIdx.x == 0) *ticket = 0;
+    return true;
 }
 
 // The largest lattice point <= target of the lattice t, fl(t + dt), ... (t itself if none): closed form inside a binade, one
 // recurrence step across a binade boundary.  Gives up (returns the point reached) where the closed form does not hold.
 __device__ __forceinline__ float lattice_floor(float t, float dt, float target) {
     for (int hop = 0; hop < 4; hop++) {
-        const float first = t + dt;
-        if (!(first <= target)) break;
-        const float c = first - t;
-        const float err = dt - c;
-        const uint32_t eb = __float_as_uint(t) >> 23;
-        const bool normal = t >= dt && dt > 0.0f && eb > 30u && eb < 254u;
-        const float half_ulp = __uint_as_float((eb - 24u) << 23), c_cap = __uint_as_float((eb - 5u) << 23);
-        if (!(normal && fabsf(err) != half_ulp && c < c_cap)) break;
+        if (!(t + dt <= target)) break;
+        float c;
+        uint32_t eb;
+        if (!lattice_closed_form(t, dt, 254u, c, eb)) break;
         const float top = __uint_as_float(((eb + 1u) << 23) - 1u);       // the largest float of t's binade
         const float lim = fminf(target, top);
         float k = floorf((lim - t) / c);
@@ -1390,7 +1465,7 @@ __device__ __forceinline__ float lattice_floor(float t, float dt, float target) 
 // for all N rays -- filling the t_end cache -- and iteration 0 then works on the compacted list of the rays that MAY produce a sample:
 // dense waves instead of N-ray launches in which most lanes stop at the cull test.  Nothing observable changes: a ray the test rejects
 // produces no sample and dies in iteration 0 either way, the survivors of iteration 0 -- and therefore every later iteration, every
-// sample and every count -- are the same, and the trace logs N for iteration 0 (state[15], k_loop_advance / k_scatter_advance).
+// sample and every count -- are the same, and the trace logs N for iteration 0 (SdnLoopRecord::culled_start, advance_record).
 // The certified jump.  With a constant step every parameter the marcher visits is a point of the lattice L_0 = t, L_(k+1) = fl(L_k + dt);
 // the walk from t visits, of every voxel that holds lattice points, a first one, and leaves it for the first lattice point >= the
 // voxel's exit parameter.  Everything before `t_safe` (ray_may_hit) is >= 2 fine voxels away from any occupied voxel, so the walk emits
@@ -1406,11 +1481,9 @@ __device__ __forceinline__ float certified_jump(const MarcherT<true> &m, float t
     const float L = lattice_floor(t, dt, t_safe - 18.0f * dt);
     if (!(L > t)) return t;
     // closed form of the lattice around L (the conditions of lattice_floor, for the 14 steps either side that are looked at)
-    const float c = (L + dt) - L, err = dt - c;
-    const uint32_t eb = __float_as_uint(L) >> 23;
-    if (!(L >= dt && dt > 0.0f && eb > 30u && eb < 254u)) return t;
-    const float half_ulp = __uint_as_float((eb - 24u) << 23), c_cap = __uint_as_float((eb - 5u) << 23);
-    if (!(fabsf(err) != half_ulp && c < c_cap && c > 0.0f)) return t;
+    float c;
+    uint32_t eb;
+    if (!(lattice_closed_form(L, dt, 254u, c, eb) && c > 0.0f)) return t;
     if ((__float_as_uint(L - 14.0f * c) >> 23) != eb || (__float_as_uint(L + 14.0f * c) >> 23) != eb) return t;
     float x, y, z;
     int vx, vy, vz, nx, ny, nz;
@@ -1473,26 +1546,25 @@ __global__ void __launch_bounds__(256) k_cull_start(uint32_t N, const float *__r
     if (n < N) go = cull_start_ray(n, rays_o, rays_d, nears, fars, cull, fs, alive_a, rays_tend, bound, dt_gamma, max_steps, C, H, jump);
     // rays of this 256-ray block that go on: the compaction's scatter sums these (no separate count launch)
     __shared__ uint32_t s_cnt[4];
-    const unsigned long long m = __ballot(go);
-    if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) block_totals[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const uint32_t c = block_count_256(go, s_cnt);
+    if (threadIdx.x == 0) block_totals[blockIdx.x] = c;
 }
 
 // after the compaction of the culled start: the list is in alive_b (side 1), n_out[0] rays long
 __global__ void k_cull_advance(int32_t *__restrict__ state, const int32_t *__restrict__ n_out, int32_t *__restrict__ trace) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    SdnLoopRecord &rec = *sdn_loop(state);
     const int32_t n0 = n_out[0];
-    state[4] = 1;
-    state[15] = 1;            // iteration 0 runs on the culled list: the trace logs N for it
+    rec.side = 1;
+    rec.culled_start = 1;     // iteration 0 runs on the culled list: the trace logs N for it
     if (n0 > 0) {
-        state[0] = n0;
+        rec.n_alive = n0;
     } else {                  // no ray can produce a sample: the reference's iteration 0 (N rays, one step) finds nothing and the loop ends
-        trace[0] = state[5];
-        trace[1] = state[1];
-        state[2] += state[1];
-        state[3] = 1;
-        state[0] = 0;
+        trace[0] = rec.N;
+        trace[1] = rec.n_step;
+        rec.steps_done += rec.n_step;
+        rec.iteration = 1;
+        rec.n_alive = 0;
     }
 }
 
@@ -1501,34 +1573,7 @@ __global__ void k_cull_advance(int32_t *__restrict__ state, const int32_t *__res
 __global__ void k_loop_advance(int32_t *__restrict__ state, const int32_t *__restrict__ n_out, int32_t *__restrict__ trace,
                                int32_t *__restrict__ snap, int freeze) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int32_t it = state[3];
-    const int32_t call = state[7];  // number of advance calls so far (no-op iterations included)
-    state[7] = call + 1;
-    if (state[0] > 0) {  // log only iterations that did work: (n_alive, n_step)
-        trace[2 * it] = (it == 0 && state[15]) ? state[5] : state[0];   // culled start: iteration 0 is the reference's N-ray iteration
-        trace[2 * it + 1] = state[1];
-        state[2] += state[1];
-        state[3] = it + 1;
-        state[4] ^= 1;
-        int32_t n_new = n_out[0];
-        if (state[2] >= state[6]) n_new = 0;  // `while step < max_steps`
-        state[0] = n_new;
-        if (n_new > 0) {
-            int32_t ns = state[5] / n_new;  // n_step = max(min(N // n_alive, 8), 1)
-            state[1] = ns > 8 ? 8 : (ns < 1 ? 1 : ns);
-        }
-    }
-    if (freeze) { state[8] = state[0]; state[9] = 0; }   // k_steady_begin folded in: the compacted list is the steady mode's new frozen list
-    publish_snapshot(state, snap, call);
-}
-
-__device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t *lds4) {
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();  // protects lds4 against the previous use
-    if ((threadIdx.x & 63u) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return lds4[0] + lds4[1] + lds4[2] + lds4[3];
+    advance_record<true, true>(*sdn_loop(state), trace, snap, n_out[0], freeze);
 }
 
 // Stable compaction of the alive list (256-ray blocks, totals produced by k_composite_rays) fused with the loop advance:
@@ -1539,63 +1584,25 @@ __global__ void __launch_bounds__(256) k_scatter_advance(int32_t *__restrict__ a
                                                          int32_t *__restrict__ ticket, int32_t *__restrict__ trace, int32_t *__restrict__ snap,
                                                          int freeze) {
     __shared__ uint32_t lds4[4];
-    __shared__ int s_last;
-    const uint32_t n = loop_list_len(state);
-    const int32_t *in = state[4] ? alive_b : alive_a;
-    int32_t *out = state[4] ? alive_a : alive_b;
+    SdnLoopRecord &rec = *sdn_loop(state);
+    const uint32_t n = sdn_loop_list_len(rec);
+    const int32_t *in = rec.side ? alive_b : alive_a;
+    int32_t *out = rec.side ? alive_a : alive_b;
     const uint32_t nb = (n + 255u) / 256u;
     if (blockIdx.x < nb) {
         uint32_t part = 0;
         for (uint32_t b = threadIdx.x; b < blockIdx.x; b += 256) part += block_totals[b];
         const uint32_t prev = block_sum_256(part, lds4);
         const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-        const int32_t v = i < n ? in[i] : -1;
-        const bool keep = v >= 0;
-        const unsigned long long mask = __ballot(keep);
-        const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-        const uint32_t below = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        __syncthreads();
-        if (lane == 0) lds4[wid] = (uint32_t)__popcll(mask);
-        __syncthreads();
-        uint32_t carry = 0;
-        for (uint32_t w = 0; w < wid; w++) carry += lds4[w];
-        if (keep) out[prev + carry + below] = v;
+        ranked_scatter<4>(i < n ? in[i] : -1, prev, out, lds4);
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        s_last = (atomicAdd(ticket, 1) == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
+    if (!last_workgroup(ticket)) return;
     uint32_t part = 0;
     for (uint32_t b = threadIdx.x; b < nb; b += 256) part += block_totals[b];
     const uint32_t total = block_sum_256(part, lds4);
-    if (threadIdx.x == 0) {
-        *ticket = 0;
-        const int32_t it = state[3];
-        const int32_t call = state[7];
-        state[7] = call + 1;
-        if (state[0] > 0) {
-            trace[2 * it] = (it == 0 && state[15]) ? state[5] : state[0];
-            trace[2 * it + 1] = state[1];
-            state[2] += state[1];
-            state[3] = it + 1;
-            state[4] ^= 1;
-            int32_t n_new = (int32_t)total;
-            if (state[2] >= state[6]) n_new = 0;  // `while step < max_steps`
-            state[0] = n_new;
-            if (n_new > 0) {
-                const int32_t ns = state[5] / n_new;  // n_step = max(min(N // n_alive, 8), 1)
-                state[1] = ns > 8 ? 8 : (ns < 1 ? 1 : ns);
-            }
-        }
-        if (freeze) { state[8] = state[0]; state[9] = 0; }   // (k_steady_begin folded in)
-        publish_snapshot(state, snap, call);
-    }
+    if (threadIdx.x == 0) advance_record<true, true>(rec, trace, snap, (int32_t)total, freeze);
 }
-
 
 // ---------------------------------------------------------------------------
 // steady mode of the device loop: once n_alive <= N / 8 the schedule is n_step = 8 for good (n_alive only shrinks), so
@@ -1604,7 +1611,10 @@ __global__ void __launch_bounds__(256) k_scatter_advance(int32_t *__restrict__ a
 // Two launches per iteration (fused field, composite+march) instead of five.  Samples, schedule and counts are unchanged.
 // ---------------------------------------------------------------------------
 __global__ void k_steady_begin(int32_t *__restrict__ state) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { state[8] = state[0]; state[9] = 0; }
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    SdnLoopRecord &rec = *sdn_loop(state);
+    rec.frozen_len = rec.n_alive;
+    rec.survivors = 0;
 }
 
 template <bool FAST>
@@ -1622,11 +1632,11 @@ __global__ void __launch_bounds__(256) k_composite_march(float T_thresh, int32_t
     __shared__ uint4 s_cull4[FAST ? 256 : 1];
     __shared__ unsigned long long s_fine[FAST ? kFineCacheCells : 1];
     __shared__ uint32_t s_cnt[4], s_min4[4];
-    __shared__ int s_last;
-    const uint32_t n_alive = (uint32_t)state[0], n_step = (uint32_t)state[1], list_len = (uint32_t)state[8];
-    const int32_t it = state[3];
-    int32_t *__restrict__ alive = state[4] ? alive_b : alive_a;
-    const bool march_next = (uint32_t)state[2] + n_step < (uint32_t)state[6];  // `while step < max_steps` admits another iteration
+    SdnLoopRecord &rec = *sdn_loop(state);
+    const uint32_t n_alive = (uint32_t)rec.n_alive, n_step = (uint32_t)rec.n_step, list_len = (uint32_t)rec.frozen_len;
+    const int32_t it = rec.iteration;
+    int32_t *__restrict__ alive = rec.side ? alive_b : alive_a;
+    const bool march_next = (uint32_t)rec.steps_done + n_step < (uint32_t)rec.max_steps;  // `while step < max_steps` admits another iteration
     const uint32_t n = threadIdx.x + blockIdx.x * blockDim.x;
     bool survives = false;
     uint32_t emitted = 0;
@@ -1634,67 +1644,33 @@ __global__ void __launch_bounds__(256) k_composite_march(float T_thresh, int32_t
         const int index = n < list_len ? alive[n] : -1;
         // composite iteration `it` of this ray; survivors march iteration it + 1 below.  The marcher's inputs are fetched together with
         // the compositing's (they land under it, the barriers and the LDS fill), and the ray's new t travels in a register
-        float ro[3] = {0, 0, 0}, rdv[3] = {0, 0, 1}, far_ray = 0, t_new = 0;
+        RayIn ray;
+        float t_new = 0;
         if (index >= 0) {
-            if (march_next) {
-                ro[0] = rays_o[(size_t)index * 3]; ro[1] = rays_o[(size_t)index * 3 + 1]; ro[2] = rays_o[(size_t)index * 3 + 2];
-                rdv[0] = rays_d[(size_t)index * 3]; rdv[1] = rays_d[(size_t)index * 3 + 1]; rdv[2] = rays_d[(size_t)index * 3 + 2];
-                far_ray = fars[index];
-            }
+            if (march_next) ray_in_fetch(ray, index, rays_o, rays_d, fars);
             survives = composite_ray(index, n_step, T_thresh, sigmas + (size_t)n * n_step, rgbs + (size_t)n * n_step * 3,
                                      deltas + (size_t)n * n_step * 2, rays_t, weights_sum, depth, image, &t_new);
             if (!survives) alive[n] = -1;
         }
-        const bool marches = survives && march_next;
-        const bool grouped = fs.n_frames > 1;  // kernel-uniform
-        const uint32_t frame = (grouped && marches) ? (uint32_t)index / fs.rays_per_frame : (grouped ? kNoFrame : 0u);
-        uint32_t fcur = grouped ? block_min_256(frame, s_min4) : 0u;
-        while (fcur != kNoFrame) {   // one round per frame present among this workgroup's marching rays (see block_min_256)
-            const uint8_t *grid_f = grouped ? frame_grid_uniform(fs, fcur) : grid;
-            const uint32_t *cull_f = (grouped && cull) ? cull + (size_t)fcur * fs.cull_stride : cull;
-            OccCache oc;
-            occ_cache_load<FAST>(cull_f, grid_f, s_cull4, s_fine, oc);
-            if (marches && frame == fcur) {
-                float *px = xyzs + (size_t)n * n_step * 3, *pd = dirs + (size_t)n * n_step * 3, *pl = deltas + (size_t)n * n_step * 2;
-                MarcherT<FAST> m;
-                m.init(ro, rdv, bound, dt_gamma, max_steps, C, H, grid_f);
-                float *tend = state_tend(state);
-                if (tend) tend += index;
-                emitted = march_ray<FAST>(m, oc, t_new, far_ray, n_step, px, pd, pl, tend,
-                                          grouped ? fs.slot_frame + (size_t)n * n_step : nullptr, frame);
-            }
-            if (!grouped) break;
-            fcur = block_min_256((frame != kNoFrame && frame > fcur) ? frame : kNoFrame, s_min4);
-        }
+        frame_rounds<FAST>(fs, survives && march_next, index, grid, cull, s_cull4, s_fine, s_min4,
+                           [&](const OccCache &oc, const uint8_t *grid_f, uint32_t frame, bool grouped) __attribute__((always_inline)) {
+            float *px = xyzs + (size_t)n * n_step * 3, *pd = dirs + (size_t)n * n_step * 3, *pl = deltas + (size_t)n * n_step * 2;
+            MarcherT<FAST> m;
+            m.init(ray.o, ray.d, bound, dt_gamma, max_steps, C, H, grid_f);
+            float *tend = sdn_loop_tend(rec);
+            if (tend) tend += index;
+            emitted = march_ray<FAST>(m, oc, t_new, ray.far, n_step, px, pd, pl, tend, grouped ? fs.slot_frame + (size_t)n * n_step : nullptr,
+                                      frame);
+        });
         live_append(emitted, n, n_step, live_idx, live_counts + it + 1);
     }
     // survivors of this workgroup -> global accumulator; the last workgroup of the launch advances the loop record
-    const unsigned long long mask = __ballot(survives);
-    if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        if (c) atomicAdd(state + 9, (int32_t)c);
-        __threadfence();
-        s_last = (atomicAdd(ticket, 1) == (int)gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!s_last || threadIdx.x != 0) return;
-    __threadfence();
-    *ticket = 0;
-    const int32_t call = state[7];
-    state[7] = call + 1;
-    if (state[0] > 0) {
-        trace[2 * it] = state[0];
-        trace[2 * it + 1] = state[1];
-        state[2] += state[1];
-        state[3] = it + 1;
-        int32_t n_new = atomicAdd(state + 9, 0);
-        state[9] = 0;
-        if (state[2] >= state[6]) n_new = 0;
-        state[0] = n_new;  // n_step stays 8: N / n_new >= 8 holds from here on
-    }
-    publish_snapshot(state, snap, call);
+    const uint32_t c = block_count_256(survives, s_cnt);
+    if (threadIdx.x == 0 && c) atomicAdd(&rec.survivors, (int32_t)c);
+    if (!last_workgroup(ticket) || threadIdx.x != 0) return;
+    const int32_t n_new = atomicAdd(&rec.survivors, 0);
+    rec.survivors = 0;
+    advance_record<false, false>(rec, trace, snap, n_new, 0);
 }
 
 // image = image + (1 - weights_sum) * bg ; depth = clamp(depth - nears, 0) / (fars - nears)   (dnerf/renderer.py:378-379)
@@ -1728,16 +1704,14 @@ struct MarchRays {
 };
 int launch_k_march_rays(const MarchRays &m, hipStream_t st) {
     const dim3 g(sdn_div_up(m.threads, 256u)), b(256);
-    if (fast_config(m.bound, m.C, m.H)) {
-        const uint32_t *cull = (m.cull && m.H != 128) ? nullptr : m.cull;  // the cull grid is built for the 128^3 grid only
-        hipLaunchKernelGGL(k_march_rays<true>, g, b, 0, st, m.n_alive, m.n_step, m.rays_alive, m.rays_t, m.rays_o, m.rays_d, m.bound, m.dt_gamma,
-                           m.max_steps, m.C, m.H, m.grid, m.fars, m.xyzs, m.dirs, m.deltas, m.noises, m.M_pad, cull, m.live_idx, m.live_count, m.state,
-                           m.rays_alive_b, m.fs, cull ? m.jump : (const float *)nullptr);
-    } else {
-        hipLaunchKernelGGL(k_march_rays<false>, g, b, 0, st, m.n_alive, m.n_step, m.rays_alive, m.rays_t, m.rays_o, m.rays_d, m.bound, m.dt_gamma,
-                           m.max_steps, m.C, m.H, m.grid, m.fars, m.xyzs, m.dirs, m.deltas, m.noises, m.M_pad, (const uint32_t *)nullptr, m.live_idx,
-                           m.live_count, m.state, m.rays_alive_b, m.fs, (const float *)nullptr);
-    }
+    const bool fast = fast_config(m.bound, m.C, m.H);
+    const uint32_t *cull = (fast && m.H == 128) ? m.cull : nullptr;   // the cull grid is built for the 128^3 grid of the FAST configuration only
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, g, b, 0, st, m.n_alive, m.n_step, m.rays_alive, m.rays_t, m.rays_o, m.rays_d, m.bound, m.dt_gamma, m.max_steps, m.C,
+                           m.H, m.grid, m.fars, m.xyzs, m.dirs, m.deltas, m.noises, m.M_pad, cull, m.live_idx, m.live_count, m.state, m.rays_alive_b,
+                           m.fs, cull ? m.jump : (const float *)nullptr);
+    };
+    if (fast) launch(k_march_rays<true>); else launch(k_march_rays<false>);
     return sdn_launch_status();
 }
 
@@ -1821,17 +1795,14 @@ int loop_composite_march(const SdnRenderCtx &c, uint32_t bound_list, hipStream_t
     const dim3 g(sdn_div_up(bound_list, 256u)), b(256);
     const FrameSel fs = frame_sel(c);
     int32_t *snap = snap_ring(c);
-    if (fast_config(c.bound, c.C, c.H)) {
-        const uint32_t *cull = loop_cull(c);
-        if (cull && c.H != 128) cull = nullptr;
-        hipLaunchKernelGGL(k_composite_march<true>, g, b, 0, st, c.T_thresh, c.alive_a, c.alive_b, c.rays_t, c.rays_o, c.rays_d, c.bound, c.dt_gamma,
-                           c.max_steps, c.C, c.H, c.bitfield, c.fars, c.sigmas, c.rgbs, c.xyzs, c.dirs, c.deltas, c.weights_sum, c.depth, c.image, cull,
-                           c.live_idx, live_counters(c), c.state, c.n_out, c.trace, snap, fs);   // (n_out: the ticket counter)
-    } else {
-        hipLaunchKernelGGL(k_composite_march<false>, g, b, 0, st, c.T_thresh, c.alive_a, c.alive_b, c.rays_t, c.rays_o, c.rays_d, c.bound, c.dt_gamma,
-                           c.max_steps, c.C, c.H, c.bitfield, c.fars, c.sigmas, c.rgbs, c.xyzs, c.dirs, c.deltas, c.weights_sum, c.depth, c.image,
-                           (const uint32_t *)nullptr, c.live_idx, live_counters(c), c.state, c.n_out, c.trace, snap, fs);
-    }
+    const bool fast = fast_config(c.bound, c.C, c.H);
+    const uint32_t *cull = (fast && c.H == 128) ? loop_cull(c) : nullptr;   // the cull grid is built for the 128^3 grid of the FAST configuration only
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, g, b, 0, st, c.T_thresh, c.alive_a, c.alive_b, c.rays_t, c.rays_o, c.rays_d, c.bound, c.dt_gamma, c.max_steps, c.C, c.H,
+                           c.bitfield, c.fars, c.sigmas, c.rgbs, c.xyzs, c.dirs, c.deltas, c.weights_sum, c.depth, c.image, cull, c.live_idx,
+                           live_counters(c), c.state, c.n_out, c.trace, snap, fs);   // (n_out: the ticket counter)
+    };
+    if (fast) launch(k_composite_march<true>); else launch(k_composite_march<false>);
     return sdn_launch_status();
 }
 

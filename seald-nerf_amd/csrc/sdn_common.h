@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/sdn_hip.h"
@@ -11,6 +12,25 @@
 static inline int sdn_launch_status() {
     hipError_t e = hipGetLastError();
     return (int)e;
+}
+
+// The loop record (SdnLoopRecord, include/sdn_hip.h) behind the `int32_t *state` every loop kernel and field kernel is handed
+static_assert(sizeof(SdnLoopRecord) == 16 * sizeof(int32_t), "SdnRenderCtx::state is 16 ints");
+static_assert(offsetof(SdnLoopRecord, n_alive) == 0 && offsetof(SdnLoopRecord, iteration) == 12 && offsetof(SdnLoopRecord, N) == 20 &&
+              offsetof(SdnLoopRecord, max_steps) == 24 && offsetof(SdnLoopRecord, culled_start) == 60, "words the host and other files read");
+__host__ __device__ __forceinline__ SdnLoopRecord *sdn_loop(int32_t *state) { return reinterpret_cast<SdnLoopRecord *>(state); }
+__host__ __device__ __forceinline__ const SdnLoopRecord *sdn_loop(const int32_t *state) { return reinterpret_cast<const SdnLoopRecord *>(state); }
+// Length of the alive list the loop kernels walk: the frozen list of the steady mode (dead entries = -1 included) when one exists -- the
+// compositing + compaction pass then RE-compacts it (render.hip, FrameRun::enqueue) -- else the compacted list.
+__device__ __forceinline__ uint32_t sdn_loop_list_len(const SdnLoopRecord &rec) {
+    const int32_t frozen = rec.frozen_len;
+    return frozen ? (uint32_t)frozen : (uint32_t)rec.n_alive;
+}
+__device__ __forceinline__ float *sdn_loop_tend(const SdnLoopRecord &rec) {
+    return reinterpret_cast<float *>(((unsigned long long)(uint32_t)rec.tend_hi << 32) | (uint32_t)rec.tend_lo);
+}
+__device__ __forceinline__ unsigned long long *sdn_loop_mailbox(const SdnLoopRecord &rec) {
+    return reinterpret_cast<unsigned long long *>(((unsigned long long)(uint32_t)rec.mailbox_hi << 32) | (uint32_t)rec.mailbox_lo);
 }
 
 template <typename T>

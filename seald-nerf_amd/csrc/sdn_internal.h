@@ -49,7 +49,7 @@ int copy_cull(const void *const *prebuilt, uint32_t n_frames, uint32_t *cull_bit
 struct FieldCall {
     const float *xyzs = nullptr, *dirs = nullptr;
     const uint32_t *live_idx = nullptr, *live_count = nullptr;   // both or neither
-    const int32_t *state = nullptr;      // the loop record (the live count is then live_count[state[3]]), or nullptr
+    const int32_t *state = nullptr;      // the loop record (the live count is then live_count[SdnLoopRecord::iteration]), or nullptr
     uint32_t M = 0;
     const void *weights = nullptr;
     const float *bias0 = nullptr;        // n_frames rows

@@ -82,13 +82,13 @@ __global__ void __launch_bounds__(256) k_seal_bbox_map(float *__restrict__ xyzs,
 }
 
 // The samples of a call: all M slots, or -- in the device-driven loop, whose sample buffers may hold stale slots of earlier iterations
-// beyond the live ones -- the slots of the iteration's live list (count read on the device: live_count[state[3]] with the loop record).
+// beyond the live ones -- the slots of the iteration's live list (count read on the device: live_count[SdnLoopRecord::iteration] with the loop record).
 struct SealSlots {
     const uint32_t *live_idx;     // or nullptr = slots 0 .. M-1
     const uint32_t *live_count;
     const int32_t *state;
     uint32_t M;
-    __device__ __forceinline__ uint32_t count() const { return live_idx ? (state ? live_count[state[3]] : live_count[0]) : M; }
+    __device__ __forceinline__ uint32_t count() const { return live_idx ? (state ? live_count[sdn_loop(state)->iteration] : live_count[0]) : M; }
     __device__ __forceinline__ uint32_t slot(uint32_t j) const { return live_idx ? live_idx[j] : j; }
 };
 

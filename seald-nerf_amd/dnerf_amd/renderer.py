@@ -673,7 +673,8 @@ class DeviceLoop:
     def collect(self, nears, fars, want_stats):
         out = {"image": self.image_out, "depth": self.depth_out, "weights_sum": self.buf["weights_sum"], "nears": nears, "fars": fars}
         if want_stats:
-            iters = int(self.buf["state"][3].item())
+            from sdn_backend import LOOP_ITERATION
+            iters = int(self.buf["state"][LOOP_ITERATION].item())
             tr = self.buf["trace"][: 2 * iters].cpu().view(-1, 2).tolist()
             out["trace"] = [(a, s, a * s + (128 - (a * s) % 128)) for a, s in tr]
             out["n_samples"] = int(self.buf["live_counts"][:iters].sum().item())

@@ -92,6 +92,13 @@ class SdnRenderCtx(ctypes.Structure):
                    ("frame_cull", _vp * MAX_GROUP_FRAMES), ("field_f32", _i32), ("reserved2_", _i32)])
 
 
+# Word indices of `SdnLoopRecord` (include/sdn_hip.h: the 16 ints of `SdnRenderCtx.state`, one name per word, same order)
+LOOP_WORDS = ("n_alive", "n_step", "steps_done", "iteration", "side", "N", "max_steps", "advance_calls", "frozen_len", "survivors",
+              "mailbox_lo", "mailbox_hi", "frame_tag", "tend_lo", "tend_hi", "culled_start")
+(LOOP_N_ALIVE, LOOP_N_STEP, LOOP_STEPS_DONE, LOOP_ITERATION, LOOP_SIDE, LOOP_N, LOOP_MAX_STEPS, LOOP_ADVANCE_CALLS, LOOP_FROZEN_LEN,
+ LOOP_SURVIVORS, LOOP_MAILBOX_LO, LOOP_MAILBOX_HI, LOOP_FRAME_TAG, LOOP_TEND_LO, LOOP_TEND_HI, LOOP_CULLED_START) = range(len(LOOP_WORDS))
+
+
 class SdnSealBox(ctypes.Structure):
     """Mirror of `SdnSealBox` in include/sdn_hip.h."""
     _fields_ = [("bounds", _f32 * 24), ("n_bounds", _u32), ("n_tris", _u32), ("tris", _vp), ("test_dir", _f32 * 3), ("tinv", _f32 * 12),

@@ -677,3 +677,56 @@ def test_persistent_two_set_field_kernel_is_the_one_tile_kernel_bit_for_bit(smal
     finally:
         sel(-1)
         sdn_backend.lib.sdn_field_persistent_workgroups(0)
+
+
+def test_frame_group_of_3600_ray_frames_and_the_loop_record_by_name():
+    """60x60 frames: 3600 rays are no multiple of 256, so already the first launches of a three-frame loop have workgroups that
+    straddle a frame boundary (the frame rounds of k_march_rays / k_composite_march).  Three cameras at three times (the canonical
+    t = 0 among them) through ONE `DeviceLoop(..., frames=3)`: image, depth and weights_sum of every frame are bit for bit those of
+    the frame through a single-frame loop.  The single-frame loop in turn equals `render_frame` in image, depth, weights_sum, trace
+    and sample count.  (Trace and sample count of the GROUP are not those of its frames: the group's schedule is
+    n_step = clamp(3 N // n_alive_group, 1, 8) over the alive rays of all three frames.)
+    After every single-frame render the loop record is read through the names of `SdnLoopRecord` (sdn_backend.LOOP_*)."""
+    import sdn_backend as B
+    from dnerf_amd import fused, scene
+    from dnerf_amd.bench_scene import build_scene
+    from dnerf_amd.renderer import render_frame, DeviceLoop
+    sc = build_scene(H=60, W=60, device="cuda", seed=0)
+    dev, N, max_steps = sc.rays_o.device, 3600, 1024
+    assert sc.rays_o.shape[0] == N
+    f = fused.FusedField(sc.model, sc.time, fp16=True)
+    times, cams = [0.5, 0.0, 0.25], []
+    for az in (30.0, 140.0, 310.0):
+        ro, rd = scene.get_rays(scene.look_at_pose(az, 25.0), scene.intrinsics(sc.H, sc.W), sc.H, sc.W)
+        cams.append((torch.from_numpy(ro).to(dev), torch.from_numpy(rd).to(dev)))
+    one = DeviceLoop(sc.model, f, N, dev, max_steps=max_steps)
+    alone, steady = [], 0
+    for (ro, rd), t in zip(cams, times):
+        tt = torch.tensor([[t]], dtype=torch.float32, device=dev)
+        a = render_frame(sc.model, ro, rd, tt, fp16=True, field=fused.FusedField(sc.model, tt, fp16=True), max_steps=max_steps)
+        b = one.render(ro, rd, t)
+        torch.cuda.synchronize()
+        assert torch.equal(a["image"], b["image"]), t
+        assert torch.equal(torch.nan_to_num(a["depth"]), torch.nan_to_num(b["depth"])), t
+        assert torch.equal(a["weights_sum"], b["weights_sum"]), t
+        assert [tuple(x) for x in a["trace"]] == [tuple(x) for x in b["trace"]], t
+        assert a["n_samples"] == b["n_samples"] > 1000, t
+        rec = one.buf["state"].cpu().tolist()
+        assert rec[B.LOOP_ITERATION] == len(b["trace"]), rec
+        assert rec[B.LOOP_N] == N and rec[B.LOOP_MAX_STEPS] == max_steps, rec
+        assert rec[B.LOOP_N_ALIVE] == 0 or rec[B.LOOP_STEPS_DONE] >= max_steps, rec
+        steady += sum(1 for x in b["trace"] if x[1] == 8)
+        alone.append((b["image"].clone(), b["depth"].clone(), b["weights_sum"].clone()))
+    assert steady >= 1      # an n_step == 8 iteration: the steady kernel (k_composite_march) ran
+    grp = DeviceLoop(sc.model, f, 3 * N, dev, max_steps=max_steps, frames=3)
+    g = grp.render(torch.cat([c[0] for c in cams]).contiguous(), torch.cat([c[1] for c in cams]).contiguous(), times)
+    torch.cuda.synchronize()
+    assert any(x[1] == 8 for x in g["trace"]) and g["n_samples"] > 0
+    rec = grp.buf["state"].cpu().tolist()          # the named record on the group path
+    assert rec[B.LOOP_ITERATION] == len(g["trace"]) and rec[B.LOOP_N] == 3 * N and rec[B.LOOP_MAX_STEPS] == max_steps, rec
+    assert rec[B.LOOP_N_ALIVE] == 0 or rec[B.LOOP_STEPS_DONE] >= max_steps, rec
+    for k in range(3):
+        s = slice(k * N, (k + 1) * N)
+        assert torch.equal(g["image"][s], alone[k][0]), k
+        assert torch.equal(torch.nan_to_num(g["depth"][s]), torch.nan_to_num(alone[k][1])), k
+        assert torch.equal(g["weights_sum"][s], alone[k][2]), k
