@@ -271,7 +271,8 @@ int sdn_field_build_quad_table(const void *embeddings, int dtype, const int32_t 
 
 /* ---------------------------------------------------------------------------
  * density-grid maintenance  (reference: NeRFRenderer.update_extra_state, dnerf/renderer.py:453-555; the network queries of
- * :470-497 / :503-533, the EMA of :536-538, the mean + packbits of :539-545).  No host synchronisation in any of the three.
+ * :470-497 / :503-533, the EMA of :536-538, the mean + packbits of :539-545; and mark_untrained_grid, :389-451).  No host
+ * synchronisation in any of them.
  * ------------------------------------------------------------------------- */
 /* tmp_slice[cell] = density_scale * sigma(jittered centre of `cell`, t) for one time slice and one cascade, through the fused
  * field network (weights / bias0 / table / offsets_host / S / H / bound / zero_deform as for sdn_field_forward_f16; bias0 carries
@@ -299,6 +300,18 @@ int sdn_density_grid_ema(float *density_grid, const float *tmp_grid, uint64_t n,
  * (raymarching.cu:268-289) for all n cells of all slices at once (n % 8 == 0).  mean_out (device [2], or NULL) = {mean, threshold}. */
 int sdn_density_grid_pack(const float *density_grid, uint64_t n, const double *sum, float density_thresh, float *mean_out,
                           uint8_t *bitfield, void *stream);
+/* NeRFRenderer.mark_untrained_grid, dnerf/renderer.py:389-451: density_grid [T, cascade, H^3] (Morton order) gets -1, in every one of
+ * the T time slices, in each cell that none of the B cameras sees.  For cascade `cas` (:424-427) cas_bound = min(2^cas, bound),
+ * half = cas_bound / H and the cell's point is (2 * coord / (H - 1) - 1) * (cas_bound - half); a camera sees it (:435-441) if
+ * cam = (point - pose[:3,3]) @ pose[:3,:3] has cam.z > 0, |cam.x| < cx / fx * cam.z + 2 * half and |cam.y| < cy / fy * cam.z + 2 * half,
+ * all in fp32.  Seen cells are not written.  marked[cas] = number of unseen cells of the cascade (what :451 prints, summed); the
+ * call zeroes it on `stream` first.  Poses are staged SDN_MARK_POSE_CHUNK at a time.  SDN_E_BADARG: null grid or poses, B == 0, H zero
+ * or not a power of two, fx or fy zero; SDN_E_UNSUPPORTED: H > 1024 (morton3D spreads 10 bits per axis) or cascade > 65535. */
+#define SDN_MARK_POSE_CHUNK 256
+int sdn_mark_untrained_grid(float *density_grid, uint32_t T, uint32_t cascade, uint32_t H, float bound,
+                            const float *poses /* [B,4,4] row-major c2w, device */, uint32_t B,
+                            float fx, float fy, float cx, float cy,
+                            uint32_t *marked /* [cascade] cells seen by no camera, device, may be NULL */, void *stream);
 
 /* ---------------------------------------------------------------------------
  * ffmlp: fully fused bias-free MLP on fp16  (reference: ffmlp/src/ffmlp.h:8-14, ffmlp/src/ffmlp.cu:630-894,

@@ -236,8 +236,58 @@ class NeRFRenderer(nn.Module):
         return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "deform": dens["deform"]}
 
     # ------------------------------------------------------------------------------------------
-    # density-grid maintenance (dnerf/renderer.py:453-555)
+    # density-grid maintenance (dnerf/renderer.py:389-555)
     # ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def mark_untrained_grid(self, poses, intrinsic, S=64):
+        """dnerf/renderer.py:389-451: `density_grid` = -1, in every time slice, in the cells that none of the cameras `poses` [B,4,4]
+        (camera-to-world, torch or numpy) with `intrinsic` = (fx, fy, cx, cy) sees; `update_extra_state` leaves negative cells as they are,
+        so they never enter the bitfield.  One launch of csrc/density.hip when the grid lives on the device, the torch restatement
+        (`_untrained_cells`, batched by `S` as the reference is) otherwise.  `untrained_cells` keeps the per-cascade count of marked
+        cells of the last call as a tensor on the grid's device (the reference prints their sum).
+        Only `density_grid` is written: `density_bitfield`, `mean_density` and `iter_density` stay as they are, so the cull-grid caches
+        keyed on the bitfield need no invalidation here -- the marks reach the bitfield with the next `update_extra_state`."""
+        if not self.cuda_ray:
+            return
+        if isinstance(poses, np.ndarray):
+            poses = torch.from_numpy(poses)
+        grid = self.density_grid
+        poses = poses.to(grid.device, torch.float32).contiguous()
+        fx, fy, cx, cy = (float(v) for v in intrinsic)
+        if grid.is_cuda and grid.dtype == torch.float32 and grid.is_contiguous():
+            from sdn_backend import lib, check, ptr, stream
+            self.untrained_cells = torch.empty(self.cascade, dtype=torch.int32, device=grid.device)
+            check(lib.sdn_mark_untrained_grid(ptr(grid), grid.shape[0], self.cascade, self.grid_size, float(self.bound), ptr(poses), poses.shape[0],
+                                              fx, fy, cx, cy, ptr(self.untrained_cells), stream()), "mark_untrained_grid")
+            torch.autograd.graph.increment_version(grid)      # written behind torch's back
+            return
+        unseen = self._untrained_cells(poses, (fx, fy, cx, cy), S)
+        grid[unseen.unsqueeze(0).expand_as(grid)] = -1
+        self.untrained_cells = unseen.sum(dim=1, dtype=torch.int32)
+
+    def _untrained_cells(self, poses, intrinsic, S=64):
+        """[cascade, grid_size^3] bool in Morton order: the cells whose point no camera sees (dnerf/renderer.py:403-447), S^3 cells
+        against S poses at a time.  The checker of the native pass, and the path of a grid that is not on the device."""
+        from .scene import morton3d
+        fx, fy, cx, cy = intrinsic
+        H, dev = self.grid_size, poses.device
+        ax = np.arange(H)
+        coords = np.stack(np.meshgrid(ax, ax, ax, indexing="ij"), axis=-1).reshape(-1, 3)
+        order = torch.from_numpy(morton3d(coords[:, 0], coords[:, 1], coords[:, 2]).astype(np.int64)).to(dev).split(S ** 3)
+        xyzs = 2 * torch.from_numpy(coords).to(dev).float() / (H - 1) - 1
+        unseen = torch.empty(self.cascade, H ** 3, dtype=torch.bool, device=dev)
+        for cas in range(self.cascade):
+            bound = min(2 ** cas, self.bound)
+            half_grid = bound / H
+            for cells, points in zip(order, (xyzs * (bound - half_grid)).split(S ** 3)):
+                seen = torch.zeros(points.shape[0], dtype=torch.bool, device=dev)
+                for c2w in poses.split(S):
+                    cam = (points - c2w[:, :3, 3].unsqueeze(1)) @ c2w[:, :3, :3]           # [S,N,3]
+                    z = cam[..., 2]
+                    seen |= ((z > 0) & (cam[..., 0].abs() < cx / fx * z + half_grid * 2) & (cam[..., 1].abs() < cy / fy * z + half_grid * 2)).any(0)
+                unseen[cas, cells] = ~seen
+        return unseen
+
     @torch.no_grad()
     def update_extra_state(self, decay=0.95, S=128):
         if not self.cuda_ray:

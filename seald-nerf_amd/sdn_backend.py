@@ -65,11 +65,13 @@ PROTOTYPES = {
     "sdn_density_query_cells_f32": [_vp, _vp, _u32, _vp, _u32, _u32, _f32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp],
     "sdn_density_grid_ema": [_vp, _vp, ctypes.c_uint64, _f32, _vp, _vp],
     "sdn_density_grid_pack": [_vp, ctypes.c_uint64, _vp, _f32, _vp, _vp, _vp],
+    "sdn_mark_untrained_grid": [_vp, _u32, _u32, _u32, _f32, _vp, _u32, _f32, _f32, _f32, _f32, _vp, _vp],
     "sdn_ffmlp_forward": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp],
     "sdn_ffmlp_inference": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp],
     "sdn_ffmlp_backward": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _vp, _vp],
 }
 MAX_GROUP_FRAMES = 16   # SDN_MAX_GROUP_FRAMES
+MARK_POSE_CHUNK = 256   # SDN_MARK_POSE_CHUNK
 
 
 class SdnFrameTime(ctypes.Structure):
