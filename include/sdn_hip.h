@@ -314,6 +314,26 @@ int sdn_mark_untrained_grid(float *density_grid, uint32_t T, uint32_t cascade, u
                             uint32_t *marked /* [cascade] cells seen by no camera, device, may be NULL */, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * error-map ray sampling  (reference: nerf/utils.py:105-118 `get_rays` with an error map, main_dnerf.py --error_map)
+ * ------------------------------------------------------------------------- */
+/* One weighted draw of N of the S * S cells of one error-map row WITHOUT replacement, and a random pixel of the H x W image inside each
+ * drawn cell; one launch of one workgroup, no host read-back, no scratch memory.
+ * The draw is torch.multinomial(error_row, N, replacement=False)'s: key_i = error_row[i] / (-log(u_i)) in fp32, u_i uniform in (0, 1),
+ * and the N cells with the largest keys.  u_i = u_key[i] when u_key is given (replays a draw), else a counter-based generator on
+ * (seed, i).  Equal keys go to the lower cell index; a cell of weight zero has key zero and is taken only after every cell of
+ * positive weight.  Weights must be finite and non-negative: anything else is outside the contract (such a cell is drawn as if
+ * its weight were zero or some positive number, never out of bounds).
+ * Pixel of cell c (nerf/utils.py:108-112), sx = (float)H / S, sy = (float)W / S, every operation in fp32:
+ *   x = min((long)((c / S) * sx + r0 * sx), H - 1),  y = min((long)((c % S) * sy + r1 * sy), W - 1),  inds = x * W + y
+ * with r0 = u_fine[k], r1 = u_fine[N + k] for result k when u_fine is given (uniform [0, 1)), else from the generator on (seed, c).
+ * Results: inds_coarse[k] = c and inds[k] belong together; k runs over the drawn cells in ascending cell order (the order carries
+ * no meaning: a batch's rays are a set).
+ * SDN_E_BADARG: a null error_row / inds_coarse / inds, S == 0 or S * S > 16384, N == 0 or N > S * S, H or W zero, H * W >= 2^31. */
+int sdn_error_map_sample(const float *error_row /* [S*S] */, uint32_t S, uint32_t N, uint32_t H, uint32_t W,
+                         const float *u_key /* optional [S*S] in (0,1) */, const float *u_fine /* optional [2N] in [0,1) */,
+                         uint64_t seed, int32_t *inds_coarse /* [N] */, int32_t *inds /* [N] */, void *stream);
+
+/* ---------------------------------------------------------------------------
  * ffmlp: fully fused bias-free MLP on fp16  (reference: ffmlp/src/ffmlp.h:8-14, ffmlp/src/ffmlp.cu:630-894,
  * Python wrapper ffmlp/ffmlp.py:15-168).  Layout as in the reference: inputs [B, input_dim], outputs [B, 16],
  * forward_buffer / backward_buffer [num_layers, B, hidden_dim], all fp16 and point-major; weights flat fp16,
@@ -637,6 +657,17 @@ typedef struct SdnTrainStep {
     /* optional deterministic mode: grid_offsets[16] * 2 64-bit words of device memory for the table gradient's order-independent
      * accumulation (sdn_grid_encode_backward_det); NULL = the plain half atomics */
     void *det_scratch;
+    /* Optional error-map update of the reference's trainer (dnerf/utils.py:91-113; main_dnerf.py --error_map), inside the compositing
+     * launch: ray k of the batch has the loss l = mean over channels of (pred - target)^2 (utils.py:85; a ray without samples, or one
+     * dropped for the sample budget, predicts the background) and error_row[inds_coarse[k]] = 0.1f * error_row[inds_coarse[k]] + 0.9f * l.
+     * error_row: the map row of this step's frame, [S * S] floats, updated in place; NULL = no update, and the step is what it was
+     * without these fields.  Precondition: 0 <= inds_coarse[k] < S * S, and no two rays share a cell -- the cells come from a draw
+     * WITHOUT replacement (sdn_error_map_sample, torch.multinomial(replacement=False)); the update is a plain read-modify-write, not
+     * an atomic.  It happens in every call that has a forward pass (mode 0 / 1, phase 0 / 2; not mode 2, not phase 1), before and
+     * whether or not the scaler skips the optimizer step, as in the reference. */
+    float *error_row;
+    const int32_t *inds_coarse;     /* [N], required with error_row */
+    float *ray_loss_out;            /* optional [N]: every ray's loss l (read only with error_row) */
 } SdnTrainStep;
 
 /* Byte offsets into the workspace of what a caller or a test may want to look at.  fp16 "flat" networks are laid out as the fused

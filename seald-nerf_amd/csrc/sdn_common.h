@@ -36,6 +36,14 @@ __device__ __forceinline__ unsigned long long *sdn_loop_mailbox(const SdnLoopRec
 template <typename T>
 static inline T sdn_div_up(T a, T b) { return (a + b - 1) / b; }
 
+// The counter-based generator of the training kernels: splitmix64 of (seed, counter), 64 random bits
+__device__ __forceinline__ uint64_t sdn_splitmix64(uint64_t seed, uint32_t i) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(i + 1u);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // float(exp(double(x))): agrees with the oracle's correctly rounded exp except for
 // double-rounding ties (~1e-9 of inputs); the compositing kernels are HBM/latency
 // bound, the fp64 polynomial is free next to their loads.

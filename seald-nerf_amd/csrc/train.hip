@@ -161,11 +161,7 @@ void dw_job_list(const Layout &L, unsigned char *ws, uint32_t M, sdn_ffh::DwJob 
 
 // ---- small kernels --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float u01(uint64_t seed, uint32_t i) {   // splitmix64 -> 24 random bits -> [0, 1), like torch.rand's float grid
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(i + 1u);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
+    return (float)(uint32_t)(sdn_splitmix64(seed, i) >> 40) * (1.0f / 16777216.0f);
 }
 
 __global__ void __launch_bounds__(256) k_train_rays(float *__restrict__ noises, const float *__restrict__ given, uint32_t N, uint64_t seed, int perturb,
@@ -406,6 +402,10 @@ template <class Net> struct CompositeArgs {
     T *dcol_out, *dh0;                   // backward: [M,16], [M]
     uint32_t M, N;
     float T_thresh, bg_value, density_scale;
+    // optional error-map update (utils.py:91-113): the map row of this step's frame, every ray's cell in it, every ray's loss
+    float *error_row;
+    const int32_t *inds_coarse;
+    float *ray_loss_out;
 };
 
 template <class Net>
@@ -461,6 +461,14 @@ __global__ void __launch_bounds__(256) k_train_composite_fwd(CompositeArgs<Net> 
             if (P.image_out) P.image_out[(size_t)index * 3 + ch] = pred;
         }
         P.sq_err[index] = sq;
+        if (P.error_row) {
+            // utils.py:85, :109-110, for every ray of the batch (one without samples predicts the background).  No two rays share a
+            // cell (the draw is without replacement), so the read-modify-write needs no atomic.
+            const float l = sq / 3.0f;
+            const int32_t c = P.inds_coarse[index];
+            P.error_row[c] = 0.1f * P.error_row[c] + 0.9f * l;
+            if (P.ray_loss_out) P.ray_loss_out[index] = l;
+        }
     }
 }
 
@@ -831,6 +839,7 @@ bool step_ok(const SdnTrainStep *s, bool fp32) {
     if (s->phase < 0 || s->phase > 2 || (s->mode == 2 && s->phase != 0)) return false;
     if (s->mode != 2 && s->phase != 2 && (!s->rays_o || !s->rays_d || !s->bitfield || !s->aabb || !s->counter)) return false;
     if (s->mode != 2 && s->phase != 1 && (!s->target || !s->loss_out)) return false;
+    if (s->mode != 2 && s->phase != 1 && s->error_row && !s->inds_coarse) return false;
     if (s->N == 0 || s->M == 0 || s->max_steps == 0 || s->bound <= 0 || (fp32 && s->grid_offsets[kLevels] <= 0)) return false;
     for (int i = 0; i < SDN_TRAIN_N_PARAMS; i++) if (!s->params[i].param) return false;
     if (s->mode != 1) {
@@ -959,7 +968,8 @@ int sdn_train_step_f16(const SdnTrainStep *s, void *stream) {
     SDN_TRY(sdn_ffh::forward_packed(H(L.col_in), ws + L.pk_col_f, M, kColIn, kColW, kColL, ACT_RELU, H(L.col_hidden), H(L.col_out), st));
     // ---- compositing, loss, and their gradients (renderer.py:309-318, utils.py:85-125), one wave per ray ----------------------------
     const CompositeArgs<Fp16Net> ca{F(L.sigmas), deltas, H(L.col_out), H(L.hout), ray_table, s->bg_color, s->target, s->loss_scale, F(L.weights_sum),
-                           F(L.depth), F(L.image), s->image_out, F(L.sq_err), H(L.dcol_out), H(L.dh0), M, N, s->T_thresh, s->bg_value, s->density_scale};
+                           F(L.depth), F(L.image), s->image_out, F(L.sq_err), H(L.dcol_out), H(L.dh0), M, N, s->T_thresh, s->bg_value, s->density_scale,
+                           s->error_row, s->inds_coarse, s->ray_loss_out};
     hipLaunchKernelGGL(k_train_composite_fwd<Fp16Net>, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
     hipLaunchKernelGGL(k_train_loss, dim3(1), dim3(1024), 0, st, F(L.sq_err), N, s->loss_out);
 
@@ -1430,7 +1440,7 @@ int sdn_train_step_f32(const SdnTrainStep *s, void *stream) {
     // ---- compositing, loss and their gradients, one wave per ray -------------------------------------------------------------------------
     const CompositeArgs<Fp32Net> ca{F(L.sigmas), deltas, F(L.col_out), F(L.hout), ray_table, s->bg_color, s->target, nullptr, F(L.weights_sum), F(L.depth),
                                     F(L.image), s->image_out, F(L.sq_err), F(L.dcol_out), F(L.dh0), M, N, s->T_thresh, s->bg_value,
-                                    s->density_scale};
+                                    s->density_scale, s->error_row, s->inds_coarse, s->ray_loss_out};
     hipLaunchKernelGGL(k_train_composite_fwd<Fp32Net>, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);
     hipLaunchKernelGGL(k_train_loss, dim3(1), dim3(1024), 0, st, F(L.sq_err), N, s->loss_out);
     hipLaunchKernelGGL(k_train_composite_bwd<Fp32Net>, dim3(sdn_div_up(N, 4u)), dim3(256), 0, st, ca);

@@ -209,7 +209,7 @@ class NeRFDataset:
         poses = self.poses[index].to(self.device)
         times = self.times[index].to(self.device)
         error_map = None if self.error_map is None else self.error_map[index]
-        rays = get_rays(poses, self.intrinsics, self.H, self.W, self.num_rays, error_map)
+        rays = get_rays(poses, self.intrinsics, self.H, self.W, self.num_rays, error_map, native_error_map=getattr(self.opt, "native_error_map", False))
         out = {"time": times, "H": self.H, "W": self.W, "rays_o": rays["rays_o"], "rays_d": rays["rays_d"]}
         if self.images is not None:
             images = self.images[index].to(self.device)

@@ -53,9 +53,14 @@ class EditTrainStep:
         self._checked += 1
         return self.loop.render(rays_o, rays_d, time, bg_color=bg_color, check=self._checked in (1, 2) or self._checked % 256 == 0)["image"]
 
-    def __call__(self, rays_o, rays_d, time):
+    def __call__(self, rays_o, rays_d, time, error_map=None, index=None, inds_coarse=None):
+        """error_map / index / inds_coarse: the student's step folds its per-ray losses into the map (`NativeTrainStep.load`)."""
         target = self.proxy_truth(rays_o, rays_d, time)
-        return self.step(rays_o, rays_d, target, time)
+        if error_map is None and index is None and inds_coarse is None:
+            return self.step(rays_o, rays_d, target, time)
+        if not hasattr(self.step, "check_error_map_args"):
+            raise NotImplementedError("EditTrainStep: the error-map update is part of the native step only (native=True)")
+        return self.step(rays_o, rays_d, target, time, error_map=error_map, index=index, inds_coarse=inds_coarse)
 
     def run(self, batches):
         """Software-pipelined epoch over an iterable of (rays_o, rays_d, time): the student's graph for batch k is launched (one call,

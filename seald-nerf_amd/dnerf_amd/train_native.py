@@ -94,6 +94,9 @@ class NativeTrainStep:
         self.bg = torch.zeros(n_rays, 3, dtype=f32, device=device)
         self.image = torch.zeros(n_rays, 3, dtype=f32, device=device)
         self.loss = torch.zeros(1, dtype=f32, device=device)
+        self.ray_loss = torch.zeros(n_rays, dtype=f32, device=device)       # every ray's loss of the last step that updated an error map
+        self._inds32 = torch.zeros(n_rays, dtype=torch.int32, device=device)     # int64 `inds_coarse` of a caller, narrowed
+        self._error_map = None                                              # (map, frame, int32 cells) of the next step
         self.adam_steps = torch.zeros(2, dtype=f32, device=device)
         self.time = 0.5
         self._offsets = (ctypes.c_int32 * 17)(*[int(v) for v in enc.offsets.cpu().tolist()])
@@ -302,7 +305,50 @@ class NativeTrainStep:
         own.copy_(t.reshape(own.shape))
         return own
 
-    def load(self, rays_o, rays_d, target, time, bg_color=None):
+    @staticmethod
+    def check_error_map_args(error_map, index, inds_coarse, n_rays, device):
+        """The three error-map arguments of `load` / `__call__`, validated: (frame, cells per row).  error_map: the provider's
+        [frames, S * S] fp32 tensor, contiguous and on `device` (it is updated in place through its address: nothing is copied);
+        index: an int or a one-element list, as `collate` hands it over; inds_coarse: int32 or int64, [n_rays] or [1, n_rays]."""
+        if error_map is None or index is None or inds_coarse is None:
+            raise ValueError("NativeTrainStep: error_map, index and inds_coarse go together")
+        if not isinstance(error_map, torch.Tensor) or error_map.dtype != torch.float32 or error_map.dim() != 2:
+            raise ValueError("NativeTrainStep: error_map must be the [frames, S * S] fp32 map")
+        if not error_map.is_contiguous():
+            raise ValueError("NativeTrainStep: error_map must be contiguous (it is updated in place; nothing is copied)")
+        if isinstance(index, (list, tuple)):
+            if len(index) != 1:
+                raise ValueError("NativeTrainStep: one frame per step (index must be an int or a one-element list)")
+            index = index[0]
+        if isinstance(index, bool) or not isinstance(index, (int, np.integer)):
+            raise ValueError("NativeTrainStep: index must be an int or a one-element list")
+        if not 0 <= int(index) < error_map.shape[0]:
+            raise ValueError(f"NativeTrainStep: frame {int(index)} is not a row of the [{error_map.shape[0]}, ...] error map")
+        if (not isinstance(inds_coarse, torch.Tensor) or inds_coarse.dtype not in (torch.int32, torch.int64)
+                or tuple(inds_coarse.shape) not in ((n_rays,), (1, n_rays))):
+            raise ValueError(f"NativeTrainStep: inds_coarse must be int32 or int64 of shape [{n_rays}] or [1, {n_rays}]")
+        dev = torch.device(device)
+        for name, t in (("error_map", error_map), ("inds_coarse", inds_coarse)):
+            if t.device.type != dev.type or (dev.index is not None and t.device.index != dev.index):
+                raise ValueError(f"NativeTrainStep: {name} must be on the step's device {dev}, not {t.device}")
+        return int(index), int(error_map.shape[1])
+
+    def _load_error_map(self, error_map, index, inds_coarse):
+        if error_map is None and index is None and inds_coarse is None:
+            self._error_map = None
+            return
+        frame, _ = self.check_error_map_args(error_map, index, inds_coarse, self.n_rays, self.device)
+        cells = inds_coarse.reshape(-1)
+        if cells.dtype != torch.int32 or not cells.is_contiguous():
+            self._inds32.copy_(cells)
+            cells = self._inds32
+        self._error_map = (error_map, frame, cells)
+
+    def load(self, rays_o, rays_d, target, time, bg_color=None, error_map=None, index=None, inds_coarse=None):
+        """error_map / index / inds_coarse (all three or none): the step also folds every ray's loss into row `index` of the map at the
+        ray's cell, `0.1 * old + 0.9 * loss` (dnerf/utils.py:91-113), inside its compositing launch; `self.ray_loss` then holds the
+        losses.  The cells must be distinct (a draw without replacement).  They apply to the next step only."""
+        self._load_error_map(error_map, index, inds_coarse)
         if self._pending is None:                         # (a prefetched batch already has its rays in place and its samples marched)
             self.rays_o, self.rays_d = self._adopt(rays_o, self._rays[self._set][0]), self._adopt(rays_d, self._rays[self._set][1])
             self.time = self._time_value(time)
@@ -357,7 +403,8 @@ class NativeTrainStep:
             done.record(side)
         self._pending = {"set": q, "event": done, "time": tv, "local_step": m.local_step, "step_count": self.step_count, "rays": (ro, rd)}
 
-    def __call__(self, rays_o=None, rays_d=None, target=None, time=None, bg_color=None, grads_only=False):
+    def __call__(self, rays_o=None, rays_d=None, target=None, time=None, bg_color=None, grads_only=False, error_map=None, index=None,
+                 inds_coarse=None):
         """One training step on the loaded batch.  Arguments, if given: `time` is taken by value; fp32 contiguous tensors on this device
         are READ IN PLACE by the step's kernels (`_adopt`: no device-to-device copy) -- stream order makes later writes on the SAME
         stream safe, but a loader that refills its ray / target buffers on ANOTHER stream must order that stream behind the step (an
@@ -367,7 +414,9 @@ class NativeTrainStep:
         Returns the loss tensor (device, overwritten by the next step).  grads_only: forward + backward only -- gradients stay in the
         workspace (`view("g_deform", ...)`), nothing is updated."""
         if rays_o is not None:
-            self.load(rays_o, rays_d, target, time, bg_color)
+            self.load(rays_o, rays_d, target, time, bg_color, error_map, index, inds_coarse)
+        elif error_map is not None or index is not None or inds_coarse is not None:
+            self._load_error_map(error_map, index, inds_coarse)
         m = self.model
         if self._rec is None or self._M != _budget(int(m.mean_count)):
             self._build()       # `update_extra_state` moved the budget (dnerf/renderer.py:550-552): new buffers, same parameters
@@ -401,6 +450,12 @@ class NativeTrainStep:
             n = self.ema_updates + (0 if grads_only else 1)
             r.ema_decay = min(self.ema_decay, (1 + n) / (10 + n))       # torch_ema: num_updates is incremented before use
         r.deform_frozen = 0 if self.train_deform else 1
+        em, self._error_map = self._error_map, None
+        if em is not None:
+            r.error_row = em[0].data_ptr() + em[1] * em[0].shape[1] * 4
+            r.inds_coarse, r.ray_loss_out = em[2].data_ptr(), self.ray_loss.data_ptr()
+        else:
+            r.error_row, r.inds_coarse, r.ray_loss_out = None, None, None
         if self.grad_sync is not None and not grads_only:
             # data parallel: backward | all-reduce of the gradient buffers (sums; the optimizer divides) | optimizer
             r.mode, r.keep_deform, r.grad_divisor = 1, 1, float(self.grad_sync.world)
@@ -416,6 +471,8 @@ class NativeTrainStep:
         self._grads_left = self.fp32 and grads_only
         _sdn.check(self._fn(ctypes.byref(r), _sdn.stream()), "train_step")
         m.local_step += 1
+        if em is not None:
+            torch.autograd.graph.increment_version(em[0])
         if not grads_only:
             torch.autograd.graph.increment_version(self._written)
             if self._table_side is not None:

@@ -14,9 +14,50 @@ def _meshgrid(*args):
     return torch.meshgrid(*args, indexing="ij")
 
 
+_draws = 0      # native draws made without an explicit seed: each gets its own
+
+
 @torch.no_grad()
-def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1):
-    """poses [B,4,4] cam2world, intrinsics (fx, fy, cx, cy) -> {'rays_o','rays_d': [B,N,3] (+ 'inds', 'inds_coarse')}."""
+def sample_error_map(error_row, N, H, W, u_key=None, u_fine=None, seed=None):
+    """The error-map draw of nerf/utils.py:105-118 as ONE launch (`sdn_error_map_sample`, csrc/error_map.hip): N of the S * S cells of
+    one map row, weighted, without replacement -- torch.multinomial's rule, the N largest w / Exp(1) -- and a random pixel of the
+    H x W image inside each.  Returns (inds_coarse, inds), int32 [N] on the map's device, in ascending cell order.
+    u_key [S * S] in (0, 1) / u_fine [2 N] in [0, 1): the uniforms to use instead of the generator (replays a draw).  seed: the
+    generator's; None = torch's seed (`torch.manual_seed`) mixed with the number of such draws made so far, without touching the device."""
+    global _draws
+    if not isinstance(error_row, torch.Tensor) or error_row.dtype != torch.float32 or error_row.dim() != 1 or not error_row.is_contiguous():
+        raise ValueError("sample_error_map: error_row must be a contiguous fp32 tensor [S * S] (one row of the error map)")
+    cells = error_row.numel()
+    S = int(round(cells ** 0.5))
+    if S * S != cells or not 1 <= cells <= 16384:
+        raise ValueError(f"sample_error_map: {cells} cells are not a square map of at most 128 x 128")
+    N, H, W = int(N), int(H), int(W)
+    if not 1 <= N <= cells:
+        raise ValueError(f"sample_error_map: cannot draw {N} of {cells} cells without replacement")
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"sample_error_map: image size {H} x {W}")
+    for name, u, n in (("u_key", u_key, cells), ("u_fine", u_fine, 2 * N)):
+        if u is not None and (not isinstance(u, torch.Tensor) or u.dtype != torch.float32 or u.numel() != n or not u.is_contiguous()
+                              or u.device != error_row.device):
+            raise ValueError(f"sample_error_map: {name} must be a contiguous fp32 tensor of {n} values on the map's device")
+    if not error_row.is_cuda:
+        raise _sdn.SdnError("sample_error_map: the map must be on the GPU (there is no CPU fallback)")
+    if seed is None:
+        seed = torch.initial_seed() * 0x9E3779B97F4A7C15 + _draws
+        _draws += 1
+    inds_coarse = torch.empty(N, dtype=torch.int32, device=error_row.device)
+    inds = torch.empty(N, dtype=torch.int32, device=error_row.device)
+    with _sdn.timed("error_map_sample", cells):
+        _check(_lib.sdn_error_map_sample(_ptr(error_row), S, N, H, W, _ptr(u_key), _ptr(u_fine), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                         _ptr(inds_coarse), _ptr(inds), _stream()), "error_map_sample")
+    return inds_coarse, inds
+
+
+@torch.no_grad()
+def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1, native_error_map=False):
+    """poses [B,4,4] cam2world, intrinsics (fx, fy, cx, cy) -> {'rays_o','rays_d': [B,N,3] (+ 'inds', 'inds_coarse')}.
+    native_error_map: with a map on the GPU and B == 1, the error-map draw is `sample_error_map` ('inds_coarse' is then int32, as
+    `NativeTrainStep` takes it) instead of torch.multinomial and the expressions after it."""
     device = poses.device
     B = poses.shape[0]
     fx, fy, cx, cy = [float(v) for v in intrinsics]
@@ -47,6 +88,10 @@ def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1):
             inds = (inds[:, 0] * W + inds[:, 1]).expand([B, N])
         elif error_map is None:  # :102-104
             inds = torch.randint(0, H * W, size=[N], device=device).expand([B, N])
+        elif native_error_map and error_map.is_cuda and B == 1:  # :105-118 in one launch
+            inds_coarse, inds = sample_error_map(error_map.reshape(-1), N, H, W)
+            inds_coarse, inds = inds_coarse[None], inds[None].long()
+            results["inds_coarse"] = inds_coarse
         else:  # :105-118
             inds_coarse = torch.multinomial(error_map.to(device), N, replacement=False)
             inds_x, inds_y = inds_coarse // 128, inds_coarse % 128

@@ -66,6 +66,7 @@ PROTOTYPES = {
     "sdn_density_grid_ema": [_vp, _vp, ctypes.c_uint64, _f32, _vp, _vp],
     "sdn_density_grid_pack": [_vp, ctypes.c_uint64, _vp, _f32, _vp, _vp, _vp],
     "sdn_mark_untrained_grid": [_vp, _u32, _u32, _u32, _f32, _vp, _u32, _f32, _f32, _f32, _f32, _vp, _vp],
+    "sdn_error_map_sample": [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp],
     "sdn_ffmlp_forward": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp],
     "sdn_ffmlp_inference": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp],
     "sdn_ffmlp_backward": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _vp, _vp],
@@ -130,7 +131,8 @@ class SdnTrainStep(ctypes.Structure):
                 + [("adam_steps", _vp), ("loss_scale", _vp), ("growth_tracker", _vp), ("growth_factor", _f32), ("backoff_factor", _f32),
                    ("growth_interval", _u32), ("ema_decay", _f32), ("loss_out", _vp), ("image_out", _vp), ("workspace", _vp),
                    ("mode", ctypes.c_int32), ("keep_deform", ctypes.c_int32), ("grad_divisor", _f32), ("deform_frozen", ctypes.c_int32), ("phase", ctypes.c_int32), ("sample_set", ctypes.c_int32),
-                   ("table_stream", _vp), ("table_ready", _vp), ("table_done", _vp), ("det_scratch", _vp)])
+                   ("table_stream", _vp), ("table_ready", _vp), ("table_done", _vp), ("det_scratch", _vp),
+                   ("error_row", _vp), ("inds_coarse", _vp), ("ray_loss_out", _vp)])
 
 
 class SdnTrainLayout(ctypes.Structure):
