@@ -398,7 +398,10 @@ typedef struct SdnLoopRecord {
     int32_t culled_start;   /* 1: iteration 0 runs on the culled list (sdn_render_begin's culled start); the trace logs N for it */
 } SdnLoopRecord;
 
-/* Arguments of sdn_seal_bbox_map(_source) / sdn_seal_modify_hsv / sdn_seal_modify_rgb as one record (host memory except `tris`), for SdnRenderCtx.seal. */
+/* Arguments of sdn_seal_bbox_map(_source) / sdn_seal_anchor_map / sdn_seal_modify_hsv / sdn_seal_modify_rgb as one record (host memory
+ * except `tris`), for SdnRenderCtx.seal.  `kind` (at the end) selects the mapper; the box test and the colour fields serve both. */
+#define SDN_SEAL_BBOX 0
+#define SDN_SEAL_ANCHOR 1
 typedef struct SdnSealBox {
     float bounds[24];          /* n_bounds x {lo xyz, hi xyz} */
     uint32_t n_bounds, n_tris;
@@ -414,7 +417,12 @@ typedef struct SdnSealBox {
     int32_t has_map_source;
     float source_bound[6], map_source[3];
     uint32_t reserved_;
-    void *scratch;             /* device, 32 bytes, zeroed once by the caller: [0..15] modify_rgb's sum / count, [16..19] the mapSource flag word */
+    void *scratch;             /* device, 32 bytes, zeroed once by the caller: [0..15] modify_rgb's sum / count, [16..19] the flag word
+                                * of `mapSource` / of the anchor mapper ("did this iteration map anything") */
+    /* SDN_SEAL_BBOX: the fields above.  SDN_SEAL_ANCHOR (SealAnchorMapper, seal_utils.py:464-578): bounds / tris / test_dir are the
+     * mapper's one box, `scale` its per-axis scale about v_anchor; tinv, rinv, center and the mapSource fields are not read */
+    uint32_t kind;
+    float v_anchor[3], v_offset[3], v_h[3], len_h, radius;
 } SdnSealBox;
 
 /* Several frames may be rendered TOGETHER by one loop ("frame group": the shards of consecutive frames of a camera path / of
@@ -466,8 +474,9 @@ typedef struct SdnRenderCtx {
      * samples, survivors and the trace (which logs N for iteration 0) are unchanged; `sigmas` holds the per-ray start parameters
      * between sdn_render_begin and the first field launch. */
     float *rays_tend;
-    /* optional SealD edit: a bounding-box seal mapper applied to every iteration's samples between the marcher and the field
-     * network (sdn_seal_bbox_map) and to the colours of the mapped samples after it (sdn_seal_modify_hsv); NULL = no edit */
+    /* optional SealD edit: a bounding-box or anchor seal mapper (SdnSealBox::kind) applied to every iteration's samples between the
+     * marcher and the field network (sdn_seal_bbox_map(_source) / sdn_seal_anchor_map) and to the colours of the mapped samples after
+     * it (sdn_seal_modify_hsv / _rgb); NULL = no edit */
     const struct SdnSealBox *seal;
     uint8_t *seal_mask;        /* [M_cap] scratch, required with `seal` */
     /* optional frame group (n_group_frames > 1; N = n_group_frames * rays_per_frame): frame f marches frame_bitfield[f], its field
@@ -534,7 +543,7 @@ int sdn_render_frames_pipelined_f16(const SdnRenderCtx *const *ctxs, uint32_t n_
                                     const uint8_t *exclusive_frames, const SdnFrameTime *frame_times, void *const *done_events,
                                     uint32_t *iterations_out);
 /* ---------------------------------------------------------------------------
- * SealD-NeRF bounding-box seal mapper on the sample stream  (reference: SealNeRF/seal_utils.py:132-153 map_mask, :245-286
+ * SealD-NeRF bounding-box and anchor seal mappers on the sample stream  (reference: SealNeRF/seal_utils.py:132-153 map_mask, :245-286
  * SealBBoxMapper.map_to_origin, :638-693 moller_trumbore / points_in_mesh, :747-758 modify_hsv; torch boolean-mask code there)
  * ------------------------------------------------------------------------- */
 /* In place on xyzs / dirs [M,3] (device): a sample that is non-zero in every coordinate, strictly inside one of the n_bounds (<= 4)
@@ -554,6 +563,22 @@ int sdn_seal_bbox_map_source(float *xyzs, float *dirs, uint32_t M, const float *
                              uint32_t n_tris, const float *test_dir, const float *tinv, const float *rinv, const float *scale,
                              const float *center, const float *source_bound, const float *map_source, uint32_t *flag, uint8_t *mask,
                              const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state, void *stream);
+/* SealD-NeRF anchor (control-point) seal mapper, SealAnchorMapper.map_to_origin (seal_utils.py:522-578, project_points :736-744), in
+ * place on xyzs [M,3] (device); the reference returns dirs unchanged, so `dirs` is not touched (may be NULL).  bounds / tris / test_dir
+ * describe the mapper's box exactly as for sdn_seal_bbox_map; flag, live_idx / live_count / state as for sdn_seal_bbox_map_source.
+ * Step 1: the box test (map_mask) of every slot; the flag is raised to this call's tag if a sample OF THE CALL is inside -- the
+ * reference returns its inputs otherwise (:527-528).  Step 2, if it was raised: for EVERY one of the M slots, in the box or not
+ * (valid_mask is not ANDed with map_mask there) -- project the point onto the anchor plane (normal v_h, through v_anchor), shear the
+ * projection back by (plane distance / len_h) * v_offset, and call the slot valid if that point lies within `radius` of v_anchor,
+ * plane distance / (radius - that distance) < len_h / radius * 1.1 (IEEE division: inf and NaN compare false) and the point is on
+ * the side of the plane v_h points away from; valid slots receive (sheared point + (len_h - plane distance) / 10 * v_h / len_h -
+ * v_anchor) * scale + v_anchor.  mask [M] u8: 1 for valid slots, else 0 (all 0, points untouched, if the flag was not raised).
+ * Slots with a zero coordinate never count for step 1 (`points.all(1)`) but are candidates in step 2 like any other point.
+ * v_anchor, v_offset, v_h, scale: host arrays [3]. */
+int sdn_seal_anchor_map(float *xyzs, float *dirs, uint32_t M, const float *bounds, uint32_t n_bounds, const float *tris,
+                        uint32_t n_tris, const float *test_dir, const float *v_anchor, const float *v_offset, const float *v_h,
+                        float len_h, float radius, const float *scale, uint32_t *flag, uint8_t *mask, const uint32_t *live_idx,
+                        const uint32_t *live_count, const int32_t *state, void *stream);
 /* rgbs [M,3] of the masked samples: rgb -> hsv, + (dh, ds, dv), -> rgb (color_utils.py:31-63), in place. */
 int sdn_seal_modify_hsv(float *rgbs, const uint8_t *mask, uint32_t M, float dh, float ds, float dv, void *stream);
 /* modify_rgb (seal_utils.py:761-777) on the masked samples, in place: hue and saturation of the target colour (r, g, b), brightness

@@ -55,6 +55,13 @@ static int seal_map(const SdnRenderCtx &c, uint32_t m_slots, hipStream_t st) {
     const SdnSealBox *s = c.seal;
     if (!s) return 0;
     if (!c.seal_mask) return SDN_E_BADARG;
+    if (s->kind == SDN_SEAL_ANCHOR) {
+        if (!s->scratch) return SDN_E_BADARG;
+        return sdn_seal_anchor_map(c.xyzs, c.dirs, m_slots, s->bounds, s->n_bounds, s->tris, s->n_tris, s->test_dir, s->v_anchor, s->v_offset,
+                                   s->v_h, s->len_h, s->radius, s->scale, (uint32_t *)((char *)s->scratch + 16), c.seal_mask, c.live_idx,
+                                   sdn_int::live_counters(c), c.state, st);
+    }
+    if (s->kind != SDN_SEAL_BBOX) return SDN_E_UNSUPPORTED;
     if (s->has_map_source) {
         if (!s->scratch) return SDN_E_BADARG;
         return sdn_seal_bbox_map_source(c.xyzs, c.dirs, m_slots, s->bounds, s->n_bounds, s->tris, s->n_tris, s->test_dir, s->tinv, s->rinv,

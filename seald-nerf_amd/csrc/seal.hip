@@ -1,4 +1,4 @@
-// SealD-NeRF bounding-box seal mapper on the sample stream (scope row "next" #1) for gfx950.
+// SealD-NeRF bounding-box and anchor (control-point) seal mappers on the sample stream (scope row "next" #1) for gfx950.
 //
 // Behavioural contract: SealNeRF/seal_utils.py of the reference --
 //   map_mask            :132-153  (points.all(1) & strict AABB test of each bound, then points_in_mesh)
@@ -9,20 +9,27 @@
 //   modify_rgb :761-777 (hue / saturation of a target colour, brightness = its V + (V - mean V of the masked samples) + light offset)
 //   the `mapSource` redirect of SealBBoxMapper.map_to_origin :269-273 (samples strictly inside the source box are sent to one point --
 //   only in calls that map at least one sample: the early return of :251-252 comes first)
+//   SealAnchorMapper.map_to_origin :522-578 with project_points :736-744 (the cone / plane-side deformation, see k_seal_anchor_apply)
 // The reference evaluates this with boolean-mask gathers / scatters and O(points x triangles) temporaries in torch, inside the
 // render loop; here it is one lane per sample slot, in place, between the marcher and the field kernel.  Dot products are
 // accumulated x, y, z in fp32 (torch's einsum order is library-defined): masks agree with the torch restatement except for
 // points within rounding of a face, mapped coordinates to ~1e-6 -- the tolerances its tests state.
 #include "sdn_common.h"
 
+#include <atomic>
+
 namespace {
 
-struct SealBoxArgs {
+struct SealBoxTest {        // map_mask's inputs
     float bounds[4][6];     // up to 4 AABBs {lo xyz, hi xyz}
     uint32_t n_bounds;
     const float *tris;      // [F][12]: v0, E1, E2, N (host-precomputed from the box triangles)
     uint32_t n_tris;
     float test_dir[3];
+};
+
+struct SealBoxArgs {
+    SealBoxTest box;
     float tinv[12];         // inverse transform, rows of [3 x 4]
     float rinv[9];          // inverse rotation
     float scale[3], center[3];
@@ -45,6 +52,20 @@ __device__ __forceinline__ bool any_hit(const float *__restrict__ tris, uint32_t
     return hit;
 }
 
+// map_mask (seal_utils.py:132-153) of one point: non-zero in every coordinate (`points.all(1)`: empty slots and exact zeros are never
+// inside), strictly inside one of the AABBs, and inside the mesh
+__device__ __forceinline__ bool seal_in_box(const SealBoxTest &B, float x, float y, float z) {
+    bool in = false;
+    if (x != 0.0f && y != 0.0f && z != 0.0f) {
+        for (uint32_t b = 0; b < B.n_bounds; b++)
+            in |= (B.bounds[b][3] > x) & (x > B.bounds[b][0]) & (B.bounds[b][4] > y) & (y > B.bounds[b][1]) & (B.bounds[b][5] > z) & (z > B.bounds[b][2]);
+    }
+    if (in)
+        in = any_hit(B.tris, B.n_tris, x, y, z, B.test_dir[0], B.test_dir[1], B.test_dir[2]) &&
+             any_hit(B.tris, B.n_tris, x, y, z, -B.test_dir[0], -B.test_dir[1], -B.test_dir[2]);
+    return in;
+}
+
 struct SealSourceArgs {
     float lo[3], hi[3];     // the source box (`empty_bound`)
     float to[3];            // `map_source`
@@ -57,14 +78,7 @@ __global__ void __launch_bounds__(256) k_seal_bbox_map(float *__restrict__ xyzs,
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
     const float x = xyzs[(size_t)i * 3], y = xyzs[(size_t)i * 3 + 1], z = xyzs[(size_t)i * 3 + 2];
-    bool in = false;
-    if (x != 0.0f && y != 0.0f && z != 0.0f) {   // `points.all(1)`: empty slots (and exact zeros) are never mapped
-        for (uint32_t b = 0; b < A.n_bounds; b++)
-            in |= (A.bounds[b][3] > x) & (x > A.bounds[b][0]) & (A.bounds[b][4] > y) & (y > A.bounds[b][1]) & (A.bounds[b][5] > z) & (z > A.bounds[b][2]);
-    }
-    if (in)
-        in = any_hit(A.tris, A.n_tris, x, y, z, A.test_dir[0], A.test_dir[1], A.test_dir[2]) &&
-             any_hit(A.tris, A.n_tris, x, y, z, -A.test_dir[0], -A.test_dir[1], -A.test_dir[2]);
+    const bool in = seal_in_box(A.box, x, y, z);
     mask[i] = in ? 1 : 0;
     if (!in) return;
     float m[3];
@@ -108,6 +122,64 @@ __global__ void __launch_bounds__(256) k_seal_source_redirect(float *__restrict_
     const float x = xyzs[(size_t)i * 3], y = xyzs[(size_t)i * 3 + 1], z = xyzs[(size_t)i * 3 + 2];
     if ((S.hi[0] > x) & (x > S.lo[0]) & (S.hi[1] > y) & (y > S.lo[1]) & (S.hi[2] > z) & (z > S.lo[2])) {
         xyzs[(size_t)i * 3] = S.to[0]; xyzs[(size_t)i * 3 + 1] = S.to[1]; xyzs[(size_t)i * 3 + 2] = S.to[2];
+    }
+}
+
+// ---- anchor (control-point) mapper, SealAnchorMapper.map_to_origin, seal_utils.py:522-578 -------------------------------------------
+// Step 1 of a call: map_mask of every slot into `mask` (k_seal_any then raises the call's flag if one of the call's samples is inside).
+__global__ void __launch_bounds__(256) k_seal_box_mask(const float *__restrict__ xyzs, uint32_t M, SealBoxTest B, uint8_t *__restrict__ mask) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    mask[i] = seal_in_box(B, xyzs[(size_t)i * 3], xyzs[(size_t)i * 3 + 1], xyzs[(size_t)i * 3 + 2]) ? 1 : 0;
+}
+
+struct SealAnchorArgs {
+    float v_anchor[3], v_offset[3], v_h[3];
+    float len_h, radius;
+    float scale[3];
+    uint32_t tag;
+    const uint32_t *flag;
+};
+
+// Step 2.  The box only gates the call (the early return of :527-528): in a call whose flag was raised the cone and plane-side
+// predicates of :545-551 are evaluated for EVERY slot -- `valid_mask` is not ANDed with `map_mask` in the reference.  That includes
+// the empty slots (a zero coordinate): they fail map_mask, so they never raise the flag, but they are candidates for valid_mask as any
+// other point is, and are mapped when the origin-side point they hold lies in the cone (the loops never evaluate or composite them).
+// The statements follow the reference's order in fp32; `d / (radius - pop)` is left to IEEE (pop == radius: +inf, or NaN for d == 0 --
+// both compare false, as they do in torch).  mask: 1 for valid slots, 0 otherwise; all zeros, points untouched, in a call that maps nothing.
+__global__ void __launch_bounds__(256) k_seal_anchor_apply(float *__restrict__ xyzs, uint32_t M, SealAnchorArgs A, uint8_t *__restrict__ mask) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    if (*A.flag != A.tag) { mask[i] = 0; return; }
+    const float p[3] = {xyzs[(size_t)i * 3], xyzs[(size_t)i * 3 + 1], xyzs[(size_t)i * 3 + 2]};
+    // project_points(v_h, v_anchor, points), :736-744
+    const float along = dot3(p[0] - A.v_anchor[0], p[1] - A.v_anchor[1], p[2] - A.v_anchor[2], A.v_h[0], A.v_h[1], A.v_h[2]) /
+                        dot3(A.v_h[0], A.v_h[1], A.v_h[2], A.v_h[0], A.v_h[1], A.v_h[2]);
+    float proj[3], to_plane[3];
+    #pragma unroll
+    for (int k = 0; k < 3; k++) {
+        proj[k] = p[k] - along * A.v_h[k];
+        to_plane[k] = proj[k] - p[k];
+    }
+    const float d = sqrtf(dot3(to_plane[0], to_plane[1], to_plane[2], to_plane[0], to_plane[1], to_plane[2]));   // points_plane_dist
+    const float offset_scale = d / A.len_h;
+    float pop[3], r[3];                                        // projected_offset_points, and their offset from the anchor
+    #pragma unroll
+    for (int k = 0; k < 3; k++) {
+        pop[k] = proj[k] - offset_scale * A.v_offset[k];
+        r[k] = pop[k] - A.v_anchor[k];
+    }
+    const float pop_dist = sqrtf(dot3(r[0], r[1], r[2], r[0], r[1], r[2]));
+    const bool in_cone = (pop_dist <= A.radius) & (d / (A.radius - pop_dist) < A.len_h / A.radius * 1.1f);
+    const bool valid_side = dot3(to_plane[0], to_plane[1], to_plane[2], A.v_h[0], A.v_h[1], A.v_h[2]) > 0.0f;
+    const bool valid = in_cone & valid_side;
+    mask[i] = valid ? 1 : 0;
+    if (!valid) return;
+    const float lift = -((A.len_h - d) / 10.0f);               // v_map = lift * v_h / len_h, :555-556
+    #pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float mapped = pop[k] - lift * A.v_h[k] / A.len_h;
+        xyzs[(size_t)i * 3 + k] = (mapped - A.v_anchor[k]) * A.scale[k] + A.v_anchor[k];
     }
 }
 
@@ -212,6 +284,20 @@ __global__ void __launch_bounds__(256) k_seal_hsv(float *__restrict__ rgbs, cons
     rgbs[(size_t)i * 3] = o0 + m; rgbs[(size_t)i * 3 + 1] = o1 + m; rgbs[(size_t)i * 3 + 2] = o2 + m;
 }
 
+// One tag per call that asks "did this call map anything": unique in the process, so any flag word sees increasing tags whichever entry
+// points share it (a wrap after 2^32 calls would need the flag cleared: not in this process's life)
+std::atomic<uint32_t> g_seal_tag{0};
+
+int fill_box_test(SealBoxTest &b, const float *bounds, uint32_t n_bounds, const float *tris, uint32_t n_tris, const float *test_dir) {
+    if (!bounds || !tris || !test_dir) return SDN_E_BADARG;
+    if (n_bounds == 0 || n_bounds > 4 || n_tris == 0) return SDN_E_UNSUPPORTED;
+    for (uint32_t k = 0; k < n_bounds; k++)
+        for (int j = 0; j < 6; j++) b.bounds[k][j] = bounds[6 * k + j];
+    b.n_bounds = n_bounds; b.tris = tris; b.n_tris = n_tris;
+    for (int k = 0; k < 3; k++) b.test_dir[k] = test_dir[k];
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -220,13 +306,10 @@ int sdn_seal_bbox_map(float *xyzs, float *dirs, uint32_t M, const float *bounds,
                       const float *test_dir, const float *tinv, const float *rinv, const float *scale, const float *center, uint8_t *mask,
                       void *stream) {
     if (M == 0) return 0;
-    if (!xyzs || !dirs || !bounds || !tris || !test_dir || !tinv || !rinv || !scale || !center || !mask) return SDN_E_BADARG;
-    if (n_bounds == 0 || n_bounds > 4 || n_tris == 0) return SDN_E_UNSUPPORTED;
+    if (!xyzs || !dirs || !tinv || !rinv || !scale || !center || !mask) return SDN_E_BADARG;
     SealBoxArgs a;
-    for (uint32_t b = 0; b < n_bounds; b++)
-        for (int k = 0; k < 6; k++) a.bounds[b][k] = bounds[6 * b + k];
-    a.n_bounds = n_bounds; a.tris = tris; a.n_tris = n_tris;
-    for (int k = 0; k < 3; k++) { a.test_dir[k] = test_dir[k]; a.scale[k] = scale[k]; a.center[k] = center[k]; }
+    if (int rc = fill_box_test(a.box, bounds, n_bounds, tris, n_tris, test_dir)) return rc;
+    for (int k = 0; k < 3; k++) { a.scale[k] = scale[k]; a.center[k] = center[k]; }
     for (int k = 0; k < 12; k++) a.tinv[k] = tinv[k];
     for (int k = 0; k < 9; k++) a.rinv[k] = rinv[k];
     hipLaunchKernelGGL(k_seal_bbox_map, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, xyzs, dirs, M, a, mask);
@@ -244,14 +327,38 @@ int sdn_seal_bbox_map_source(float *xyzs, float *dirs, uint32_t M, const float *
     if (!source_bound || !map_source || !flag || (live_idx && !live_count)) return SDN_E_BADARG;
     int rc = sdn_seal_bbox_map(xyzs, dirs, M, bounds, n_bounds, tris, n_tris, test_dir, tinv, rinv, scale, center, mask, stream);
     if (rc) return rc;
-    static uint32_t next_tag = 0;          // tags only grow (a wrap after 2^32 calls would need the flag cleared: not in this process's life)
-    const uint32_t tag = ++next_tag;
+    const uint32_t tag = ++g_seal_tag;
     SealSourceArgs sa;
     for (int k = 0; k < 3; k++) { sa.lo[k] = source_bound[k]; sa.hi[k] = source_bound[3 + k]; sa.to[k] = map_source[k]; }
     sa.tag = tag; sa.flag = flag;
     const SealSlots L{live_idx, live_count, state, M};
     hipLaunchKernelGGL(k_seal_any, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)mask, L, flag, tag);
     hipLaunchKernelGGL(k_seal_source_redirect, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, xyzs, (const uint8_t *)mask, M, sa);
+    return sdn_launch_status();
+}
+
+// SealAnchorMapper.map_to_origin (seal_utils.py:522-578), in place on xyzs (dirs are returned unchanged by the reference and are not
+// touched: the pointer is accepted for symmetry and may be NULL).  flag, live list: as for sdn_seal_bbox_map_source -- the flag is raised
+// when a sample OF THE CALL lies in the box, and then every one of the M slots is tested against the cone.  Three launches, no host
+// synchronisation.
+int sdn_seal_anchor_map(float *xyzs, float *dirs, uint32_t M, const float *bounds, uint32_t n_bounds, const float *tris, uint32_t n_tris,
+                        const float *test_dir, const float *v_anchor, const float *v_offset, const float *v_h, float len_h, float radius,
+                        const float *scale, uint32_t *flag, uint8_t *mask, const uint32_t *live_idx, const uint32_t *live_count,
+                        const int32_t *state, void *stream) {
+    (void)dirs;
+    if (M == 0) return 0;
+    if (!xyzs || !v_anchor || !v_offset || !v_h || !scale || !flag || !mask || (live_idx && !live_count)) return SDN_E_BADARG;
+    SealBoxTest b;
+    if (int rc = fill_box_test(b, bounds, n_bounds, tris, n_tris, test_dir)) return rc;
+    SealAnchorArgs a;
+    for (int k = 0; k < 3; k++) { a.v_anchor[k] = v_anchor[k]; a.v_offset[k] = v_offset[k]; a.v_h[k] = v_h[k]; a.scale[k] = scale[k]; }
+    a.len_h = len_h; a.radius = radius; a.flag = flag;
+    const uint32_t tag = a.tag = ++g_seal_tag;
+    const SealSlots L{live_idx, live_count, state, M};
+    const dim3 grid(sdn_div_up(M, 256u)), block(256);
+    hipLaunchKernelGGL(k_seal_box_mask, grid, block, 0, (hipStream_t)stream, (const float *)xyzs, M, b, mask);
+    hipLaunchKernelGGL(k_seal_any, grid, block, 0, (hipStream_t)stream, (const uint8_t *)mask, L, flag, tag);
+    hipLaunchKernelGGL(k_seal_anchor_apply, grid, block, 0, (hipStream_t)stream, xyzs, M, a, mask);
     return sdn_launch_status();
 }
 

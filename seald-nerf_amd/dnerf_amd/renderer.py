@@ -577,10 +577,11 @@ class DeviceLoop:
         self.set_mapper(mapper)
 
     def set_mapper(self, mapper):
-        """Hooks a SealD bounding-box seal mapper (`dnerf_amd.seal_mapper.SealBBoxMapper`, or None) into every iteration of the native
-        loop: samples are mapped back to their origin before the field kernel, colours of the mapped samples re-mapped after it."""
+        """Hooks a SealD seal mapper (`dnerf_amd.seal_mapper.SealBBoxMapper` / `SealAnchorMapper`, or None) into every iteration of the
+        native loop: samples are mapped back to their origin before the field kernel, colours of the mapped samples re-mapped after it."""
         import ctypes
-        from sdn_backend import SdnSealBox
+        from sdn_backend import SdnSealBox, SEAL_ANCHOR, SEAL_BBOX
+        from .seal_mapper import SealAnchorMapper
         c = self.ctx
         self.mapper = mapper
         if mapper is None:
@@ -589,15 +590,22 @@ class DeviceLoop:
         dev = self.buf["xyzs"].device
         mapper.map_data_conversion(self.buf["xyzs"])
         a = mapper._native_args(dev)
-        if self.frames > 1 and ("map_source" in mapper.map_data or "rgb" in mapper.map_data):
-            # both options look at ALL samples of a loop iteration (the mean brightness of the masked ones, "does the call map anything"):
-            # in a frame group an iteration holds several frames' samples, which the reference never mixes
-            raise NotImplementedError("mapSource / rgb tint depend on the set of samples of an iteration: render such edits one frame per loop")
+        anchor = isinstance(mapper, SealAnchorMapper)
+        if self.frames > 1 and (anchor or mapper.redirects_source or "rgb" in mapper.map_data):
+            # these look at ALL samples of a loop iteration (the mean brightness of the masked ones, "does the call map anything" of
+            # mapSource and of the anchor mapper): in a frame group an iteration holds several frames' samples, which the reference never mixes
+            raise NotImplementedError("mapSource / rgb tint / the anchor mapper depend on the set of samples of an iteration: render such edits one frame per loop")
         box = SdnSealBox()
         for k in range(6 * a["n_bounds"]):
             box.bounds[k] = a["bounds"][k]
         box.n_bounds, box.n_tris, box.tris = a["n_bounds"], a["n_tris"], a["tris"].data_ptr()
-        for name, n in (("test_dir", 3), ("tinv", 12), ("rinv", 9), ("scale", 3), ("center", 3)):
+        box.kind = SEAL_ANCHOR if anchor else SEAL_BBOX
+        if anchor:
+            fields = (("test_dir", 3), ("scale", 3), ("v_anchor", 3), ("v_offset", 3), ("v_h", 3))
+            box.len_h, box.radius = a["len_h"], a["radius"]
+        else:
+            fields = (("test_dir", 3), ("tinv", 12), ("rinv", 9), ("scale", 3), ("center", 3))
+        for name, n in fields:
             for k in range(n):
                 getattr(box, name)[k] = a[name][k]
         if "hsv" in mapper.map_data:
@@ -605,13 +613,13 @@ class DeviceLoop:
             box.hsv[0], box.hsv[1], box.hsv[2], box.modify_hsv = h[0], h[1], h[2], 1
         if "rgb" in a:
             box.rgb[0], box.rgb[1], box.rgb[2], box.rgb_light_offset, box.modify_rgb = a["rgb"][0], a["rgb"][1], a["rgb"][2], a["rgb_light_offset"], 1
-        if "map_source" in a:
+        if mapper.redirects_source:
             for k in range(6):
                 box.source_bound[k] = a["source_bound"][k]
             for k in range(3):
                 box.map_source[k] = a["map_source"][k]
             box.has_map_source = 1
-        # the record's 32 scratch bytes (modify_rgb's sum / count, the mapSource flag word) belong to THIS loop, zeroed once: the loops
+        # the record's 32 scratch bytes (modify_rgb's sum / count, the mapSource / anchor flag word) belong to THIS loop, zeroed once: the loops
         # of a PipelinedDeviceLoop share the mapper and run on their own streams, and one buffer between them would let one loop's
         # memset / sums land in another's mean brightness, and a later loop's mapSource tag cancel an earlier one's redirect
         scratch = torch.zeros(32, dtype=torch.uint8, device=dev)
@@ -950,9 +958,10 @@ class RayBatchRenderer:
     def __init__(self, model, field, N, device, max_steps=1024, T_thresh=1e-2, dt_gamma=0.0, mapper=None, samples_per_ray=96):
         import sdn_backend as B
         B.require_device()
-        if mapper is not None and ("rgb" in mapper.map_data or "map_source" in mapper.map_data):
+        if mapper is not None and ("rgb" in mapper.map_data or mapper.redirects_source):
             # (the loop's iterations are the unit both options look at -- modify_rgb's mean brightness, map_to_origin's early return:
-            #  one pass over all samples would tint and redirect differently from the reference's loop)
+            #  one pass over all samples would tint and redirect differently from the reference's loop.  The anchor mapper's early return
+            #  is no such case: its box contains its cone, so an iteration without a sample in the box holds no sample to map either)
             raise NotImplementedError("mapSource / rgb tint depend on the loop's iterations: use render_frame / DeviceLoop for such edits")
         self.model, self.field, self.N, self.device, self.mapper = model, field, int(N), torch.device(device), mapper
         self.max_steps, self.T_thresh, self.dt_gamma = int(max_steps), float(T_thresh), float(dt_gamma)

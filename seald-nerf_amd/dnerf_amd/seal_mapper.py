@@ -1,13 +1,14 @@
-"""SealD-NeRF bounding-box mapper on the device (scope row "next" #1): the object the teacher / student renderers hook
-between the marcher and the field network (`map_to_origin`) and after it (`map_color`).
+"""SealD-NeRF bounding-box and anchor (control-point) mappers on the device (scope row "next" #1): the objects the teacher /
+student renderers hook between the marcher and the field network (`map_to_origin`) and after it (`map_color`).
 
 Mirrors, with the same names and `map_data` keys, the pieces of the reference that sit inside the render loop:
   * `SealMapper.map_mask` / `map_color` / `map_data_conversion`      SealNeRF/seal_utils.py:40-153
   * `SealBBoxMapper.__init__` / `map_to_origin`                      SealNeRF/seal_utils.py:156-286
+  * `SealAnchorMapper.__init__` / `map_to_origin`, `project_points`  SealNeRF/seal_utils.py:464-578, 736-744
   * `moller_trumbore`, `points_in_mesh`                              SealNeRF/seal_utils.py:638-693
   * `modify_hsv`, `modify_rgb`                                       SealNeRF/seal_utils.py:747-777
   * `rgb2hsv_torch`, `hsv2rgb_torch` ([N,3] form)                    SealNeRF/color_utils.py:31-63
-without pytorch3d / trimesh / open3d (none is installed here): the "from" box is the oriented box of the config's `raw`
+without pytorch3d / trimesh / open3d / scikit-spatial (none is installed here): the bbox mapper's "from" box is the oriented box of the config's `raw`
 points, the "to" box its scaled + transformed image, both as 8 vertices / 12 triangles.
 
 One documented difference: trimesh's `bounding_box_oriented` searches a minimum-volume box over the convex hull; here `raw` is
@@ -176,6 +177,69 @@ class SealMapper:
     def map_to_origin(self, points, dirs=None):
         raise NotImplementedError()
 
+    @property
+    def redirects_source(self):
+        """Does `map_to_origin` carry the bbox mapper's `mapSource` redirect?  (Only that mapper's `map_data["map_source"]` is one: the
+        anchor mapper stores a flag for pretraining under the same key.)"""
+        return False
+
+    # ---- device fast path: csrc/seal.hip, one lane per sample slot, in place ---------------------------------------------
+    # (shared by the mappers: the box test's arguments and the colour part are the same for all of them; `_native_map_args` adds a
+    #  mapper's own `map_to_origin` constants, `map_to_origin_` is its kernel call)
+    def _native_ok(self, points, dirs):
+        return (points.is_cuda and dirs is not None and points.dtype == torch.float32 and dirs.dtype == torch.float32
+                and points.is_contiguous() and dirs.is_contiguous())
+
+    def _native_map_args(self, md, f32, cfl):
+        raise NotImplementedError()
+
+    def _native_args(self, device):
+        import ctypes
+        key = str(device)
+        if getattr(self, "_native_key", None) != key:
+            f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32))  # noqa: E731
+            cfl = lambda a: (ctypes.c_float * a.size)(*a.reshape(-1).tolist())                          # noqa: E731
+            md = {k: (v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64))
+                  for k, v in self.map_data.items()}
+            tri = self.map_triangles.detach().cpu().double().numpy()
+            e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+            tris12 = np.concatenate([tri[:, 0], e1, e2, np.cross(e1, e2)], axis=1)
+            bounds = md["map_bound"].reshape(-1, 2, 3)
+            self._native = dict(tris=torch.from_numpy(f32(tris12)).to(device), n_tris=int(tris12.shape[0]),
+                                bounds=cfl(f32(bounds.reshape(-1, 6))), n_bounds=int(bounds.shape[0]),
+                                test_dir=cfl(f32(_TEST_DIR if self.map_test_dir is None else self.map_test_dir.cpu().numpy())),
+                                # [0..15] modify_rgb's sum / count, [16..19] the "did this call map anything" flag word (only ever raised),
+                                # zeroed once; used by the in-place calls (a DeviceLoop keeps its own: loops on other streams share the mapper)
+                                scratch=torch.zeros(32, dtype=torch.uint8, device=device))
+            self._native.update(self._native_map_args(md, f32, cfl))
+            if "rgb" in md:
+                self._native["rgb"] = [float(v) for v in f32(md["rgb"].reshape(3))]
+                self._native["rgb_light_offset"] = float(np.float32(md["rgb_light_offset"]))
+            self._native_key = key
+        return self._native
+
+    def map_to_origin_(self, points, dirs):
+        raise NotImplementedError()
+
+    @torch.no_grad()
+    def map_color_(self, rgbs, mask):
+        """In-place `map_color` of the masked samples (seal_utils.py:48-57: the hsv modification, then the rgb tint): HIP kernels on CUDA
+        fp32 buffers, the torch restatement otherwise (and for an `image` modification, which the mappers of this build do not carry)."""
+        if rgbs.is_cuda and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and "image" not in self.map_data:
+            from sdn_backend import lib, check, ptr, stream
+            m8 = mask.view(torch.uint8)
+            if "hsv" in self.map_data:
+                h = [float(v) for v in self.map_data["hsv"].reshape(-1).tolist()]
+                check(lib.sdn_seal_modify_hsv(ptr(rgbs), ptr(m8), rgbs.shape[0], h[0], h[1], h[2], stream()), "seal_modify_hsv")
+            if "rgb" in self.map_data:
+                a = self._native_args(rgbs.device)
+                c = a["rgb"]
+                check(lib.sdn_seal_modify_rgb(ptr(rgbs), ptr(m8), rgbs.shape[0], c[0], c[1], c[2], a["rgb_light_offset"], ptr(a["scratch"]),
+                                              None, None, None, stream()), "seal_modify_rgb")
+        elif bool(mask.any()):
+            rgbs[mask] = self.map_color(None, None, rgbs[mask]).to(rgbs.dtype)
+        return rgbs
+
 
 class SealBBoxMapper(SealMapper):
     """seal_utils.py:156-286.  seal_config: {type: 'bbox', raw: [N,3], transform: [4,4], scale: [3], boundType: 'from' | 'to' |
@@ -222,39 +286,16 @@ class SealBBoxMapper(SealMapper):
             self.map_data["map_source"] = seal_config["mapSource"]
         self.map_data_conversion(force=True)
 
-    # ---- device fast path: csrc/seal.hip, one lane per sample slot, in place ---------------------------------------------
-    def _native_ok(self, points, dirs):
-        return (points.is_cuda and dirs is not None and points.dtype == torch.float32 and dirs.dtype == torch.float32
-                and points.is_contiguous() and dirs.is_contiguous())
+    @property
+    def redirects_source(self):
+        return "map_source" in self.map_data
 
-    def _native_args(self, device):
-        import ctypes
-        key = str(device)
-        if getattr(self, "_native_key", None) != key:
-            f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32))  # noqa: E731
-            cfl = lambda a: (ctypes.c_float * a.size)(*a.reshape(-1).tolist())                          # noqa: E731
-            md = {k: (v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64))
-                  for k, v in self.map_data.items()}
-            tri = self.map_triangles.detach().cpu().double().numpy()
-            e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
-            tris12 = np.concatenate([tri[:, 0], e1, e2, np.cross(e1, e2)], axis=1)
-            bounds = md["map_bound"].reshape(-1, 2, 3)
-            self._native = dict(tris=torch.from_numpy(f32(tris12)).to(device), n_tris=int(tris12.shape[0]),
-                                bounds=cfl(f32(bounds.reshape(-1, 6))), n_bounds=int(bounds.shape[0]),
-                                test_dir=cfl(f32(_TEST_DIR if self.map_test_dir is None else self.map_test_dir.cpu().numpy())),
-                                tinv=cfl(f32(md["transform"][:3, :4])), rinv=cfl(f32(md["rotation"])), scale=cfl(f32(md["scale"])),
-                                center=cfl(f32(md["center"])),
-                                # [0..15] modify_rgb's sum / count, [16..19] the mapSource flag word (only ever raised), zeroed once;
-                                # used by the in-place calls below (a DeviceLoop keeps its own: loops on other streams share the mapper)
-                                scratch=torch.zeros(32, dtype=torch.uint8, device=device))
-            if "map_source" in md:
-                self._native["source_bound"] = cfl(f32(md["empty_bound"].reshape(2, 3)))
-                self._native["map_source"] = cfl(f32(md["map_source"].reshape(3)))
-            if "rgb" in md:
-                self._native["rgb"] = [float(v) for v in f32(md["rgb"].reshape(3))]
-                self._native["rgb_light_offset"] = float(np.float32(md["rgb_light_offset"]))
-            self._native_key = key
-        return self._native
+    def _native_map_args(self, md, f32, cfl):
+        a = dict(tinv=cfl(f32(md["transform"][:3, :4])), rinv=cfl(f32(md["rotation"])), scale=cfl(f32(md["scale"])), center=cfl(f32(md["center"])))
+        if self.redirects_source:
+            a["source_bound"] = cfl(f32(md["empty_bound"].reshape(2, 3)))
+            a["map_source"] = cfl(f32(md["map_source"].reshape(3)))
+        return a
 
     @torch.no_grad()
     def map_to_origin_(self, points, dirs):
@@ -273,25 +314,6 @@ class SealBBoxMapper(SealMapper):
             check(lib.sdn_seal_bbox_map(ptr(points), ptr(dirs), M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"], a["tinv"],
                                         a["rinv"], a["scale"], a["center"], ptr(mask), stream()), "seal_bbox_map")
         return mask.view(torch.bool)
-
-    @torch.no_grad()
-    def map_color_(self, rgbs, mask):
-        """In-place `map_color` of the masked samples (seal_utils.py:48-57: the hsv modification, then the rgb tint): HIP kernels on CUDA
-        fp32 buffers, the torch restatement otherwise (and for an `image` modification, which the bbox mapper of this build does not carry)."""
-        if rgbs.is_cuda and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and "image" not in self.map_data:
-            from sdn_backend import lib, check, ptr, stream
-            m8 = mask.view(torch.uint8)
-            if "hsv" in self.map_data:
-                h = [float(v) for v in self.map_data["hsv"].reshape(-1).tolist()]
-                check(lib.sdn_seal_modify_hsv(ptr(rgbs), ptr(m8), rgbs.shape[0], h[0], h[1], h[2], stream()), "seal_modify_hsv")
-            if "rgb" in self.map_data:
-                a = self._native_args(rgbs.device)
-                c = a["rgb"]
-                check(lib.sdn_seal_modify_rgb(ptr(rgbs), ptr(m8), rgbs.shape[0], c[0], c[1], c[2], a["rgb_light_offset"], ptr(a["scratch"]),
-                                              None, None, None, stream()), "seal_modify_rgb")
-        elif bool(mask.any()):
-            rgbs[mask] = self.map_color(None, None, rgbs[mask]).to(rgbs.dtype)
-        return rgbs
 
     @torch.no_grad()
     def map_to_origin(self, points, dirs=None):
@@ -329,11 +351,151 @@ class SealBBoxMapper(SealMapper):
             return points_copy, dirs_copy, mask
 
 
+def best_fit_plane(points):
+    """skspatial's `Plane.best_fit` in numpy -> (point, unit normal): the centroid, and the left singular vector of the centred
+    points (as 3 x N) with the smallest singular value.  The normal's sign is the SVD's."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    c = p.mean(0)
+    u, _, _ = np.linalg.svd((p - c).T, full_matrices=False)
+    return c, u[:, -1]
+
+
+def uv_sphere_points(radius, count=32):
+    """`count` x `count` latitude / longitude points of a sphere about the origin (both poles included)."""
+    theta = np.linspace(0.0, np.pi, count)
+    phi = np.linspace(0.0, 2.0 * np.pi, count, endpoint=False)
+    st = np.sin(theta)[:, None]
+    return radius * np.stack([st * np.cos(phi)[None], st * np.sin(phi)[None], np.cos(theta)[:, None] * np.ones_like(phi)[None]], -1).reshape(-1, 3)
+
+
+def project_points(plane_norm, plane_point, target_points):
+    """seal_utils.py:736-744."""
+    v_target_to_plane = target_points - plane_point
+    v_projection = (v_target_to_plane @ plane_norm).unsqueeze(1) / (plane_norm @ plane_norm) * plane_norm
+    return target_points - v_projection
+
+
+class SealAnchorMapper(SealMapper):
+    """seal_utils.py:464-578, the control-point (anchor) tool: the surface around an anchor is pulled along a vector.  seal_config:
+    {type: 'anchor', raw: [N,3] points that determine the anchor plane (their mean is the anchor), translation: [3], radius: the
+    affected radius in the plane, scale: [3], hsv / rgb / rgbLightOffset optional}.
+
+    The deformed region is a cone: its base the disk of `radius` around the anchor in the plane, its apex at anchor + 1.1 *
+    translation.  `map_to_origin` takes a sample of the cone back to the undeformed content: sheared back onto the plane's normal
+    through the anchor, then squeezed towards the plane (a tenth of its remaining height is kept), then scaled about the anchor.
+
+    The box (`to_mesh`) is the oriented box of the reference's point set: a sphere of 1.1 * radius about the anchor, the same sphere
+    moved by -0.1 * translation, and anchor + 1.1 * translation.  The sphere is a 32 x 32 latitude / longitude point set (trimesh's
+    `uv_sphere` is not available) and the box is `oriented_box`'s PCA-aligned one, so it may differ from trimesh's minimum-volume
+    `bounding_box_oriented`.  What the box decides: `force_fill_bound` (the occupancy cells an edit render marks), and the early return
+    of `map_to_origin` -- a call none of whose points lies in the box returns its inputs.  What it does not decide: WHICH points are
+    mapped.  In a call that passes the gate the cone and plane-side tests run over all points, inside the box or not; the box
+    contains the cone, so for two boxes that both do, the mapped sets differ only in calls that hold no point of the smaller box.
+    `map_triangles`, `map_bound` and `force_fill_bound` all come from this one box.
+
+    A translation that lies in the anchor plane has no height (`len_h == 0`, which the reference divides by): ValueError."""
+
+    def __init__(self, seal_config, config_path=None):
+        super().__init__(seal_config)
+        v_translation = np.array(seal_config["translation"], dtype=np.float64)
+        len_translation = np.linalg.norm(v_translation, 2)
+        raw = np.asarray(seal_config["raw"], dtype=np.float64).reshape(-1, 3)
+        v_anchor = raw.mean(0)
+        radius = float(seal_config["radius"])
+        plane_point, normal = best_fit_plane(raw)
+        v_translated_anchor = v_anchor + v_translation
+        v_projected_translated_anchor = v_translated_anchor - ((v_translated_anchor - plane_point) @ normal) * normal
+        v_offset = v_projected_translated_anchor - v_anchor
+        v_h = v_projected_translated_anchor - v_translated_anchor          # = -(translation . n) n: the same for either sign of n
+        len_h = np.linalg.norm(v_h, 2)
+        if not len_h > 1e-9 * len_translation:
+            raise ValueError("the anchor's translation lies in the plane of its `raw` points (len_h == 0): there is no height to deform along")
+        sphere = uv_sphere_points(radius * 1.1) + v_anchor
+        self.to_vertices, to_center = oriented_box(np.vstack([sphere, v_anchor + 1.1 * v_translation, sphere - 0.1 * v_translation]))
+        self.map_triangles = torch.from_numpy(self.to_vertices[_BOX_FACES])
+        self.map_data = {
+            "force_fill_bound": _bounds(self.to_vertices),
+            "map_bound": _bounds(self.to_vertices),
+            "pose_center": to_center,
+            "pose_radius": len_translation * 10,
+            "v_anchor": v_anchor,
+            "v_offset": v_offset,
+            "v_h": v_h,
+            "len_h": len_h,
+            "radius": radius,
+            "scale": seal_config["scale"],
+            "map_source": True,         # the reference's flag for pretraining (:512-513), NOT a bbox `mapSource` redirect: nothing here reads it
+        }
+        if "hsv" in seal_config:
+            self.map_data["hsv"] = seal_config["hsv"]
+        if "rgb" in seal_config:
+            self.map_data["rgb"] = seal_config["rgb"]
+            self.map_data["rgb_light_offset"] = seal_config.get("rgbLightOffset", 0)
+        self.map_data_conversion(force=True)
+
+    def _native_map_args(self, md, f32, cfl):
+        return dict(v_anchor=cfl(f32(md["v_anchor"])), v_offset=cfl(f32(md["v_offset"])), v_h=cfl(f32(md["v_h"])), scale=cfl(f32(md["scale"])),
+                    len_h=float(np.float32(md["len_h"])), radius=float(np.float32(md["radius"])))
+
+    @torch.no_grad()
+    def map_to_origin_(self, points, dirs):
+        """In-place `map_to_origin` on the sample buffers (CUDA fp32 contiguous) -> bool mask [M]; `sdn_seal_anchor_map` of csrc/seal.hip.
+        Every slot of the buffers is a sample of the call.  `dirs` are left as they are, as in the reference."""
+        from sdn_backend import lib, check, ptr, stream
+        a = self._native_args(points.device)
+        M = points.shape[0]
+        mask = torch.empty(M, dtype=torch.uint8, device=points.device)
+        check(lib.sdn_seal_anchor_map(ptr(points), ptr(dirs), M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"], a["v_anchor"],
+                                      a["v_offset"], a["v_h"], a["len_h"], a["radius"], a["scale"], a["scratch"].data_ptr() + 16, ptr(mask),
+                                      None, None, None, stream()), "seal_anchor_map")
+        return mask.view(torch.bool)
+
+    @torch.no_grad()
+    def map_to_origin(self, points, dirs=None):
+        """-> (points', dirs, mask): the points of the affected cone taken back to the undeformed content.  CUDA fp32 inputs take the
+        HIP kernel (on copies, as the reference returns copies); everything else the torch restatement below."""
+        if self._native_ok(points, dirs):
+            self.map_data_conversion(points)
+            p, d = points.clone(), dirs.clone()
+            return p, d, self.map_to_origin_(p, d)
+        return self._map_to_origin_torch(points, dirs)
+
+    @torch.no_grad()
+    def _map_to_origin_torch(self, points, dirs=None):
+        """seal_utils.py:522-578, statement by statement."""
+        with torch.autocast(points.device.type if points.device.type != "cpu" else "cpu", enabled=False):
+            self.map_data_conversion(points)
+            md = self.map_data
+            map_mask = self.map_mask(points)
+            if not map_mask.any():
+                return points, dirs, map_mask
+            projected_points = project_points(md["v_h"], md["v_anchor"], points)
+            v_points_to_plane = projected_points - points
+            points_plane_dist = torch.norm(v_points_to_plane, 2, 1)
+            offset_scale = points_plane_dist.unsqueeze(1) / md["len_h"]
+            scaled_offset = offset_scale * md["v_offset"]
+            projected_offset_points = projected_points - scaled_offset
+            pop_anchor_dist = torch.norm(projected_offset_points - md["v_anchor"], 2, 1)
+            is_points_in_affected_cone = torch.logical_and(
+                pop_anchor_dist <= md["radius"], points_plane_dist / (md["radius"] - pop_anchor_dist) < md["len_h"] / md["radius"] * 1.1)
+            is_points_in_valid_side = v_points_to_plane @ md["v_h"] > 0
+            valid_mask = torch.logical_and(is_points_in_affected_cone, is_points_in_valid_side)      # (not ANDed with map_mask)
+            valid_points_plane_dist = points_plane_dist[valid_mask]
+            v_map = -((md["len_h"] - valid_points_plane_dist) / 10)[None].T @ md["v_h"][None] / md["len_h"]
+            mapped_points = projected_offset_points[valid_mask] - v_map
+            mapped_points = (mapped_points - md["v_anchor"]) * md["scale"] + md["v_anchor"]
+            points_copy = points.clone()
+            points_copy[valid_mask] = mapped_points
+            return points_copy, dirs, valid_mask
+
+
 def get_seal_mapper(seal_config, config_path=None):
-    """seal_utils.py:581-592 for the mapper type built here."""
+    """seal_utils.py:581-592 for the mapper types built here."""
     if seal_config.get("type") == "bbox":
         return SealBBoxMapper(seal_config, config_path)
-    raise NotImplementedError(f"seal mapper type {seal_config.get('type')!r} (brush / anchor mappers need trimesh + pytorch3d mesh fitting)")
+    if seal_config.get("type") == "anchor":
+        return SealAnchorMapper(seal_config, config_path)
+    raise NotImplementedError(f"seal mapper type {seal_config.get('type')!r} (the brush mapper needs trimesh + pytorch3d + open3d mesh fitting)")
 
 
 @torch.no_grad()
