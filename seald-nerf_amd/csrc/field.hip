@@ -38,12 +38,11 @@
 #include "sdn_internal.h"
 #include "cell_points.h"
 #include "grid_common.h"
-#include "sh_eval.h"
+#include "field_f16_net.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace sdn_f16;
 
 #ifdef SDN_STAMPS
 // Diagnostic build only (make diag; the product library has no stamp): raw shader-clock stamps of k_field_f16, stored as they are taken
@@ -59,117 +58,12 @@ __device__ unsigned long long g_field_stamps[kStampWGs * 2 * 32];
 #define FSTAMP(k) ((void)0)
 #endif
 
-// fragment (1 KiB block) indices inside the packed weight buffer
-constexpr int kBlkD0 = 0;                 // 4 Mt x 4 ks
-constexpr int kBlkD1 = kBlkD0 + 16;       // 6 layers x (4 Mt x 8 ks)
-constexpr int kBlkD7 = kBlkD1 + 6 * 32;   // 1 Mt x 8 ks
-constexpr int kBlkS0 = kBlkD7 + 8;        // 2 Mt x 2 ks
-constexpr int kBlkS1 = kBlkS0 + 4;        // 1 Mt x 4 ks
-constexpr int kBlkC0 = kBlkS1 + 4;        // 2 Mt x 2 ks
-constexpr int kBlkC1 = kBlkC0 + 4;        // 2 Mt x 4 ks
-constexpr int kBlkC2 = kBlkC1 + 8;        // 1 Mt x 4 ks
-constexpr int kBlkTotal = kBlkC2 + 4;     // 240
-static_assert(kBlkTotal - kBlkD7 == 32, "the tail stage must be exactly one 32 KiB buffer");
-
 constexpr int kStageBytes = 32768;
 constexpr int kWaves = 8;                 // waves per workgroup, 32 points each; two workgroups per CU = 4 waves per SIMD
 constexpr int kPointsPerWG = 32 * kWaves;
 
-// tiled-grid level constants (D = 3, align_corners = false), host-precomputed: gridencoder.cu:66-84,138-139
-struct TiledLevels {
-    uint32_t offset[16];  // first row of the level
-    uint32_t s1[16];      // row stride of +1 in y (0 if the dimension is dropped: stride > rows)
-    uint32_t s2[16];      // row stride of +1 in z (0 if dropped)
-    uint32_t hsize[16];   // rows in the level
-    uint32_t mask[16];    // hsize - 1 if hsize is a power of two (wrapping level), else 0xFFFFFFFF (dense level)
-    float scale[16];
-};
-
-struct FieldArgs {
-    const float *xyzs;        // [M,3]
-    const float *dirs;        // [M,3]
-    const uint32_t *live_idx; // [<=M] slot indices to evaluate, or nullptr = all M slots
-    const uint32_t *live_count;
-    const int32_t *state;     // device-driven loop: the count is live_count[SdnLoopRecord::iteration] (one counter per iteration), else nullptr
-    uint32_t M;
-    const unsigned char *weights;  // kBlkTotal KiB, fragment order
-    const float *bias0;       // [128] time-encoding contribution to the first deform layer
-    const __half *table;      // grid embeddings, fp16 [rows, 2]
-    float *sigmas;            // [M]
-    float *rgbs;              // [M,3]
-    float bound;
-    float inv_2bound;         // 1 / (2 bound) if that is a power of two (the division is then an exact multiplication), else 0
-    float density_scale;
-    int zero_deform;          // bit f: frame f is at t == 0, the canonical frame (dnerf/network.py:140-141); a single frame uses bit 0
-    const uint8_t *slot_frame;  // frame group: frame of every sample slot (selects bias0 + 128 f and bit f of zero_deform), or nullptr
-    // density-grid query (CELLS variant): the points are jittered centres of occupancy-grid cells, built in the kernel
-    const float *cell_noise;  // [count,3] uniform [0,1) by list position, or nullptr = counter-based generator on cell_seed
-    uint32_t cell_seed;
-    float cell_inv;           // 1 / (grid_size - 1) in fp32: torch divides a tensor by a host scalar as a multiplication by its reciprocal
-    float cell_span;          // bound_cas - half_grid   (dnerf/renderer.py:484-488)
-    float cell_half;          // half_grid = bound_cas / grid_size
-    uint32_t n_frames;        // rows of bias0 (frames of a frame group; 1 without slot_frame)
-    uint32_t pp_soft;         // persistent kernel: the workgroup count to stay within unless more workgroups save a whole round (0 = gridDim.x)
-};
-
 using sdn_cells::cell_uniform;
 using sdn_cells::compact_bits3;
-
-__device__ __forceinline__ f32x16 mfma(half8 a, half8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
-// accumulator tile -> the two B fragments (k-steps) it provides to the next layer
-// (the reference rounds the Linear output to fp16 and applies ReLU on the fp16 tensor: round first, then a packed max)
-template <bool RELU>
-__device__ __forceinline__ void acc_to_frags(const f32x16 &acc, half8 &f0, half8 &f1) {
-    #pragma unroll
-    for (int j = 0; j < 8; j++) {
-        f0[j] = (_Float16)acc[j];
-        f1[j] = (_Float16)acc[8 + j];
-    }
-    if (RELU) {
-        const half8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-        f0 = __builtin_elementwise_max(f0, zero);
-        f1 = __builtin_elementwise_max(f1, zero);
-    }
-}
-
-__device__ __forceinline__ float round_h(float v) { return (float)(_Float16)v; }
-
-// fp32 multiply with one operand taken straight from the low / high half of a packed fp16 pair (v_fma_mix_f32):
-//   mix_mul_*(w, h2) = w * float(h2.half)        as fma(w, half, -0)  -- identical to the rounded product for every input
-__device__ __forceinline__ float mix_mul_lo(float w, uint32_t h2) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[0,1,0]" : "=v"(r) : "v"(w), "v"(h2), "s"(-0.0f));
-    return r;
-}
-__device__ __forceinline__ float mix_mul_hi(float w, uint32_t h2) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(w), "v"(h2), "s"(-0.0f));
-    return r;
-}
-// sin(a) and cos(a) with one shared 3-term Cody-Waite reduction by pi (explicit FMAs: this file is built with -ffp-contract=off):
-// r = a - k pi in [-pi/2, pi/2], sin(a) = (-1)^k sin(r), cos(a) = (-1)^k cos(r); odd degree-9 / even degree-10 polynomials,
-// ~1.3e-7 absolute for |a| < ~1e4.  The standalone freq_encode kernel uses OCML sinf (<= 1 ulp); the two agree to ~1e-7, far below
-// the fp16 rounding the features get as MFMA operands.
-__device__ __forceinline__ void fast_sincos(float a, float &sn, float &cs) {
-    const float k = rintf(a * 0.31830988618379067f);
-    float r = __builtin_fmaf(-k, 3.140625f, a);
-    r = __builtin_fmaf(-k, 9.67502593994140625e-4f, r);
-    r = __builtin_fmaf(-k, 1.509957990978376e-7f, r);
-    const float r2 = r * r;
-    float p = __builtin_fmaf(r2, 2.6083159809786593e-6f, -1.9810690719168633e-4f);
-    p = __builtin_fmaf(p, r2, 8.3330785855650902e-3f);
-    p = __builtin_fmaf(p, r2, -1.6666659712791443e-1f);
-    const float s = __builtin_fmaf(r * r2, p, r);
-    float q = __builtin_fmaf(r2, -2.6051615e-07f, 2.4760495e-05f);
-    q = __builtin_fmaf(q, r2, -1.3888378e-03f);
-    q = __builtin_fmaf(q, r2, 4.1666638e-02f);
-    q = __builtin_fmaf(q, r2, -0.5f);
-    const float c = __builtin_fmaf(q, r2, 1.0f);
-    const int sign = ((int)k & 1) << 31;
-    sn = __int_as_float(__float_as_int(s) ^ sign);
-    cs = __int_as_float(__float_as_int(c) ^ sign);
-}
 
 // Stage `nbytes` (multiple of 4 KiB) of packed weights global -> LDS, all 256 threads, 16 B per lane per instruction.
 // One wave-instruction moves 1 KiB to a wave-uniform LDS base + lane * 16 (global_load_lds_dwordx4).
@@ -198,10 +92,6 @@ __device__ __forceinline__ void stage_wait_and_sync() {
     __syncthreads();
 }
 
-__device__ __forceinline__ half8 lds_frag(const unsigned char *buf, int blk, uint32_t lane) {
-    return *reinterpret_cast<const half8 *>(buf + (size_t)blk * 1024 + lane * 16);
-}
-
 // OCC = waves per SIMD the kernel is compiled for, LA = LDS fragment reads kept in flight ahead of the MFMAs of a hidden layer.
 //   <4, 2>: the throughput variant (128 VGPRs, two workgroups per CU) for launches that fill the chip;
 //   <2, 8>: the latency variant for launches of at most one workgroup per CU (the tail iterations of a frame, every iteration
@@ -218,6 +108,7 @@ __device__ __forceinline__ half8 lds_frag(const unsigned char *buf, int blk, uin
 //                phase is bound by the rate at which the texture-address unit takes divergent lane addresses (~1 per cycle and CU:
 //                64 gathers per point are as many cycles of that unit as the point's 240 MFMAs are of a matrix pipe), not by bytes:
 //                half the gathers, the same values into the same arithmetic.
+// The network's stages are field_f16_net.h's; what is written here is this kernel's schedule.
 constexpr int kLayoutRef = 0, kLayoutPad = 1, kLayoutQuad = 2;
 template <int OCC, int LA, bool CELLS, int LAYOUT>
 __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, TiledLevels lv) {
@@ -243,12 +134,8 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
         stamp_slot[17] = __builtin_amdgcn_s_getreg((31 << 11) | 20);    // HW_REG_XCC_ID
     }
 #endif
-    if (threadIdx.x < 16) {         // visible to everyone after the first stage barrier below
-        const uint32_t l = threadIdx.x;
-        s_lv[l][0] = make_uint4(lv.offset[l], lv.s1[l], lv.s2[l], lv.hsize[l]);
-        s_lv[l][1] = make_uint4(lv.mask[l], __float_as_uint(lv.scale[l]), 0u, 0u);
-    }
-    const uint32_t count = P.state ? P.live_count[sdn_loop(P.state)->iteration] : (P.live_idx ? *P.live_count : P.M);
+    levels_to_lds(s_lv, lv);        // visible to everyone after the first stage barrier below
+    const uint32_t count = live_points(P);
     if (blockIdx.x * (uint32_t)kPointsPerWG >= count) return;  // workgroup-uniform: nothing to do, no barrier touched
     const uint32_t n = lane & 31u, h = lane >> 5;
     const uint32_t i = blockIdx.x * (uint32_t)kPointsPerWG + wave * 32u + n;
@@ -277,59 +164,16 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
         d0 = P.dirs[(size_t)p * 3]; d1 = P.dirs[(size_t)p * 3 + 1]; d2 = P.dirs[(size_t)p * 3 + 2];
     }
 
-    // ---------------- deform layer 0: freq features as B fragments ----------------
-    // lane-half h owns (freq, dim) pairs 15h .. 15h+14 (sin and cos) plus x0,x1 (h = 0) / x2,pad (h = 1), i.e. the five octaves
-    // 2^(5h) .. 2^(5h+4) of every coordinate.  One sine / cosine pair per coordinate at the lane-half's base octave (shared range
-    // reduction, two short polynomials), the four higher octaves by angle doubling in fp32:  s' = 2 s c,  c' = 1 - 2 s^2  -- 6
-    // polynomial evaluations + 48 multiply-adds per lane instead of 30 sine evaluations.  The doubling error (<= 2^4 x 1e-7) is two
-    // orders of magnitude below the fp16 rounding the features get as MFMA operands; kernel_freq (freqencoder.cu:52-56) evaluates
-    // cos as sin(x 2^f + float(pi/2)), which is itself off by up to 3e-5 at 2^9 -- the values here are the closer to the exact ones.
+    // ---------------- deform layer 0: freq features, the frame's bias row as the initial accumulator ----------------
     half8 bf[8];
     {
-        const float xs[3] = {x0, x1, x2};
-        const float fscale = h ? 32.0f : 1.0f;
-        float sv[5][3], cv[5][3];
-        #pragma unroll
-        for (int dd = 0; dd < 3; dd++) {
-            // (v_sin_f32 / v_cos_f32 on revolutions here measured no faster and leave 1.6 % of the fp16 features off the exactly rounded
-            //  value against 0.14 % for this pair and 0.40 % for the reference's own float form: profiles/r04_field_valu_diet.txt)
-            fast_sincos(xs[dd] * fscale, sv[0][dd], cv[0][dd]);
-            #pragma unroll
-            for (int f = 1; f < 5; f++) {
-                const float sp = sv[f - 1][dd], cp = cv[f - 1][dd];
-                const float s2 = sp + sp;                         // (2 s) c and 1 - (2 s) s: the same roundings as 2 (s c) and 1 - 2 s^2
-                sv[f][dd] = s2 * cp;
-                cv[f][dd] = __builtin_fmaf(-s2, sp, 1.0f);
-            }
-        }
-        #pragma unroll
-        for (int s = 0; s < 4; s++) {
-            #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const int q = s * 8 + j;
-                float v;
-                if (q < 30) {
-                    const int pr = q >> 1, f = pr / 3, dd = pr % 3;
-                    v = (q & 1) ? cv[f][dd] : sv[f][dd];
-                } else if (q == 30) {
-                    v = h ? x2 : x0;
-                } else {
-                    v = h ? 0.0f : x1;
-                }
-                bf[s][j] = (_Float16)v;
-            }
-        }
+        float sv0[3], cv0[3];
+        freq_base(x0, x1, x2, h, sv0, cv0);
+        freq_operand(x0, x1, x2, h, sv0, cv0, bf);
     }
     f32x16 acc[4];
     const uint32_t frame = P.slot_frame ? P.slot_frame[p] : 0u;   // kernel-uniform condition
-    {
-        const float *__restrict__ b0 = P.bias0 + 128u * frame;
-        #pragma unroll
-        for (int mt = 0; mt < 4; mt++) {
-            #pragma unroll
-            for (int r = 0; r < 16; r++) acc[mt][r] = b0[32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h];
-        }
-    }
+    bias_rows(P.bias0 + 128u * frame, h, acc);
     // Wave priority follows the phase.  All vector instructions of a SIMD share one issue port and the arbiter prefers the oldest
     // wave, so a co-resident workgroup that is in its VALU-only grid phase starves a younger one's MFMAs completely (measured:
     // the second workgroup of a CU made no progress until the first had retired -- two tiles took 28 + 23 us, not ~35).  An MFMA
@@ -367,14 +211,7 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
             const half8 a = ring[i % LA];
             if (i + LA < 32) ring[i % LA] = lds_frag(cur, ((i + LA) & 3) * 8 + ((i + LA) >> 2), lane);
             if ((i & 7) == 1 && (i >> 3) < kStageBytes / 1024 / kWaves) stage_piece(refill_src, other, i >> 3, wave, lane);
-            if (ks == 0) {
-                f32x16 z;
-                #pragma unroll
-                for (int r = 0; r < 16; r++) z[r] = 0.0f;
-                acc[mt] = mfma(a, bf[0], z);
-            } else {
-                acc[mt] = mfma(a, bf[ks], acc[mt]);
-            }
+            acc[mt] = mfma(a, bf[ks], ks == 0 ? zero_tile() : acc[mt]);
         }
         // pin the interleaving the look-ahead needs (left alone, the scheduler sinks every read to just before its MFMA to save
         // registers, and each MFMA then waits out a full LDS round trip): LA reads, then MFMA / read alternating
@@ -398,83 +235,21 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
     stage_wait_and_sync();  // tail stage (D7 | S0 | S1 | C0 | C1 | C2) resident in buffer 1
     FSTAMP(10);
     const unsigned char *tail = s_w1;
-    constexpr int tD7 = 0, tS0 = kBlkS0 - kBlkD7, tS1 = kBlkS1 - kBlkD7, tC0 = kBlkC0 - kBlkD7, tC1 = kBlkC1 - kBlkD7, tC2 = kBlkC2 - kBlkD7;
 
-    // ---------------- deform layer 7 (128 -> 3) ----------------
     float u[3];
-    {
-        f32x16 o;
-        #pragma unroll
-        for (int r = 0; r < 16; r++) o[r] = 0.0f;
-        #pragma unroll
-        for (int ks = 0; ks < 8; ks++) o = mfma(lds_frag(tail, tD7 + ks, lane), bf[ks], o);
-        // rows 0..2 = registers 0..2 of lane-half 0; broadcast to both halves
-        float df[3];
-        #pragma unroll
-        for (int c = 0; c < 3; c++) df[c] = __shfl(round_h(o[c]), (int)n, 64);
-        const float xs[3] = {x0, x1, x2};
-        #pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float xd = ((P.zero_deform >> frame) & 1) ? xs[c] : xs[c] + df[c];
-            // GridEncoder.forward (grid.py:149): (x + bound) / (2 bound); for 2 bound a power of two the quotient is the exact product
-            u[c] = P.inv_2bound != 0.0f ? (xd + P.bound) * P.inv_2bound : (xd + P.bound) / (2 * P.bound);
-        }
-    }
+    grid_coords(deform_d7(tail, bf, lane), lane, x0, x1, x2, (P.zero_deform >> frame) & 1, P, u);
     __builtin_amdgcn_s_setprio(0);
     FSTAMP(11);
     // ---------------- grid encode: lane-half h evaluates levels 8h .. 8h+7 ----------------
-    half8 gf[2];
-    uint32_t gfw[2][4];   // the same 2 x 8 halfs as packed pairs
+    uint32_t gfw[2][4];   // 8 levels x 2 features as packed pairs
     {
-        const bool oob = (u[0] < 0) | (u[0] > 1) | (u[1] < 0) | (u[1] > 1) | (u[2] < 0) | (u[2] > 1);
+        const bool oob = out_of_grid(u);
         const unsigned char *__restrict__ table_bytes = reinterpret_cast<const unsigned char *>(P.table);
-        // Per level: cell coordinates, fractions and the row of the cell's low corner.  The level's constants come from the LDS copy made
-        // at kernel start (two 16-byte reads per level instead of six per-lane selects between kernarg values, which the compiler turns
-        // into six per-lane global loads).
-        //   pos = u scale + 0.5 >= 0.5 for every point that is not zeroed as out of range: the truncating conversion IS floor, and
-        //   v_fract_f32 returns pos - floor(pos), which is exact in fp32 -- the reference's `pos -= (float)pos_grid` (gridencoder.cu:147-151);
-        //   rows: cell coordinates <= 2049 and strides <= 2049^2 < 2^24: the low 32 bits of the 24 x 24-bit products are the uint32
-        //   products of get_grid_index (gridencoder.cu:66-84), wrap-around included (v_mad_u32_u24, not the quarter-rate v_mul_lo_u32);
-        //   `index % hashmap_size` without a division: capped levels have a power-of-two row count (AND); dense levels hold every
-        //   (res+1)^3 corner, so an in-range point never wraps.
+        // per level: the constants from their LDS copy, the cell (field_f16_net.h) and the row of its low corner -- row 0 for a point outside
         struct LevelCell { uint32_t offset, s1, s2, hsize, mask, base; };
-        auto level_cell = [&](int li, float (&fr)[3]) {
+        auto cell_of = [&](int li, float (&fr)[3]) {
             const uint4 k0 = s_lv[8 * h + li][0], k1 = s_lv[8 * h + li][1];
-            LevelCell c;
-            c.offset = k0.x; c.s1 = k0.y; c.s2 = k0.z; c.hsize = k0.w; c.mask = k1.x;
-            const float scale = __uint_as_float(k1.y);
-            uint32_t pg[3];
-            #pragma unroll
-            for (int d = 0; d < 3; d++) {
-                const float q = u[d] * scale + 0.5f;
-                pg[d] = (uint32_t)q;
-                fr[d] = __builtin_amdgcn_fractf(q);
-            }
-            c.base = oob ? 0u : pg[0] + __umul24(pg[1], c.s1) + __umul24(pg[2], c.s2);
-            return c;
-        };
-        // kernel_grid (gridencoder.cu:187-189), scalar_t = at::Half:  results[ch] += w * grid[index + ch]  is
-        //   t = Half(w * float(val));  results = Half(float(results) + float(t))
-        // -- the float product is converted to Half first (the only `Half += x` takes a Half).  The products come from
-        // v_fma_mix_f32 reading the fp16 halves of the gathered word in place (w * val as fma(w, val, -0): the individually
-        // rounded fp32 product), one v_cvt_pk_f16_f32 rounds both channels, and the Half + Half sum is ONE v_pk_add_f16:
-        // for two fp16 operands the fp16-rounded exact sum equals Half(fp32 sum) (24 >= 2 * 11 + 2 bits: no double-rounding
-        // case exists).  4 VALU instructions per corner for both channels.  `corner_bits(idx)` = the half2 of corner idx (bit d set:
-        // +1 along dimension d), in the reference's corner order.
-        auto interpolate = [&](const float (&fr)[3], auto corner_bits) {
-            typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-            half2v accv = {(_Float16)0.0f, (_Float16)0.0f};
-            #pragma unroll
-            for (uint32_t idx = 0; idx < 8; idx++) {
-                float w = 1;
-                #pragma unroll
-                for (uint32_t d = 0; d < 3; d++) w *= (idx & (1u << d)) ? fr[d] : 1 - fr[d];
-                const uint32_t bits = corner_bits(idx);
-                const half2v t = {(_Float16)mix_mul_lo(w, bits), (_Float16)mix_mul_hi(w, bits)};
-                accv = accv + t;
-            }
-            const uint32_t acc2 = __builtin_bit_cast(uint32_t, accv);
-            return oob ? 0u : acc2;
+            return LevelCell{k0.x, k0.y, k0.z, k0.w, k1.x, level_cell(k0, k1, u, fr, oob)};
         };
         #pragma unroll
         for (int lb = 0; lb < 8 / kGridBatch; lb++) {
@@ -485,7 +260,7 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
                 uint4 quads[kGridBatch][2];
                 #pragma unroll
                 for (int lq = 0; lq < kGridBatch; lq++) {
-                    const LevelCell c = level_cell(lb * kGridBatch + lq, pos[lq]);
+                    const LevelCell c = cell_of(lb * kGridBatch + lq, pos[lq]);
                     const uint32_t r0 = c.base & c.mask, r1 = (c.base + c.s2) & c.mask;
                     // (uniform 64-bit base + 32-bit byte offset: the host refuses tables of 2^28 blocks or more)
                     __builtin_memcpy(&quads[lq][0], table_bytes + ((c.offset + r0) << 4), 16);
@@ -494,10 +269,8 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
                 #pragma unroll
                 for (int lq = 0; lq < kGridBatch; lq++) {
                     const int li = lb * kGridBatch + lq;
-                    gfw[li >> 2][li & 3] = interpolate(pos[lq], [&](uint32_t idx) {
-                        const uint4 &q = quads[lq][idx >> 2];
-                        return (idx & 3u) == 0u ? q.x : ((idx & 3u) == 1u ? q.y : ((idx & 3u) == 2u ? q.z : q.w));
-                    });
+                    const uint32_t feat = interp_corners(pos[lq], [&](uint32_t idx) { return quad_corner(quads[lq], idx); });
+                    gfw[li >> 2][li & 3] = oob ? 0u : feat;
                 }
             } else {
                 // The x and x+1 corners of a (y, z) corner pair are neighbouring table rows, so one 8-byte gather fetches both:
@@ -506,7 +279,7 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
                 uint32_t wrapbits = 0;   // bit 4 lq + c: that gather's x corner is the last row of a capped level (x+1 wraps to row 0)
                 #pragma unroll
                 for (int lq = 0; lq < kGridBatch; lq++) {
-                    const LevelCell lc = level_cell(lb * kGridBatch + lq, pos[lq]);
+                    const LevelCell lc = cell_of(lb * kGridBatch + lq, pos[lq]);
                     #pragma unroll
                     for (uint32_t c = 0; c < 4; c++) {
                         const uint32_t row0 = (lc.base + ((c & 1u) ? lc.s1 : 0u) + ((c & 2u) ? lc.s2 : 0u)) & lc.mask;
@@ -536,7 +309,8 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
                 #pragma unroll
                 for (int lq = 0; lq < kGridBatch; lq++) {
                     const int li = lb * kGridBatch + lq;
-                    gfw[li >> 2][li & 3] = interpolate(pos[lq], [&](uint32_t idx) { return (idx & 1u) ? pairs[lq][idx >> 1].y : pairs[lq][idx >> 1].x; });
+                    const uint32_t feat = interp_corners(pos[lq], [&](uint32_t idx) { return (idx & 1u) ? pairs[lq][idx >> 1].y : pairs[lq][idx >> 1].x; });
+                    gfw[li >> 2][li & 3] = oob ? 0u : feat;
                 }
             }
             // keep the batches apart: hoisting the next batch's index math and gathers above this batch's interpolation doubles the
@@ -544,92 +318,23 @@ __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, Til
             if (lb + 1 < 8 / kGridBatch) __builtin_amdgcn_sched_barrier(0);
         }
     }
-
-    #pragma unroll
-    for (int q = 0; q < 2; q++) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        gf[q] = __builtin_bit_cast(half8, (u32x4){gfw[q][0], gfw[q][1], gfw[q][2], gfw[q][3]});
-    }
     FSTAMP(12);
-    // ---------------- sigma net: 32 -> 64 (ReLU) -> 16 ----------------
-    f32x16 s0[2];
-    #pragma unroll
-    for (int mt = 0; mt < 2; mt++) {
-        #pragma unroll
-        for (int r = 0; r < 16; r++) s0[mt][r] = 0.0f;
-        #pragma unroll
-        for (int ks = 0; ks < 2; ks++) s0[mt] = mfma(lds_frag(tail, tS0 + mt * 2 + ks, lane), gf[ks], s0[mt]);
-    }
-    half8 sf[4];
-    acc_to_frags<true>(s0[0], sf[0], sf[1]);
-    acc_to_frags<true>(s0[1], sf[2], sf[3]);
-    f32x16 hv;
-    #pragma unroll
-    for (int r = 0; r < 16; r++) hv[r] = 0.0f;
-    #pragma unroll
-    for (int ks = 0; ks < 4; ks++) hv = mfma(lds_frag(tail, tS1 + ks, lane), sf[ks], hv);
-    // h[0] (lane-half 0, register 0) is the density logit; trunc_exp = exp in fp32 of the fp16 value
-    // (v_exp_f32 on h log2(e): 1 ulp of the hardware exponential plus |h| 2^-24 from the product -- the reference's own operators use the
-    //  fast intrinsics of their platform here (__expf), and sigma feeds a compositing sum that is compared at 1e-4 / fp16 distance)
-    const float sigma = P.density_scale * __builtin_amdgcn_exp2f(round_h(hv[0]) * 1.4426950408889634f);
+    half8 gf[2];
+    grid_operand(gfw, gf);
+    const f32x16 hv = sigma_net(tail, gf, lane);
+    const float sigma = density(hv, P.density_scale);
     if constexpr (CELLS) {
         if (h == 0 && valid) P.sigmas[p] = sigma;   // duplicates in the list: any one of them wins, as with tmp_grid[indices] = sigmas
         return;
     }
     FSTAMP(13);
-    // ---------------- colour net: [SH(16) ++ geo_feat(15)] -> 64 -> 64 -> 3 ----------------
-    half8 cf[2], dummy;
-    acc_to_frags<false>(hv, cf[0], dummy);  // registers 0..7 of every lane = h[0..15]; column of h[0] is zero in the packed weights
-    {
-        float sh[16];
-        float *nul = nullptr;
-        sdn_sh::sh_eval<4, false>(d0, d1, d2, sh, nul, nul, nul);
-        #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            float lo = sh[j], hi = sh[8 + j];
-            // pin both candidates in VGPRs: otherwise the select of two array elements becomes one dynamically indexed
-            // load and the whole array is demoted to LDS
-            asm volatile("" : "+v"(lo), "+v"(hi));
-            cf[1][j] = (_Float16)(h ? hi : lo);
-        }
-    }
-    f32x16 c0[2];
-    #pragma unroll
-    for (int mt = 0; mt < 2; mt++) {
-        #pragma unroll
-        for (int r = 0; r < 16; r++) c0[mt][r] = 0.0f;
-        #pragma unroll
-        for (int ks = 0; ks < 2; ks++) c0[mt] = mfma(lds_frag(tail, tC0 + mt * 2 + ks, lane), cf[ks], c0[mt]);
-    }
-    half8 c1f[4];
-    acc_to_frags<true>(c0[0], c1f[0], c1f[1]);
-    acc_to_frags<true>(c0[1], c1f[2], c1f[3]);
+    half8 cf[2] = {geo_operand(hv), sh_operand(d0, d1, d2, h)}, c2f[4];
     f32x16 c1[2];
-    #pragma unroll
-    for (int mt = 0; mt < 2; mt++) {
-        #pragma unroll
-        for (int r = 0; r < 16; r++) c1[mt][r] = 0.0f;
-        #pragma unroll
-        for (int ks = 0; ks < 4; ks++) c1[mt] = mfma(lds_frag(tail, tC1 + mt * 4 + ks, lane), c1f[ks], c1[mt]);
-    }
-    half8 c2f[4];
-    acc_to_frags<true>(c1[0], c2f[0], c2f[1]);
-    acc_to_frags<true>(c1[1], c2f[2], c2f[3]);
-    f32x16 co;
-    #pragma unroll
-    for (int r = 0; r < 16; r++) co[r] = 0.0f;
-    #pragma unroll
-    for (int ks = 0; ks < 4; ks++) co = mfma(lds_frag(tail, tC2 + ks, lane), c2f[ks], co);
+    colour_hidden(tail, cf, lane, c1);
+    relu_frags(c1, c2f);
+    const f32x16 co = colour_out(tail, c2f, lane);
     FSTAMP(14);
-    if (h == 0 && valid) {
-        P.sigmas[p] = sigma;
-        #pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float logit = round_h(co[c]);
-            // torch.sigmoid on fp16: fp32 math, fp16 result
-            P.rgbs[(size_t)p * 3 + c] = round_h(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(logit * -1.4426950408889634f)));
-        }
-    }
+    if (h == 0 && valid) store_sigma_rgb(P, p, sigma, co);
     FSTAMP(15);
 }
 
@@ -724,6 +429,17 @@ static int fill_field_args(FieldArgs &a, TiledLevels &lv, const FieldCall &f) {
     return 0;
 }
 
+// One-tile-per-workgroup launch: the table layout x the variant (small: the latency variant, at most one workgroup per CU).  A
+// reference-layout table (the public entry point with a caller's own table) has one variant only -- with the wrap bookkeeping the
+// throughput variant does not fit 128 VGPRs without spilling; the derived layouts are the product path -- and no density query.
+template <bool CELLS>
+static void launch_tile(int layout, bool small, uint32_t wgs, const FieldArgs &a, const TiledLevels &lv, hipStream_t st) {
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(wgs), dim3(64 * kWaves), 0, st, a, lv); };
+    if (layout == kLayoutQuad) small ? go(k_field_f16<2, 8, CELLS, kLayoutQuad>) : go(k_field_f16<4, 2, CELLS, kLayoutQuad>);
+    else if (layout == kLayoutPad) small ? go(k_field_f16<2, 8, CELLS, kLayoutPad>) : go(k_field_f16<4, 2, CELLS, kLayoutPad>);
+    else if constexpr (!CELLS) go(k_field_f16<2, 8, false, kLayoutRef>);
+}
+
 // launch used by both the C entry point and the device-driven render loop (render.hip)
 int field_forward_f16(const FieldCall &f, hipStream_t st) {
     TiledLevels lv;
@@ -777,17 +493,7 @@ int field_forward_f16(const FieldCall &f, hipStream_t st) {
         hipLaunchKernelGGL(k_field_pp_f16, dim3(pairs < grid ? pairs : grid), dim3(64 * kPPWaves), 0, st, a, lv);
         return sdn_launch_status();
     }
-    if (layout == kLayoutQuad) {
-        if (small) hipLaunchKernelGGL((k_field_f16<2, 8, false, kLayoutQuad>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
-        else hipLaunchKernelGGL((k_field_f16<4, 2, false, kLayoutQuad>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
-    } else if (layout == kLayoutPad) {
-        if (small) hipLaunchKernelGGL((k_field_f16<2, 8, false, kLayoutPad>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
-        else hipLaunchKernelGGL((k_field_f16<4, 2, false, kLayoutPad>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
-    } else {
-        // reference-layout table (the public entry point with a caller's own table): one variant only -- with the wrap bookkeeping
-        // the throughput variant does not fit 128 VGPRs without spilling; the derived layouts are the product path
-        hipLaunchKernelGGL((k_field_f16<2, 8, false, kLayoutRef>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
-    }
+    launch_tile<false>(layout, small, wgs, a, lv, st);
     return sdn_launch_status();
 }
 
@@ -803,13 +509,7 @@ int field_cells_f16(const FieldCells &q, hipStream_t st) {
     const uint32_t wgs = sdn_div_up(q.f.M, (uint32_t)kPointsPerWG);
     const int layout = table_layout(q.f.offsets_host);
     if (layout == kLayoutRef) return SDN_E_UNSUPPORTED;   // the density query is only built for the derived layouts
-    if (layout == kLayoutQuad) {
-        if (wgs <= 256u) hipLaunchKernelGGL((k_field_f16<2, 8, true, kLayoutQuad>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
-        else hipLaunchKernelGGL((k_field_f16<4, 2, true, kLayoutQuad>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
-    } else {
-        if (wgs <= 256u) hipLaunchKernelGGL((k_field_f16<2, 8, true, kLayoutPad>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
-        else hipLaunchKernelGGL((k_field_f16<4, 2, true, kLayoutPad>), dim3(wgs), dim3(64 * kWaves), 0, st, a, lv);
-    }
+    launch_tile<true>(layout, wgs <= 256u, wgs, a, lv, st);
     return sdn_launch_status();
 }
 

@@ -1,5 +1,5 @@
-// Persistent two-set ("ping-pong") form of the fused field kernel (included by field.hip inside its anonymous namespace; same arithmetic,
-// same packed weights, same QUAD table -- outputs bit-identical to k_field_f16).
+// Persistent two-set ("ping-pong") form of the fused field kernel (included by field.hip inside its anonymous namespace; the same stages
+// of field_f16_net.h, same packed weights, same QUAD table -- outputs bit-identical to k_field_f16).
 //
 // Why: k_field_f16 gives every wave the whole chain  point -> freq features -> 7 wide layers -> grid gathers -> small nets  and lets
 // two workgroups per CU overlap by chance.  Its in-kernel stamps (profiles/r04_field_phase_stamps_*.jsonl) show a workgroup spending
@@ -114,12 +114,8 @@ __global__ void __launch_bounds__(64 * kPPWaves) k_field_pp_f16(FieldArgs P, Til
     uint32_t pp_stamp_k = 0;
     PPSTAMP();
 #endif
-    if (threadIdx.x < 16) {
-        const uint32_t l = threadIdx.x;
-        s_lv[l][0] = make_uint4(lv.offset[l], lv.s1[l], lv.s2[l], lv.hsize[l]);
-        s_lv[l][1] = make_uint4(lv.mask[l], __float_as_uint(lv.scale[l]), 0u, 0u);
-    }
-    const uint32_t count = P.state ? P.live_count[sdn_loop(P.state)->iteration] : (P.live_idx ? *P.live_count : P.M);
+    levels_to_lds(s_lv, lv);
+    const uint32_t count = live_points(P);
     const uint32_t n_tiles = (count + kPPTile - 1u) / kPPTile;
     if (blockIdx.x >= n_tiles) return;                                   // workgroup-uniform, before any barrier
     // G workgroups share the tiles (the launch is sized before the live count is known).  Optional (pp_soft bit 31 clear): the fewest
@@ -157,7 +153,6 @@ __global__ void __launch_bounds__(64 * kPPWaves) k_field_pp_f16(FieldArgs P, Til
     }
     const uint32_t n = lane & 31u, h = lane >> 5;
     const unsigned char *__restrict__ table_bytes = reinterpret_cast<const unsigned char *>(P.table);
-    constexpr int tD7 = 0, tS0 = kBlkS0 - kBlkD7, tS1 = kBlkS1 - kBlkD7, tC0 = kBlkC0 - kBlkD7, tC1 = kBlkC1 - kBlkD7, tC2 = kBlkC2 - kBlkD7;
 
     half8 bfA[8], bfB[8];        // operand fragments, alternating between layers
     #pragma unroll
@@ -185,20 +180,11 @@ __global__ void __launch_bounds__(64 * kPPWaves) k_field_pp_f16(FieldArgs P, Til
         __builtin_amdgcn_s_setprio(1);
         const unsigned char *wsrc = P.weights;
         auto no_piece = [&](int) {};
-        auto zero_init = [&](int) { f32x16 z; for (int r = 0; r < 16; r++) z[r] = 0.0f; return z; };
-        // slot 0: D0 (4 k-steps), resident buffer, nothing to refill.  Initial accumulator of output tile mt: the bias rows of the
-        // point's frame, register r <-> feature 32 mt + 8 (r >> 2) + 4 h + (r & 3)
-        const uint32_t frame = s_pt[wave][n].w >> 28;
-        f32x16 bias_rows[4];
-        #pragma unroll
-        for (int mt = 0; mt < 4; mt++) {
-            #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float4 v = *reinterpret_cast<const float4 *>(&s_bias[frame][32 * mt + 8 * q + 4 * h]);
-                bias_rows[mt][4 * q] = v.x; bias_rows[mt][4 * q + 1] = v.y; bias_rows[mt][4 * q + 2] = v.z; bias_rows[mt][4 * q + 3] = v.w;
-            }
-        }
-        auto bias_init = [&](int mt) { return bias_rows[mt]; };
+        auto zero_init = [&](int) { return zero_tile(); };
+        // slot 0: D0 (4 k-steps), resident buffer, nothing to refill; from the bias row of the point's frame
+        f32x16 bias[4];
+        bias_rows(s_bias[s_pt[wave][n].w >> 28], h, bias);
+        auto bias_init = [&](int mt) { return bias[mt]; };
         pp_wide_layer<4, 2, 0, false>(bfA, bfB, [&](int blk) { return lds_frag(s_d0, blk, lane); }, no_piece, bias_init);
         slot_barrier();
         // slots 1..6: layer l reads ring (l - 1) % 3 and refills ring (l + 1) % 3 with the stage two uses ahead
@@ -236,62 +222,47 @@ __global__ void __launch_bounds__(64 * kPPWaves) k_field_pp_f16(FieldArgs P, Til
     // 16 gathers of a point are spread over four chunks (a CU takes ~1 divergent lane address per cycle: 8 waves x 6 gathers x 64 lanes
     // are one slot's worth of that unit) and at most five levels' blocks are in registers at a time.  The chunks' own MFMAs (D7, sigma
     // net, colour net: dependent chains) run at a HIGHER priority than the X set's streams -- the X waves wait for this set at every
-    // barrier anyway.
+    // barrier anyway.  The stages themselves are field_f16_net.h's, the ones k_field_f16 calls.
     // (has_tail / has_head are COMPILE-TIME: with run-time flags every chunk is a conditional block of its own and the compiler sinks a
     //  chunk's arithmetic into the later block that first uses the result -- level 0's sixteen products waited, spilled, for chunk 5)
+    // Pins (`asm volatile("" : "+v"(..))` behind a stage): a pure value first used chunks later is otherwise placed next to that use when
+    // the block is linearised, and what it was computed from waits for it in scratch.
+    auto pin = [&](half8 &f) {
+        u32x4 w = __builtin_bit_cast(u32x4, f);
+        asm volatile("" : "+v"(w));
+        f = __builtin_bit_cast(half8, w);
+    };
     auto y_period = [&](auto has_tail_c, uint32_t tail_tile, auto has_head_c, uint32_t head_tile) __attribute__((always_inline)) {
         constexpr bool has_tail = decltype(has_tail_c)::value, has_head = decltype(has_head_c)::value;
         float u[3] = {0, 0, 0};
-        bool oob = false;
         uint32_t keep = 0xFFFFFFFFu;     // 0 for a point outside [0, 1]^3: its rows collapse to row 0 and its features are zeroed (kernel_grid's early out)
         float fr[8][3];
         uint4 quads[8][2];
         uint32_t gfw[2][4];
-        half8 cf[2];
+        half8 cf[2], c2f[4];
         float sigma = 0;
         float d0 = 0, d1 = 0, d2 = 0;
-        uint32_t tail_p = 0, zero_def = 0;
+        uint32_t tail_p = 0;
         uint32_t head_p = 0, head_frame = 0;
         float hx0 = 0, hx1 = 0, hx2 = 0;
+        float sv0[3] = {0, 0, 0}, cv0[3] = {0, 0, 0};
         // cells of levels [first, last) of the lane-half and their gathers (QUAD table: the z and z + 1 blocks of a cell)
         auto cells_and_gathers = [&](int first, int last) {
             #pragma unroll
             for (int li = first; li < last; li++) {
                 const uint4 k0 = s_lv[8 * h + li][0], k1 = s_lv[8 * h + li][1];
-                const float scale = __uint_as_float(k1.y);
-                uint32_t pg[3];
+                const uint32_t base = level_cell(k0, k1, u, fr[li], false) & keep;
                 #pragma unroll
-                for (int d = 0; d < 3; d++) {
-                    const float q = u[d] * scale + 0.5f;
-                    pg[d] = (uint32_t)q;
-                    fr[li][d] = __builtin_amdgcn_fractf(q);
-                    asm volatile("" : "+v"(fr[li][d]));          // (pinned, as the features below)
-                }
-                const uint32_t base = (pg[0] + __umul24(pg[1], k0.y) + __umul24(pg[2], k0.z)) & keep;
+                for (int d = 0; d < 3; d++) asm volatile("" : "+v"(fr[li][d]));
                 __builtin_memcpy(&quads[li][0], table_bytes + ((k0.x + (base & k1.x)) << 4), 16);
                 __builtin_memcpy(&quads[li][1], table_bytes + ((k0.x + ((base + k0.z) & k1.x)) << 4), 16);
                 __builtin_amdgcn_sched_barrier(0);   // level by level: interleaving the levels' index arithmetic only lengthens live ranges (spills at 128 registers)
             }
         };
-        // interpolation of levels [first, last) (kernel_grid's per-corner half roundings, see k_field_f16)
         auto interp_levels = [&](int first, int last) {
             #pragma unroll
             for (int li = first; li < last; li++) {
-                typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-                half2v accv = {(_Float16)0.0f, (_Float16)0.0f};
-                #pragma unroll
-                for (uint32_t idx = 0; idx < 8; idx++) {
-                    float w = 1;
-                    #pragma unroll
-                    for (uint32_t d = 0; d < 3; d++) w *= (idx & (1u << d)) ? fr[li][d] : 1 - fr[li][d];
-                    const uint4 &q = quads[li][idx >> 2];
-                    const uint32_t bits = (idx & 3u) == 0u ? q.x : ((idx & 3u) == 1u ? q.y : ((idx & 3u) == 2u ? q.z : q.w));
-                    const half2v t = {(_Float16)mix_mul_lo(w, bits), (_Float16)mix_mul_hi(w, bits)};
-                    accv = accv + t;
-                }
-                uint32_t feat = __builtin_bit_cast(uint32_t, accv) & keep;
-                // pinned HERE: a pure value first used chunks later is otherwise placed next to that use when the block is linearised,
-                // and its sixteen products wait for it in scratch
+                uint32_t feat = interp_corners(fr[li], [&](uint32_t idx) { return quad_corner(quads[li], idx); }) & keep;
                 asm volatile("" : "+v"(feat));
                 gfw[li >> 2][li & 3] = feat;
                 __builtin_amdgcn_sched_barrier(0);   // (as above: one level's 8 weights and 16 products at a time)
@@ -307,27 +278,15 @@ __global__ void __launch_bounds__(64 * kPPWaves) k_field_pp_f16(FieldArgs P, Til
         if (has_tail) {
             const uint4 rec = s_pt[wave][n];
             tail_p = rec.w & 0x0FFFFFFFu;
-            zero_def = (P.zero_deform >> (rec.w >> 28)) & 1u;
+            const uint32_t zero_def = (P.zero_deform >> (rec.w >> 28)) & 1u;
             d0 = P.dirs[(size_t)tail_p * 3]; d1 = P.dirs[(size_t)tail_p * 3 + 1]; d2 = P.dirs[(size_t)tail_p * 3 + 2];
-            const float xs[3] = {__uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z)};
             __builtin_amdgcn_s_setprio(3);
-            f32x16 o;
-            #pragma unroll
-            for (int r = 0; r < 16; r++) o[r] = 0.0f;
-            #pragma unroll
-            for (int ks = 0; ks < 8; ks++) o = mfma(lds_frag(s_tail, tD7 + ks, lane), bfB[ks], o);
+            const f32x16 o = deform_d7(s_tail, bfB, lane);
             __builtin_amdgcn_s_setprio(0);
-            float df[3];
+            grid_coords(o, lane, __uint_as_float(rec.x), __uint_as_float(rec.y), __uint_as_float(rec.z), zero_def, P, u);
             #pragma unroll
-            for (int c = 0; c < 3; c++) df[c] = __shfl(round_h(o[c]), (int)n, 64);
-            #pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const float xd = zero_def ? xs[c] : xs[c] + df[c];
-                u[c] = P.inv_2bound != 0.0f ? (xd + P.bound) * P.inv_2bound : (xd + P.bound) / (2 * P.bound);
-                asm volatile("" : "+v"(u[c]));
-            }
-            oob = (u[0] < 0) | (u[0] > 1) | (u[1] < 0) | (u[1] > 1) | (u[2] < 0) | (u[2] > 1);
-            keep = oob ? 0u : 0xFFFFFFFFu;
+            for (int c = 0; c < 3; c++) asm volatile("" : "+v"(u[c]));
+            keep = out_of_grid(u) ? 0u : 0xFFFFFFFFu;
             asm volatile("" : "+v"(keep));
         }
         slot_barrier();
@@ -338,22 +297,8 @@ __global__ void __launch_bounds__(64 * kPPWaves) k_field_pp_f16(FieldArgs P, Til
         }
         if (has_tail) {
             cells_and_gathers(0, 4);
-            // ... and the SH basis of the direction (operand k-step 1 of the colour net's first layer)
-            float sh[16];
-            float *nul = nullptr;
-            sdn_sh::sh_eval<4, false>(d0, d1, d2, sh, nul, nul, nul);
-            #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                float lo = sh[j], hi = sh[8 + j];
-                asm volatile("" : "+v"(lo), "+v"(hi));
-                cf[1][j] = (_Float16)(h ? hi : lo);
-            }
-            {
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                u32x4 w = __builtin_bit_cast(u32x4, cf[1]);
-                asm volatile("" : "+v"(w));
-                cf[1] = __builtin_bit_cast(half8, w);
-            }
+            cf[1] = sh_operand(d0, d1, d2, h);
+            pin(cf[1]);
         }
         slot_barrier();
         // chunk 2
@@ -368,139 +313,46 @@ __global__ void __launch_bounds__(64 * kPPWaves) k_field_pp_f16(FieldArgs P, Til
             cells_and_gathers(6, 8);
         }
         slot_barrier();
-        // chunk 4: the last three levels; sigma net 32 -> 64 (ReLU) -> 16, density
+        // chunk 4
         if (has_tail) {
             interp_levels(5, 8);
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
             half8 gf[2];
-            #pragma unroll
-            for (int q = 0; q < 2; q++) gf[q] = __builtin_bit_cast(half8, (u32x4){gfw[q][0], gfw[q][1], gfw[q][2], gfw[q][3]});
+            grid_operand(gfw, gf);
             __builtin_amdgcn_s_setprio(3);
-            f32x16 s0[2];
-            #pragma unroll
-            for (int mt = 0; mt < 2; mt++) {
-                #pragma unroll
-                for (int r = 0; r < 16; r++) s0[mt][r] = 0.0f;
-                #pragma unroll
-                for (int ks = 0; ks < 2; ks++) s0[mt] = mfma(lds_frag(s_tail, tS0 + mt * 2 + ks, lane), gf[ks], s0[mt]);
-            }
-            half8 sf[4];
-            acc_to_frags<true>(s0[0], sf[0], sf[1]);
-            acc_to_frags<true>(s0[1], sf[2], sf[3]);
-            f32x16 hv;
-            #pragma unroll
-            for (int r = 0; r < 16; r++) hv[r] = 0.0f;
-            #pragma unroll
-            for (int ks = 0; ks < 4; ks++) hv = mfma(lds_frag(s_tail, tS1 + ks, lane), sf[ks], hv);
+            const f32x16 hv = sigma_net(s_tail, gf, lane);
             __builtin_amdgcn_s_setprio(0);
-            sigma = P.density_scale * __builtin_amdgcn_exp2f(round_h(hv[0]) * 1.4426950408889634f);
+            sigma = density(hv, P.density_scale);
             asm volatile("" : "+v"(sigma));
-            half8 dummy;
-            acc_to_frags<false>(hv, cf[0], dummy);
-            {
-                u32x4 w = __builtin_bit_cast(u32x4, cf[0]);
-                asm volatile("" : "+v"(w));
-                cf[0] = __builtin_bit_cast(half8, w);
-            }
+            cf[0] = geo_operand(hv);
+            pin(cf[0]);
         }
         slot_barrier();
-        // chunk 5: colour net, first two layers  [SH(16) ++ geo_feat(15)] -> 64 -> 64
-        half8 c2f[4];
+        // chunk 5
         if (has_tail) {
-            __builtin_amdgcn_s_setprio(3);
-            f32x16 c0[2];
-            #pragma unroll
-            for (int mt = 0; mt < 2; mt++) {
-                #pragma unroll
-                for (int r = 0; r < 16; r++) c0[mt][r] = 0.0f;
-                #pragma unroll
-                for (int ks = 0; ks < 2; ks++) c0[mt] = mfma(lds_frag(s_tail, tC0 + mt * 2 + ks, lane), cf[ks], c0[mt]);
-            }
-            half8 c1f[4];
-            acc_to_frags<true>(c0[0], c1f[0], c1f[1]);
-            acc_to_frags<true>(c0[1], c1f[2], c1f[3]);
             f32x16 c1[2];
-            #pragma unroll
-            for (int mt = 0; mt < 2; mt++) {
-                #pragma unroll
-                for (int r = 0; r < 16; r++) c1[mt][r] = 0.0f;
-                #pragma unroll
-                for (int ks = 0; ks < 4; ks++) c1[mt] = mfma(lds_frag(s_tail, tC1 + mt * 4 + ks, lane), c1f[ks], c1[mt]);
-            }
+            __builtin_amdgcn_s_setprio(3);
+            colour_hidden(s_tail, cf, lane, c1);
             __builtin_amdgcn_s_setprio(0);
-            acc_to_frags<true>(c1[0], c2f[0], c2f[1]);
-            acc_to_frags<true>(c1[1], c2f[2], c2f[3]);
+            relu_frags(c1, c2f);
             #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                u32x4 w = __builtin_bit_cast(u32x4, c2f[k]);
-                asm volatile("" : "+v"(w));
-                c2f[k] = __builtin_bit_cast(half8, w);
-            }
+            for (int k = 0; k < 4; k++) pin(c2f[k]);
         }
-        float sv0[3] = {0, 0, 0}, cv0[3] = {0, 0, 0};
-        if (has_head) {      // ... and the base sines / cosines of the next tile's frequency features (the polynomial pair: a third of that work)
-            const float fscale = h ? 32.0f : 1.0f;
-            const float xs[3] = {hx0, hx1, hx2};
+        if (has_head) {      // (the polynomial pair: a third of the frequency features' work)
+            freq_base(hx0, hx1, hx2, h, sv0, cv0);
             #pragma unroll
-            for (int dd = 0; dd < 3; dd++) {
-                fast_sincos(xs[dd] * fscale, sv0[dd], cv0[dd]);
-                asm volatile("" : "+v"(sv0[dd]), "+v"(cv0[dd]));
-            }
+            for (int dd = 0; dd < 3; dd++) asm volatile("" : "+v"(sv0[dd]), "+v"(cv0[dd]));
         }
         slot_barrier();
-        // chunk 6: colour net's last layer 64 -> 3, stores; the next tile's frequency features -- the same expressions as k_field_f16's
-        // "deform layer 0" block -- and its record
+        // chunk 6
         if (has_tail) {
             __builtin_amdgcn_s_setprio(3);
-            f32x16 co;
-            #pragma unroll
-            for (int r = 0; r < 16; r++) co[r] = 0.0f;
-            #pragma unroll
-            for (int ks = 0; ks < 4; ks++) co = mfma(lds_frag(s_tail, tC2 + ks, lane), c2f[ks], co);
+            const f32x16 co = colour_out(s_tail, c2f, lane);
             __builtin_amdgcn_s_setprio(0);
-            const bool tail_valid = tail_tile * kPPTile + wv * 32u + n < count;
-            if (h == 0 && tail_valid) {
-                P.sigmas[tail_p] = sigma;
-                #pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const float logit = round_h(co[c]);
-                    P.rgbs[(size_t)tail_p * 3 + c] = round_h(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(logit * -1.4426950408889634f)));
-                }
-            }
+            if (h == 0 && tail_tile * kPPTile + wv * 32u + n < count) store_sigma_rgb(P, tail_p, sigma, co);
         }
-        if (has_head) {
-            const float x0 = hx0, x1 = hx1, x2 = hx2;
-            if (h == 0) s_pt[wave][n] = make_uint4(__float_as_uint(x0), __float_as_uint(x1), __float_as_uint(x2), head_p | (head_frame << 28));
-            float sv[5][3], cv[5][3];
-            #pragma unroll
-            for (int dd = 0; dd < 3; dd++) {
-                sv[0][dd] = sv0[dd]; cv[0][dd] = cv0[dd];
-                #pragma unroll
-                for (int f = 1; f < 5; f++) {
-                    const float sp = sv[f - 1][dd], cp = cv[f - 1][dd];
-                    const float s2 = sp + sp;
-                    sv[f][dd] = s2 * cp;
-                    cv[f][dd] = __builtin_fmaf(-s2, sp, 1.0f);
-                }
-            }
-            #pragma unroll
-            for (int s = 0; s < 4; s++) {
-                #pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int q = s * 8 + j;
-                    float v;
-                    if (q < 30) {
-                        const int pr = q >> 1, f = pr / 3, dd = pr % 3;
-                        v = (q & 1) ? cv[f][dd] : sv[f][dd];
-                    } else if (q == 30) {
-                        v = h ? x2 : x0;
-                    } else {
-                        v = h ? 0.0f : x1;
-                    }
-                    bfA[s][j] = (_Float16)v;
-                }
-            }
+        if (has_head) {      // the next tile's record for its X period and tail, and its D0 operand
+            if (h == 0) s_pt[wave][n] = make_uint4(__float_as_uint(hx0), __float_as_uint(hx1), __float_as_uint(hx2), head_p | (head_frame << 28));
+            freq_operand(hx0, hx1, hx2, h, sv0, cv0, bfA);
         }
         slot_barrier();
     };

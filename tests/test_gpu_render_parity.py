@@ -626,6 +626,79 @@ def test_quad_table_layout_is_the_padded_layout_bit_for_bit(small_scene):
         assert np.array_equal(got.view(np.uint16), want.view(np.uint16)), l
 
 
+def test_reference_table_layout_is_the_padded_layout_bit_for_bit(small_scene):
+    """A caller's own table in the reference's layout (level sizes multiples of 8, grid.py:118-127) through sdn_field_forward_f16 -- the
+    one kernel instance FusedField never launches: its (x, x+1) row pair is clamped into the level and a pair whose x corner is the
+    level's LAST row is patched afterwards (x+1 wraps to row 0) -- against the PADDED layout: sigma and rgb bit-identical.  The batch
+    holds points placed on the host in cells of the coarsest capped level whose low corner is that last row, or lies s1, s2 or s1 + s2
+    rows below it, so that each of the four corner pairs of a cell takes the patch path; that they do is asserted from the same index
+    arithmetic (get_grid_index, gridencoder.cu:66-84).  t = 0 is the canonical frame: the points reach the grid undeformed."""
+    import sdn_backend
+    from sdn_backend import check, ptr, stream
+    from dnerf_amd import fused
+    from dnerf_amd.bench_scene import _probe_points
+    sc = small_scene
+    enc = sc.model.encoder
+    fp = fused.FusedField(sc.model, 0.0, table_layout="pad")
+    assert fp.bound == 1.0
+    off = np.ascontiguousarray(enc.offsets.cpu().numpy().astype(np.int32))
+    assert all(int(off[l + 1] - off[l]) % 8 == 0 for l in range(16))              # announces the reference layout
+    S, H = np.float32(fp.S), np.float32(fp.H)
+
+    def level(l):
+        hs = int(off[l + 1] - off[l])
+        scale = np.exp2(np.float32(l) * S, dtype=np.float32) * H - np.float32(1.0)
+        res = int(np.ceil(np.float64(scale))) + 1
+        s1 = res + 1 if res + 1 <= hs else 0
+        s2 = (res + 1) ** 2 if s1 and (res + 1) ** 2 <= hs else 0
+        return hs, scale, res, s1, s2
+    lc = next(l for l in range(16) if (level(l)[2] + 1) ** 3 > level(l)[0])      # the coarsest capped level
+    hs, scale, res, s1, s2 = level(lc)
+    assert hs & (hs - 1) == 0 and s1 and s2
+    # cells (low corner pg, every coordinate of pg and pg + 1 inside the level) by the row of their low corner
+    g = np.arange(1, res - 1, dtype=np.int64)
+    pg = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    row = (pg[:, 0] + pg[:, 1] * s1 + pg[:, 2] * s2) % hs
+    rng = np.random.default_rng(23)
+    placed = []
+    for target in (hs - 1, hs - 1 - s1, hs - 1 - s2, hs - 1 - s1 - s2):
+        cells = pg[row == target]
+        assert cells.shape[0] > 0, target
+        for c in cells[:4]:
+            for _ in range(6):                                                    # q = u scale + 0.5 inside (pg + 0.1, pg + 0.9)
+                placed.append(2.0 * (c + rng.uniform(-0.4, 0.4, 3)) / np.float64(scale) - 1.0)
+    placed = np.asarray(placed, dtype=np.float32)
+    n = 2000
+    pts = _probe_points(sc.bitfield, n, 9) + rng.uniform(-0.01, 0.01, (n, 3)).astype(np.float32)
+    pts[: placed.shape[0]] = placed
+    # the kernel's arithmetic at level lc for the undeformed points: which gathers have the level's last row as their x corner
+    u = (pts + np.float32(1.0)) * np.float32(0.5)
+    q = u * scale + np.float32(0.5)
+    assert q.dtype == np.float32 and (u >= 0).all() and (u <= 1).all()
+    cell = q.astype(np.int64)
+    base = cell[:, 0] + cell[:, 1] * s1 + cell[:, 2] * s2
+    wraps = np.stack([(base + (c & 1) * s1 + (c >> 1) * s2) % hs == hs - 1 for c in range(4)], 1)
+    print("level", lc, "rows", hs, "wrapping gathers per corner pair", wraps.sum(0))
+    assert wraps.any(0).all(), wraps.sum(0)
+
+    x = torch.from_numpy(pts).cuda()
+    d = torch.from_numpy(rng.standard_normal((n, 3)).astype(np.float32)).cuda()
+    d = torch.nn.functional.normalize(d, dim=1).contiguous()
+    emb = enc.embeddings.detach().half().contiguous()
+    sig = torch.empty(n, dtype=torch.float32, device="cuda")
+    rgb = torch.empty(n, 3, dtype=torch.float32, device="cuda")
+    for t in (0.0, 0.5):
+        fp.set_time(t)
+        sig.fill_(-1.0); rgb.fill_(-1.0)
+        check(sdn_backend.lib.sdn_field_forward_f16(ptr(x, torch.float32, "xyzs"), ptr(d, torch.float32, "dirs"), ptr(None), ptr(None), n,
+                                                    ptr(fp.weights), ptr(fp.bias0), ptr(emb, torch.float16, "embeddings"), off.ctypes.data,
+                                                    fp.S, fp.H, fp.bound, fp.density_scale, fp.zero_deform, ptr(sig), ptr(rgb), stream()),
+              "field_forward_f16")
+        sp, cp = fp(x, d)
+        assert torch.equal(sig, sp) and torch.equal(rgb, cp), t
+        assert torch.isfinite(sig).all() and float(rgb.min()) >= 0 and float(rgb.max()) <= 1
+
+
 def test_persistent_two_set_field_kernel_is_the_one_tile_kernel_bit_for_bit(small_scene):
     """Large launches of the fused field network take the persistent two-set kernel (csrc/field_pp.inc: one 16-wave workgroup per CU, the
     sets alternate between the wide layers and the vector-side work).  Same arithmetic in the same order: sigma and rgb are bit-identical
