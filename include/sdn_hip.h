@@ -586,6 +586,25 @@ int sdn_seal_modify_hsv(float *rgbs, const uint8_t *mask, uint32_t M, float dh, 
  * point: the same for any order of the samples.  scratch16: 16 bytes of device memory, 8-byte aligned (cleared by the call). */
 int sdn_seal_modify_rgb(float *rgbs, const uint8_t *mask, uint32_t M, float r, float g, float b, float light_offset, void *scratch16,
                         const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state, void *stream);
+/* The inference loop's schedule (dnerf/renderer.py:340-381) replayed on a whole-ray sample list -- march_rays_train's ray table `rays`
+ * [N,3] {ray, offset, count} with the sigmas [M] and deltas [M,2] of its samples -- without marching or evaluating anything again:
+ * slot_iter [M] i32 receives, for every sample slot, the iteration in which the loop marches that sample (n_step = max(min(N // n_alive,
+ * 8), 1) samples per alive ray and iteration; a ray leaves when compositing kills it -- the transmittance in front of a sample of the
+ * window is < T_thresh -- or fewer than n_step samples are left; the loop ends at max_steps steps), -1 for slots it never marches (behind
+ * the window a ray dies in, rays that do not fit M, the tail of the buffer); n_iter [1] i32 the number of iterations.  Slots behind a
+ * kill INSIDE a window carry the window's iteration: the loop marched and evaluated them.  ray_stop: [N,2] i32 of work space.
+ * One workgroup replays the loop: SDN_E_UNSUPPORTED for N > sdn_whole_rays_schedule_max_rays().  No host synchronisation. */
+uint32_t sdn_whole_rays_schedule_max_rays(void);
+int sdn_whole_rays_schedule(const int32_t *rays, const float *sigmas, const float *deltas, uint32_t M, uint32_t N, float T_thresh,
+                            uint32_t max_steps, int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter, void *stream);
+/* sdn_seal_modify_rgb for the one-pass renderer (march_rays_train -> field -> this call -> sdn_composite_whole_rays): the masked samples
+ * of rgbs [M,3] are tinted as the inference loop tints them, each by the mean V of the masked samples of ITS iteration of
+ * sdn_whole_rays_schedule (run by this call; ray_stop / slot_iter / n_iter as there) -- bit for bit the loop's colours.  scratch:
+ * 16 * (max_steps + 8) bytes of device memory, 8-byte aligned: {sum, count} per iteration (cleared by the call). */
+int sdn_seal_modify_rgb_whole_rays(float *rgbs, const uint8_t *mask, const int32_t *rays, const float *sigmas, const float *deltas,
+                                   uint32_t M, uint32_t N, float T_thresh, uint32_t max_steps, float r, float g, float b,
+                                   float light_offset, void *scratch, int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter,
+                                   void *stream);
 
 /* Read-back memory for the frame drivers: 32 bytes per ray group of coherent, device-mapped host memory.  When `host_snap`
  * comes from here the loop kernels publish every iteration's survivor count into it with one 64-bit system-scope store and

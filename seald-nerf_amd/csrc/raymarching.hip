@@ -908,20 +908,8 @@ __global__ void __launch_bounds__(256) k_composite_train_fwd(const float *__rest
     image[(size_t)index * 3] = r; image[(size_t)index * 3 + 1] = g; image[(size_t)index * 3 + 2] = b;
 }
 
-// One step of the inference compositing recurrence (raymarching.cu:862-887) on a ray's accumulators: the sample of density sigma, step
-// dt and colour c, whose parameter lies dt_after behind the previous one.  Returns T, the transmittance IN FRONT of the sample, for the
-// caller's stop test; the two early exits (dt == 0 before the step, T < T_thresh after it) stay with the callers.
-struct CompositeAcc { float t, weight_sum, d, r, g, b; };
-__device__ __forceinline__ float composite_step(CompositeAcc &a, float sigma, float dt, float dt_after, float cr, float cg, float cb) {
-    const float alpha = 1.0f - sdn_exp_cr(-sigma * dt);
-    const float T = 1 - a.weight_sum;
-    const float weight = alpha * T;
-    a.weight_sum += weight;
-    a.t += dt_after;
-    a.d += weight * a.t;
-    a.r += weight * cr; a.g += weight * cg; a.b += weight * cb;
-    return T;
-}
+// (CompositeAcc / composite_step, one step of the inference compositing recurrence: sdn_common.h -- the one-pass tint's schedule replay
+// in seal.hip finds a ray's termination sample with the same code)
 
 // The INFERENCE compositing arithmetic (kernel_composite_rays, raymarching.cu:819-905: transmittance as 1 - weights_sum, the stop
 // test on the transmittance IN FRONT of a sample, t running from the ray's near bound) over ALL samples of a ray at once, in the

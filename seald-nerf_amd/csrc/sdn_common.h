@@ -48,3 +48,18 @@ __device__ __forceinline__ uint64_t sdn_splitmix64(uint64_t seed, uint32_t i) {
 // double-rounding ties (~1e-9 of inputs); the compositing kernels are HBM/latency
 // bound, the fp64 polynomial is free next to their loads.
 __device__ __forceinline__ float sdn_exp_cr(float x) { return (float)exp((double)x); }
+
+// One step of the inference compositing recurrence (raymarching.cu:862-887) on a ray's accumulators: the sample of density sigma, step
+// dt and colour c, whose parameter lies dt_after behind the previous one.  Returns T, the transmittance IN FRONT of the sample, for the
+// caller's stop test; the two early exits (dt == 0 before the step, T < T_thresh after it) stay with the callers.
+struct CompositeAcc { float t, weight_sum, d, r, g, b; };
+__device__ __forceinline__ float composite_step(CompositeAcc &a, float sigma, float dt, float dt_after, float cr, float cg, float cb) {
+    const float alpha = 1.0f - sdn_exp_cr(-sigma * dt);
+    const float T = 1 - a.weight_sum;
+    const float weight = alpha * T;
+    a.weight_sum += weight;
+    a.t += dt_after;
+    a.d += weight * a.t;
+    a.r += weight * cr; a.g += weight * cg; a.b += weight * cb;
+    return T;
+}

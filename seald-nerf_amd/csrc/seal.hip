@@ -217,14 +217,17 @@ __device__ __forceinline__ void hsv_to_rgb(float h, float s, float v, float &o0,
 // integer: exact for the fp16- or fp32-valued colours of [0, 1] up to 2^-40 per sample and, above all, INDEPENDENT OF THE ORDER -- the
 // host-stepped loop and the device loop hold the same samples in different slots and must tint them by the same mean, bit for bit
 // (torch.mean's own fp32 pairwise order is library-defined; the two agree to ~1e-7, far inside the 1e-4 bar of the fixture test).
+__device__ __forceinline__ unsigned long long seal_rgb_fixed_v(const float *__restrict__ rgbs, uint32_t i) {
+    const float mx = fmaxf(rgbs[(size_t)i * 3], fmaxf(rgbs[(size_t)i * 3 + 1], rgbs[(size_t)i * 3 + 2]));
+    return (unsigned long long)((double)fminf(fmaxf(mx, 0.0f), 4.0f) * 1099511627776.0 + 0.5);
+}
 __global__ void __launch_bounds__(256) k_seal_rgb_sum(const float *__restrict__ rgbs, const uint8_t *__restrict__ mask, SealSlots L,
                                                       unsigned long long *__restrict__ acc) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long v = 0ull, c = 0ull;
     const uint32_t i = j < L.count() ? L.slot(j) : 0u;
     if (j < L.count() && mask[i]) {
-        const float mx = fmaxf(rgbs[(size_t)i * 3], fmaxf(rgbs[(size_t)i * 3 + 1], rgbs[(size_t)i * 3 + 2]));
-        v = (unsigned long long)((double)fminf(fmaxf(mx, 0.0f), 4.0f) * 1099511627776.0 + 0.5);
+        v = seal_rgb_fixed_v(rgbs, i);
         c = 1ull;
     }
     #pragma unroll
@@ -237,11 +240,10 @@ __global__ void __launch_bounds__(256) k_seal_rgb_sum(const float *__restrict__ 
         atomicAdd(&acc[1], c);
     }
 }
-// pass 2: hue and saturation of the target colour, brightness re-centred on it (seal_utils.py:769-775), -> rgb, in place
-__global__ void __launch_bounds__(256) k_seal_rgb_apply(float *__restrict__ rgbs, const uint8_t *__restrict__ mask, uint32_t M, float tr, float tg, float tb,
-                                                        float light_offset, const unsigned long long *__restrict__ acc) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M || !mask[i] || acc[1] == 0ull) return;      // (a masked slot outside the call's samples while none of them is masked: left alone)
+// pass 2: hue and saturation of the target colour, brightness re-centred on it (seal_utils.py:769-775), -> rgb, in place.  acc: the
+// {sum, count} pair of the call the slot belongs to
+__device__ __forceinline__ void seal_rgb_tint(float *__restrict__ rgbs, uint32_t i, float tr, float tg, float tb, float light_offset,
+                                              const unsigned long long *__restrict__ acc) {
     const float mean = (float)(((double)acc[0] / 1099511627776.0) / (double)acc[1]);
     float h, s, v, mh, ms, mv;
     rgb_to_hsv(rgbs[(size_t)i * 3], rgbs[(size_t)i * 3 + 1], rgbs[(size_t)i * 3 + 2], h, s, v);
@@ -250,6 +252,132 @@ __global__ void __launch_bounds__(256) k_seal_rgb_apply(float *__restrict__ rgbs
     float o0, o1, o2;
     hsv_to_rgb(mh, ms, nv, o0, o1, o2);
     rgbs[(size_t)i * 3] = o0; rgbs[(size_t)i * 3 + 1] = o1; rgbs[(size_t)i * 3 + 2] = o2;
+}
+__global__ void __launch_bounds__(256) k_seal_rgb_apply(float *__restrict__ rgbs, const uint8_t *__restrict__ mask, uint32_t M, float tr, float tg, float tb,
+                                                        float light_offset, const unsigned long long *__restrict__ acc) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M || !mask[i] || acc[1] == 0ull) return;      // (a masked slot outside the call's samples while none of them is masked: left alone)
+    seal_rgb_tint(rgbs, i, tr, tg, tb, light_offset, acc);
+}
+
+// ---- the tint of a WHOLE-RAY sample list (the one-pass renderer: march_rays_train's (offset, count) layout, every ray's samples up front) --
+// modify_rgb re-centres brightness on the mean V of the masked samples of ONE map_color call, and in the inference loop a call is one
+// iteration (SealDNeRF/renderer.py:271-272).  Which samples share an iteration follows from the sample counts, the sigmas and the
+// loop's rule n_step = max(min(N // n_alive, 8), 1) alone -- the tint changes colours, never which ray dies when -- so the loop's
+// schedule is replayed here after the one field launch, and the two tint passes run per iteration on the result.
+constexpr int32_t kNoIteration = -1;          // slot_iter of a slot the loop never marched (0xFF bytes: the call's memset writes it)
+constexpr uint32_t kScheduleBlock = 1024;     // the replay is ONE workgroup; each lane keeps up to kScheduleMaxPerLane rays in registers
+constexpr uint32_t kScheduleMaxPerLane = 16;
+
+// Phase A, one lane per ray: {index of the sample at which the loop kills the ray, number of samples}.  The kill is k_composite_rays':
+// the first sample whose transmittance IN FRONT of it (1 - weights_sum, accumulated by composite_step) is < T_thresh -- that sample is
+// still composited -- else the sample count.  A zero step length ends the ray's list (as in k_composite_whole_rays); a ray whose
+// samples did not fit the buffer has none (as there).
+__global__ void __launch_bounds__(256) k_whole_rays_stop(const float *__restrict__ sigmas, const float *__restrict__ deltas, const int32_t *__restrict__ rays,
+                                                         uint32_t M, uint32_t N, float T_thresh, int32_t *__restrict__ ray_stop) {
+    const uint32_t n = threadIdx.x + blockIdx.x * blockDim.x;
+    if (n >= N) return;
+    const uint32_t offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
+    uint32_t stop = 0, count = 0;
+    if (num_steps != 0 && (uint64_t)offset + num_steps <= (uint64_t)M) {
+        const float *s = sigmas + offset, *dl = deltas + (size_t)offset * 2;
+        CompositeAcc a = {0, 0, 0, 0, 0, 0};
+        stop = count = num_steps;
+        for (uint32_t step = 0; step < num_steps; step++) {
+            if (dl[0] == 0) { stop = count = step; break; }
+            if (composite_step(a, s[0], dl[0], dl[1], 0.0f, 0.0f, 0.0f) < T_thresh) { stop = step; break; }
+            s++; dl += 2;
+        }
+    }
+    ray_stop[n * 2] = (int32_t)stop;
+    ray_stop[n * 2 + 1] = (int32_t)count;
+}
+
+// Phase B, one workgroup: the loop of dnerf/renderer.py:340-381 on the rays' progress alone.  Per iteration: count the alive rays
+// (wave shuffles + LDS, two LDS rows used in turn so that one barrier per iteration is enough), n_step exactly as advance_record
+// (raymarching.hip) and the reference set it, every alive ray stamps the slots the marcher would have filled -- [pos, pos + n_step),
+// cut at its sample count, INCLUDING those behind a kill inside the window: the loop marched, evaluated and averaged them -- and dies
+// when k_composite_rays would have killed it: its stop sample lies in the window (for a ray without one, stop == count: fewer than
+// n_step samples were left).  Ends as the loop does: step >= max_steps, or nobody alive.
+template <uint32_t R>
+__global__ void __launch_bounds__(kScheduleBlock) k_whole_rays_schedule(const int32_t *__restrict__ rays, const int32_t *__restrict__ ray_stop, uint32_t N,
+                                                                        uint32_t max_steps, int32_t *__restrict__ slot_iter, int32_t *__restrict__ n_iter) {
+    __shared__ uint32_t s_alive[2][kScheduleBlock / 64];
+    uint32_t pos[R], stop[R], count[R], offset[R];
+    uint32_t alive = 0;                        // bit k: ray k * kScheduleBlock + threadIdx.x is alive
+    #pragma unroll
+    for (uint32_t k = 0; k < R; k++) {
+        const uint32_t n = k * kScheduleBlock + threadIdx.x;
+        pos[k] = 0; stop[k] = 0; count[k] = 0; offset[k] = 0;
+        if (n < N) {
+            offset[k] = (uint32_t)rays[n * 3 + 1];
+            stop[k] = (uint32_t)ray_stop[n * 2];
+            count[k] = (uint32_t)ray_stop[n * 2 + 1];
+            alive |= 1u << k;
+        }
+    }
+    uint32_t step = 0, it = 0;
+    while (true) {
+        uint32_t c = (uint32_t)__popc(alive);
+        #pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+        if ((threadIdx.x & 63u) == 0u) s_alive[it & 1u][threadIdx.x >> 6] = c;
+        __syncthreads();
+        uint32_t n_alive = 0;
+        #pragma unroll
+        for (uint32_t w = 0; w < kScheduleBlock / 64; w++) n_alive += s_alive[it & 1u][w];
+        if (step >= max_steps || n_alive == 0) break;          // workgroup-uniform
+        const uint32_t ns = N / n_alive;
+        const uint32_t n_step = ns > 8u ? 8u : (ns < 1u ? 1u : ns);
+        #pragma unroll
+        for (uint32_t k = 0; k < R; k++) {
+            if (alive & (1u << k)) {
+                const uint32_t end = min(pos[k] + n_step, count[k]);
+                for (uint32_t q = pos[k]; q < end; q++) slot_iter[(size_t)offset[k] + q] = (int32_t)it;
+                if (stop[k] < pos[k] + n_step) alive &= ~(1u << k);
+                else pos[k] += n_step;
+            }
+        }
+        step += n_step;
+        it++;
+    }
+    if (threadIdx.x == 0) n_iter[0] = (int32_t)it;
+}
+
+// pass 1 per iteration: acc[2 * it + {0, 1}] += {V, 1} of the masked slots of iteration it.  A wave's 64 slots span a few iterations:
+// it reduces one iteration at a time (that of its first pending lane) and adds one pair per iteration it holds.
+__global__ void __launch_bounds__(256) k_seal_rgb_sum_iter(const float *__restrict__ rgbs, const uint8_t *__restrict__ mask, const int32_t *__restrict__ slot_iter,
+                                                           uint32_t M, unsigned long long *__restrict__ acc) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t it = i < M ? slot_iter[i] : kNoIteration;
+    const bool in = it != kNoIteration && mask[i] != 0;
+    const unsigned long long mine = in ? seal_rgb_fixed_v(rgbs, i) : 0ull;
+    unsigned long long pending = __ballot(in ? 1 : 0);
+    while (pending != 0ull) {                                   // wave-uniform
+        const int32_t cur = __shfl(it, __ffsll((long long)pending) - 1, 64);
+        const bool now = in && it == cur;
+        unsigned long long v = now ? mine : 0ull, c = now ? 1ull : 0ull;
+        #pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            v += __shfl_down(v, off, 64);
+            c += __shfl_down(c, off, 64);
+        }
+        if ((threadIdx.x & 63u) == 0u) {
+            atomicAdd(&acc[2 * (size_t)cur], v);
+            atomicAdd(&acc[2 * (size_t)cur + 1], c);
+        }
+        pending &= ~__ballot(now ? 1 : 0);
+    }
+}
+// pass 2 per iteration: a masked slot is tinted by the mean of its own iteration
+__global__ void __launch_bounds__(256) k_seal_rgb_apply_iter(float *__restrict__ rgbs, const uint8_t *__restrict__ mask, const int32_t *__restrict__ slot_iter,
+                                                             uint32_t M, float tr, float tg, float tb, float light_offset,
+                                                             const unsigned long long *__restrict__ acc) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M || !mask[i]) return;
+    const int32_t it = slot_iter[i];
+    if (it == kNoIteration || acc[2 * (size_t)it + 1] == 0ull) return;
+    seal_rgb_tint(rgbs, i, tr, tg, tb, light_offset, acc + 2 * (size_t)it);
 }
 
 // color_utils.py:31-63 + seal_utils.py:747-758 on the masked samples, in place
@@ -374,6 +502,46 @@ int sdn_seal_modify_rgb(float *rgbs, const uint8_t *mask, uint32_t M, float r, f
     hipLaunchKernelGGL(k_seal_rgb_sum, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, (const float *)rgbs, mask, L, (unsigned long long *)scratch16);
     hipLaunchKernelGGL(k_seal_rgb_apply, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, rgbs, mask, M, r, g, b, light_offset,
                        (const unsigned long long *)scratch16);
+    return sdn_launch_status();
+}
+
+uint32_t sdn_whole_rays_schedule_max_rays(void) { return kScheduleBlock * kScheduleMaxPerLane; }
+
+// The inference loop's schedule for a whole-ray sample list: slot_iter[p] = the iteration of dnerf/renderer.py:340-381 in which the loop
+// marches sample slot p, -1 for a slot it never marches; n_iter[0] = its iteration count.  Three stream operations, no host
+// synchronisation.
+int sdn_whole_rays_schedule(const int32_t *rays, const float *sigmas, const float *deltas, uint32_t M, uint32_t N, float T_thresh, uint32_t max_steps,
+                            int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter, void *stream) {
+    if (!rays || !sigmas || !deltas || !ray_stop || !slot_iter || !n_iter || M == 0 || N == 0 || max_steps == 0) return SDN_E_BADARG;
+    if (N > kScheduleBlock * kScheduleMaxPerLane) return SDN_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(slot_iter, 0xFF, (size_t)M * sizeof(int32_t), st) != hipSuccess) return sdn_launch_status();
+    hipLaunchKernelGGL(k_whole_rays_stop, dim3(sdn_div_up(N, 256u)), dim3(256), 0, st, sigmas, deltas, rays, M, N, T_thresh, ray_stop);
+    const uint32_t per_lane = sdn_div_up(N, kScheduleBlock);
+    #define SDN_SCHEDULE(R) hipLaunchKernelGGL(k_whole_rays_schedule<R>, dim3(1), dim3(kScheduleBlock), 0, st, rays, (const int32_t *)ray_stop, N, max_steps, slot_iter, n_iter)
+    if (per_lane <= 1) SDN_SCHEDULE(1);
+    else if (per_lane <= 2) SDN_SCHEDULE(2);
+    else if (per_lane <= 4) SDN_SCHEDULE(4);
+    else if (per_lane <= 8) SDN_SCHEDULE(8);
+    else SDN_SCHEDULE(16);
+    #undef SDN_SCHEDULE
+    return sdn_launch_status();
+}
+
+// modify_rgb on a whole-ray sample list, in place, tinted as the inference loop tints it: sdn_whole_rays_schedule, then the two passes of
+// sdn_seal_modify_rgb per iteration.  scratch: 16 * (max_steps + 8) bytes, 8-byte aligned (cleared here).  Six stream operations.
+int sdn_seal_modify_rgb_whole_rays(float *rgbs, const uint8_t *mask, const int32_t *rays, const float *sigmas, const float *deltas, uint32_t M, uint32_t N,
+                                   float T_thresh, uint32_t max_steps, float r, float g, float b, float light_offset, void *scratch,
+                                   int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter, void *stream) {
+    if (M == 0 || N == 0) return 0;
+    if (!rgbs || !mask || !scratch || ((uintptr_t)scratch & 7u) != 0) return SDN_E_BADARG;
+    if (int rc = sdn_whole_rays_schedule(rays, sigmas, deltas, M, N, T_thresh, max_steps, ray_stop, slot_iter, n_iter, stream)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(scratch, 0, 16 * ((size_t)max_steps + 8), st) != hipSuccess) return sdn_launch_status();
+    hipLaunchKernelGGL(k_seal_rgb_sum_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, (const float *)rgbs, mask, (const int32_t *)slot_iter, M,
+                       (unsigned long long *)scratch);
+    hipLaunchKernelGGL(k_seal_rgb_apply_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, rgbs, mask, (const int32_t *)slot_iter, M, r, g, b, light_offset,
+                       (const unsigned long long *)scratch);
     return sdn_launch_status();
 }
 

@@ -940,6 +940,37 @@ class PipelinedDeviceLoop:
 
 
 
+def loop_schedule(counts, stops, max_steps=1024):
+    """The inference loop's schedule (dnerf/renderer.py:340-381) for rays whose samples are known up front: the specification of
+    phase B of `sdn_whole_rays_schedule` (csrc/seal.hip), in Python.
+
+    counts[r]: the number of samples of ray r; stops[r]: the index of the sample at which compositing kills it (the first one whose
+    transmittance in front is < T_thresh; that sample is still composited), or counts[r] if there is none.  Per iteration the loop
+    marches n_step = max(min(N // n_alive, 8), 1) samples of every alive ray -- all of the window that exist, also those behind a kill
+    inside it --, and a ray leaves when its stop sample lies in the window (without one: when fewer than n_step samples were left; a
+    ray without samples leaves in iteration 0).  It ends after max_steps steps or with no ray alive.
+
+    -> (ids, trace): ids, int32, the iteration of every sample, rays packed one after the other (ray r's samples start at
+    sum(counts[:r])), -1 for a sample the loop never marches; trace, the (n_alive, n_step) of every iteration."""
+    counts, stops = np.asarray(counts, dtype=np.int64), np.asarray(stops, dtype=np.int64)
+    N = counts.shape[0]
+    first = np.concatenate([[0], np.cumsum(counts)])
+    ids = np.full(int(first[-1]), -1, dtype=np.int32)
+    pos, alive = np.zeros(N, dtype=np.int64), np.ones(N, dtype=bool)
+    step, trace = 0, []
+    while step < max_steps and alive.any():
+        n_alive = int(alive.sum())
+        n_step = max(min(N // n_alive, 8), 1)
+        for r in np.nonzero(alive)[0]:
+            ids[first[r] + pos[r]: first[r] + min(pos[r] + n_step, counts[r])] = len(trace)
+        dies = alive & (stops < pos + n_step)
+        alive &= ~dies
+        pos[alive] += n_step
+        trace.append((n_alive, n_step))
+        step += n_step
+    return ids, trace
+
+
 class RayBatchRenderer:
     """A SMALL ray batch (a training batch's proxy render, SealDNeRF/utils.py:632-656; a preview; an error-map pass) rendered in one
     pass instead of through the iteration loop.
@@ -952,17 +983,28 @@ class RayBatchRenderer:
     the inference arithmetic: image and weights_sum are the loop's bit for bit, depth to fp32 rounding.  A seal mapper, if given,
     sits between marcher and field exactly as in the loop.  Cost: the samples behind a ray's termination point are evaluated too.
 
+    The rgb tint (`modify_rgb`) re-centres brightness on the mean of the masked samples of one loop ITERATION.  Which samples share an
+    iteration follows from the sample counts, the sigmas and the rule n_step = max(min(N // n_alive, 8), 1) -- colours never decide
+    when a ray dies -- so after the field launch `sdn_seal_modify_rgb_whole_rays` replays the loop's schedule on the device
+    (`loop_schedule` below states it in Python) and tints every masked sample by the mean of its own iteration: the loop's colours bit
+    for bit, six more stream operations, no read-back.  `mapSource` stays with the loops: its redirect moves samples, so it changes the
+    sigmas that decide the schedule that decides which calls redirect.
+
     `samples_per_ray` sizes the sample buffer (N * samples_per_ray slots); a batch that needs more loses its last rays -- `render(...,
     check=True)` reads the count back and raises, `overflowed()` does the same on demand."""
 
     def __init__(self, model, field, N, device, max_steps=1024, T_thresh=1e-2, dt_gamma=0.0, mapper=None, samples_per_ray=96):
         import sdn_backend as B
         B.require_device()
-        if mapper is not None and ("rgb" in mapper.map_data or mapper.redirects_source):
-            # (the loop's iterations are the unit both options look at -- modify_rgb's mean brightness, map_to_origin's early return:
-            #  one pass over all samples would tint and redirect differently from the reference's loop.  The anchor mapper's early return
+        if mapper is not None and mapper.redirects_source:
+            # (map_to_origin's early return looks at one loop iteration's samples, and the redirect it gates changes their sigmas, which
+            #  decide the iterations: nothing to replay after the fact.  The tint is replayed, see above.  The anchor mapper's early return
             #  is no such case: its box contains its cone, so an iteration without a sample in the box holds no sample to map either)
-            raise NotImplementedError("mapSource / rgb tint depend on the loop's iterations: use render_frame / DeviceLoop for such edits")
+            raise NotImplementedError("mapSource depends on the loop's iterations: use render_frame / DeviceLoop for such edits")
+        tint = mapper is not None and "rgb" in mapper.map_data
+        if tint and int(N) > int(B.lib.sdn_whole_rays_schedule_max_rays()):
+            raise NotImplementedError(f"the rgb tint's schedule replay holds at most {int(B.lib.sdn_whole_rays_schedule_max_rays())} rays "
+                                      f"(N = {N}): render larger batches with DeviceLoop")
         self.model, self.field, self.N, self.device, self.mapper = model, field, int(N), torch.device(device), mapper
         self.max_steps, self.T_thresh, self.dt_gamma = int(max_steps), float(T_thresh), float(dt_gamma)
         M = self.N * int(samples_per_ray)
@@ -981,6 +1023,16 @@ class RayBatchRenderer:
         self.image = torch.empty(self.N, 3, dtype=f32, device=dev)
         self.image_out, self.depth_out = torch.empty(self.N, 3, dtype=f32, device=dev), torch.empty(self.N, dtype=f32, device=dev)
         self._aabb = model.aabb_infer.detach().to(dev, f32).contiguous()
+        self._tint = None
+        if tint:
+            # the tint's work buffers belong to THIS renderer (as a DeviceLoop owns its 32 bytes): {sum, count} per loop iteration --
+            # cleared on the stream by every render --, {stop sample, count} per ray, the iteration of every sample slot, the iteration count
+            from types import SimpleNamespace
+            i32 = torch.int32
+            self._tint = SimpleNamespace(rays=self.rays, sigmas=None, deltas=self.deltas, N=self.N, T_thresh=self.T_thresh, max_steps=self.max_steps,
+                                         scratch=torch.zeros(16 * (self.max_steps + 8), dtype=torch.uint8, device=dev),
+                                         ray_stop=torch.zeros(self.N, 2, dtype=i32, device=dev),
+                                         slot_iter=torch.full((self.M,), -1, dtype=i32, device=dev), n_iter=torch.zeros(1, dtype=i32, device=dev))
 
     @torch.no_grad()
     def render(self, rays_o, rays_d, time, bg_color=1.0, check=False):
@@ -1002,7 +1054,10 @@ class RayBatchRenderer:
         torch.clamp(self.counter[:1], max=self.M, out=self.count)
         mask = self.mapper.map_to_origin_(self.xyzs, self.dirs) if self.mapper is not None else None
         sigmas, rgbs = self.field(self.xyzs, self.dirs, live_idx=self.identity, live_count=self.count)
-        if mask is not None:
+        if self._tint is not None:
+            self._tint.sigmas = sigmas
+            self.mapper.map_color_(rgbs, mask, whole_rays=self._tint)
+        elif mask is not None:
             self.mapper.map_color_(rgbs, mask)
         B.check(lib.sdn_composite_whole_rays(B.ptr(sigmas), B.ptr(rgbs), B.ptr(self.deltas), B.ptr(self.rays), B.ptr(self.nears), self.M, self.N,
                                              self.T_thresh, B.ptr(self.weights_sum), B.ptr(self.depth), B.ptr(self.image), st), "composite_whole_rays")

@@ -222,9 +222,14 @@ class SealMapper:
         raise NotImplementedError()
 
     @torch.no_grad()
-    def map_color_(self, rgbs, mask):
+    def map_color_(self, rgbs, mask, whole_rays=None):
         """In-place `map_color` of the masked samples (seal_utils.py:48-57: the hsv modification, then the rgb tint): HIP kernels on CUDA
-        fp32 buffers, the torch restatement otherwise (and for an `image` modification, which the mappers of this build do not carry)."""
+        fp32 buffers, the torch restatement otherwise (and for an `image` modification, which the mappers of this build do not carry).
+
+        whole_rays: the buffers hold EVERY sample of a ray batch (march_rays_train's layout; `RayBatchRenderer`), not one loop iteration's:
+        the record of that list -- rays [N,3], sigmas, deltas, N, T_thresh, max_steps and the renderer's work buffers scratch, ray_stop,
+        slot_iter, n_iter (`sdn_seal_modify_rgb_whole_rays`) -- so that the tint re-centres each sample on the mean brightness of the
+        loop iteration it would have been part of.  Only the tint looks at it; there is no torch restatement of that form."""
         if rgbs.is_cuda and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and "image" not in self.map_data:
             from sdn_backend import lib, check, ptr, stream
             m8 = mask.view(torch.uint8)
@@ -234,8 +239,18 @@ class SealMapper:
             if "rgb" in self.map_data:
                 a = self._native_args(rgbs.device)
                 c = a["rgb"]
-                check(lib.sdn_seal_modify_rgb(ptr(rgbs), ptr(m8), rgbs.shape[0], c[0], c[1], c[2], a["rgb_light_offset"], ptr(a["scratch"]),
-                                              None, None, None, stream()), "seal_modify_rgb")
+                if whole_rays is not None:
+                    w = whole_rays
+                    check(lib.sdn_seal_modify_rgb_whole_rays(ptr(rgbs), ptr(m8), ptr(w.rays, torch.int32, "rays"), ptr(w.sigmas, torch.float32, "sigmas"),
+                                                             ptr(w.deltas, torch.float32, "deltas"), rgbs.shape[0], w.N, w.T_thresh, w.max_steps,
+                                                             c[0], c[1], c[2], a["rgb_light_offset"], ptr(w.scratch), ptr(w.ray_stop, torch.int32, "ray_stop"),
+                                                             ptr(w.slot_iter, torch.int32, "slot_iter"), ptr(w.n_iter, torch.int32, "n_iter"), stream()),
+                          "seal_modify_rgb_whole_rays")
+                else:
+                    check(lib.sdn_seal_modify_rgb(ptr(rgbs), ptr(m8), rgbs.shape[0], c[0], c[1], c[2], a["rgb_light_offset"], ptr(a["scratch"]),
+                                                  None, None, None, stream()), "seal_modify_rgb")
+        elif whole_rays is not None and "rgb" in self.map_data:
+            raise NotImplementedError("the whole-ray rgb tint is a device kernel (CUDA fp32 contiguous colours)")
         elif bool(mask.any()):
             rgbs[mask] = self.map_color(None, None, rgbs[mask]).to(rgbs.dtype)
         return rgbs

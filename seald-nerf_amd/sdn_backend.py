@@ -56,6 +56,8 @@ PROTOTYPES = {
     "sdn_seal_bbox_map_source": [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sdn_seal_anchor_map": [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sdn_seal_modify_rgb": [_vp, _vp, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "sdn_whole_rays_schedule": [_vp, _vp, _vp, _u32, _u32, _f32, _u32, _vp, _vp, _vp, _vp],
+    "sdn_seal_modify_rgb_whole_rays": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
     "sdn_field_forward_f16": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp],
     "sdn_field_forward_f32": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
     "sdn_field_forward_f32x3": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
@@ -161,6 +163,7 @@ PROTOTYPES_U32 = {
     "sdn_field_weight_blocks": [],
     "sdn_field_weight_floats_f32": [],
     "sdn_cull_grid_bytes": [],
+    "sdn_whole_rays_schedule_max_rays": [],
 }
 PROTOTYPES_U64 = {
     "sdn_march_rays_train_scratch_bytes": [_u32, _u32],
