@@ -402,6 +402,7 @@ typedef struct SdnLoopRecord {
  * except `tris`), for SdnRenderCtx.seal.  `kind` (at the end) selects the mapper; the box test and the colour fields serve both. */
 #define SDN_SEAL_BBOX 0
 #define SDN_SEAL_ANCHOR 1
+#define SDN_SEAL_BRUSH 2
 typedef struct SdnSealBox {
     float bounds[24];          /* n_bounds x {lo xyz, hi xyz} */
     uint32_t n_bounds, n_tris;
@@ -424,6 +425,17 @@ typedef struct SdnSealBox {
     uint32_t kind;
     float v_anchor[3], v_offset[3], v_h[3], len_h, radius;
 } SdnSealBox;
+
+/* The brush mapper's own arguments (sdn_seal_brush_map), for SdnRenderCtx.seal_brush: read when SdnSealBox::kind == SDN_SEAL_BRUSH.
+ * The SdnSealBox then carries the bounds, test_dir, the colour fields and `tris` in the BRUSH layout, [n_tris][16] (see
+ * sdn_seal_brush_map); tinv, rinv, scale, center, the mapSource and the anchor fields are not read.  Host memory except `border`. */
+typedef struct SdnSealBrush {
+    float normal_expand[3], center[3];
+    float attenuation_distance;
+    uint32_t mode;             /* 0 linear, 1 dry */
+    const float *border;       /* device, [n_border][3] */
+    uint32_t n_border, reserved_;
+} SdnSealBrush;
 
 /* Several frames may be rendered TOGETHER by one loop ("frame group": the shards of consecutive frames of a camera path / of
  * successive time steps on one GPU of a ray-sharded job).  The rays are frame-major -- ray r belongs to frame r / rays_per_frame --
@@ -474,8 +486,8 @@ typedef struct SdnRenderCtx {
      * samples, survivors and the trace (which logs N for iteration 0) are unchanged; `sigmas` holds the per-ray start parameters
      * between sdn_render_begin and the first field launch. */
     float *rays_tend;
-    /* optional SealD edit: a bounding-box or anchor seal mapper (SdnSealBox::kind) applied to every iteration's samples between the
-     * marcher and the field network (sdn_seal_bbox_map(_source) / sdn_seal_anchor_map) and to the colours of the mapped samples after
+    /* optional SealD edit: a bounding-box, anchor or brush seal mapper (SdnSealBox::kind) applied to every iteration's samples between the
+     * marcher and the field network (sdn_seal_bbox_map(_source) / sdn_seal_anchor_map / sdn_seal_brush_map) and to the colours of the mapped samples after
      * it (sdn_seal_modify_hsv / _rgb); NULL = no edit */
     const struct SdnSealBox *seal;
     uint8_t *seal_mask;        /* [M_cap] scratch, required with `seal` */
@@ -495,6 +507,8 @@ typedef struct SdnRenderCtx {
      * grid_table the fp32 embeddings in the reference's layout, grid_offsets the reference's offsets */
     int32_t field_f32;
     int32_t reserved2_;
+    /* the brush mapper's arguments: required when seal->kind == SDN_SEAL_BRUSH, not read otherwise */
+    const struct SdnSealBrush *seal_brush;
 } SdnRenderCtx;
 
 /* Resets per-ray state (alive = 0..N-1, rays_t = nears, accumulators = 0), the loop record and the counters, and builds
@@ -543,7 +557,7 @@ int sdn_render_frames_pipelined_f16(const SdnRenderCtx *const *ctxs, uint32_t n_
                                     const uint8_t *exclusive_frames, const SdnFrameTime *frame_times, void *const *done_events,
                                     uint32_t *iterations_out);
 /* ---------------------------------------------------------------------------
- * SealD-NeRF bounding-box and anchor seal mappers on the sample stream  (reference: SealNeRF/seal_utils.py:132-153 map_mask, :245-286
+ * SealD-NeRF bounding-box, anchor and brush seal mappers on the sample stream  (reference: SealNeRF/seal_utils.py:132-153 map_mask, :245-286
  * SealBBoxMapper.map_to_origin, :638-693 moller_trumbore / points_in_mesh, :747-758 modify_hsv; torch boolean-mask code there)
  * ------------------------------------------------------------------------- */
 /* In place on xyzs / dirs [M,3] (device): a sample that is non-zero in every coordinate, strictly inside one of the n_bounds (<= 4)
@@ -579,6 +593,21 @@ int sdn_seal_anchor_map(float *xyzs, float *dirs, uint32_t M, const float *bound
                         uint32_t n_tris, const float *test_dir, const float *v_anchor, const float *v_offset, const float *v_h,
                         float len_h, float radius, const float *scale, uint32_t *flag, uint8_t *mask, const uint32_t *live_idx,
                         const uint32_t *live_count, const int32_t *state, void *stream);
+/* SealD-NeRF brush seal mapper, SealBrushMapper.map_to_origin (seal_utils.py:415-461), in place on xyzs [M,3] (device); dirs are neither
+ * read nor written (may be NULL).  bounds / n_bounds / test_dir as for sdn_seal_bbox_map (test_dir is the last stroke's normal_expand,
+ * not normalised).  tris [n_tris][16] (device, 16-byte aligned) = v0, E1, E2, N = E1 x E2, 1 / -(test_dir . N + 1e-8),
+ * 1 / -(-test_dir . N + 1e-8), 0, 0 per triangle of all strokes' meshes: everything of moller_trumbore (:638-672) that does not depend on
+ * the point.  A slot is mapped iff map_mask holds (:132-153): every coordinate non-zero, strictly inside one of the bounds, and both the
+ * ray along test_dir and the opposite ray hit a triangle (t, u, v >= 0, u + v <= 1).  mode 0 (`linear`): q = the point projected onto
+ * the plane through `center` with normal `normal_expand`, dist = the distance from q to the nearest of border [n_border][3] (device,
+ * n_border >= 1) taken from coordinate differences; the point moves by -normal_expand and, where attenuation_distance > dist, back by
+ * |attenuation_distance - dist| / attenuation_distance * normal_expand.  mode 1 (`dry`): points stay, only the mask is written (border
+ * may be NULL).  mask [M] u8: 1 = mapped.  Every slot is mapped on its own: no flag word, no live list.  normal_expand, center: host
+ * arrays [3].  n_tris and n_border are not limited.  One launch, no host synchronisation. */
+int sdn_seal_brush_map(float *xyzs, float *dirs, uint32_t M, const float *bounds, uint32_t n_bounds, const float *tris,
+                       uint32_t n_tris, const float *test_dir, const float *normal_expand, const float *center,
+                       float attenuation_distance, uint32_t mode, const float *border, uint32_t n_border, uint8_t *mask,
+                       void *stream);
 /* rgbs [M,3] of the masked samples: rgb -> hsv, + (dh, ds, dv), -> rgb (color_utils.py:31-63), in place. */
 int sdn_seal_modify_hsv(float *rgbs, const uint8_t *mask, uint32_t M, float dh, float ds, float dv, void *stream);
 /* modify_rgb (seal_utils.py:761-777) on the masked samples, in place: hue and saturation of the target colour (r, g, b), brightness

@@ -61,6 +61,12 @@ static int seal_map(const SdnRenderCtx &c, uint32_t m_slots, hipStream_t st) {
                                    s->v_h, s->len_h, s->radius, s->scale, (uint32_t *)((char *)s->scratch + 16), c.seal_mask, c.live_idx,
                                    sdn_int::live_counters(c), c.state, st);
     }
+    if (s->kind == SDN_SEAL_BRUSH) {                 // per-slot map: no flag word, no live list, also in frame groups
+        const SdnSealBrush *b = c.seal_brush;
+        if (!b) return SDN_E_BADARG;
+        return sdn_seal_brush_map(c.xyzs, c.dirs, m_slots, s->bounds, s->n_bounds, s->tris, s->n_tris, s->test_dir, b->normal_expand, b->center,
+                                  b->attenuation_distance, b->mode, b->border, b->n_border, c.seal_mask, st);
+    }
     if (s->kind != SDN_SEAL_BBOX) return SDN_E_UNSUPPORTED;
     if (s->has_map_source) {
         if (!s->scratch) return SDN_E_BADARG;

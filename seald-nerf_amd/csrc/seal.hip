@@ -1,4 +1,4 @@
-// SealD-NeRF bounding-box and anchor (control-point) seal mappers on the sample stream (scope row "next" #1) for gfx950.
+// SealD-NeRF bounding-box, anchor (control-point) and brush seal mappers on the sample stream (scope row "next" #1) for gfx950.
 //
 // Behavioural contract: SealNeRF/seal_utils.py of the reference --
 //   map_mask            :132-153  (points.all(1) & strict AABB test of each bound, then points_in_mesh)
@@ -10,6 +10,7 @@
 //   the `mapSource` redirect of SealBBoxMapper.map_to_origin :269-273 (samples strictly inside the source box are sent to one point --
 //   only in calls that map at least one sample: the early return of :251-252 comes first)
 //   SealAnchorMapper.map_to_origin :522-578 with project_points :736-744 (the cone / plane-side deformation, see k_seal_anchor_apply)
+//   SealBrushMapper.map_to_origin :415-461 (the surface pushed along the stroke's normal, attenuated towards the stroke's border, see k_seal_brush_map)
 // The reference evaluates this with boolean-mask gathers / scatters and O(points x triangles) temporaries in torch, inside the
 // render loop; here it is one lane per sample slot, in place, between the marcher and the field kernel.  Dot products are
 // accumulated x, y, z in fp32 (torch's einsum order is library-defined): masks agree with the torch restatement except for
@@ -181,6 +182,149 @@ __global__ void __launch_bounds__(256) k_seal_anchor_apply(float *__restrict__ x
         const float mapped = pop[k] - lift * A.v_h[k] / A.len_h;
         xyzs[(size_t)i * 3 + k] = (mapped - A.v_anchor[k]) * A.scale[k] + A.v_anchor[k];
     }
+}
+
+// ---- brush mapper, SealBrushMapper.map_to_origin, seal_utils.py:415-461 -----------------------------------------------------------------
+// The brush's mesh has on the order of a thousand triangles (the box and anchor mappers have 12), so its map_mask does not walk them
+// per lane through seal_in_box:
+//   * the AABB test comes first, and the workgroup packs the slots that pass it into its leading lanes (LDS): a wave without a
+//     candidate returns before the triangle loop, whatever n_tris is, and the waves that stay are full of candidates instead of
+//     holding the few lanes of a ray bundle that cross the stroke;
+//   * the triangle records [F][16] = v0, E1, E2, N = E1 x E2, 1 / -(d . N + eps), 1 / -(-d . N + eps), 0, 0 are prepared on the host --
+//     one direction serves all points, so both inverse determinants are lane-independent -- and reach the lanes through an LDS tile
+//     per wave, fetched coalesced one tile ahead (walking them with wave-uniform scalar loads was measured first: every wave then
+//     waits out a load's latency per two triangles, 0.37 ms for a 2198-triangle mesh however few samples there are); the border
+//     points, a few dozen, are read with wave-uniform addresses (scalar loads);
+//   * the ray along d and the opposite ray share A0 = p - v0 and A0 x d (the opposite ray's cross product is its exact negation), so
+//     one pass over the triangles serves both;
+//   * every kBrushChunk triangles a wave stops once each of its candidates has both hits (a tile's tail is padded with NaN records,
+//     which no comparison accepts, so chunks are always whole and unrolled).
+// n_tris and n_border are not limited: the tiles and the border loop run over any count.
+// t, u, v and eps are moller_trumbore's (:638-672); dot products are accumulated x, y, z as in any_hit.
+constexpr uint32_t kBrushTriVec4 = 4;           // a triangle record is 16 floats
+constexpr uint32_t kBrushTile = 64;            // triangles per LDS tile of a wave (one float4 per lane and record quarter)
+constexpr uint32_t kBrushChunk = 16;
+constexpr uint32_t kBrushBlock = 256;
+static_assert(kBrushTile % kBrushChunk == 0 && kBrushTile * kBrushTriVec4 == 4 * 64, "a tile is whole chunks, and one float4 per lane and record quarter");
+
+// orders the LDS stores and loads of the lanes of ONE wave (a wave's lanes run in lockstep; this keeps the compiler from moving them)
+__device__ __forceinline__ void brush_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+struct SealBrushArgs {
+    float bounds[4][6];
+    uint32_t n_bounds, n_tris, n_border;
+    float test_dir[3];
+    float normal_expand[3], center[3];
+    float attenuation_distance;
+    uint32_t mode;             // 0 linear, 1 dry
+};
+
+__global__ void __launch_bounds__(kBrushBlock) k_seal_brush_map(float *__restrict__ xyzs, uint32_t M, SealBrushArgs A, const float4 *__restrict__ tris,
+                                                                const float *__restrict__ border, uint8_t *__restrict__ mask) {
+    __shared__ float s_p[kBrushBlock][3];
+    __shared__ uint32_t s_slot[kBrushBlock];
+    __shared__ uint32_t s_count[kBrushBlock / 64];
+    __shared__ float4 s_tile[kBrushBlock / 64][kBrushTile * kBrushTriVec4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t i = blockIdx.x * kBrushBlock + tid;
+    float x = 0.0f, y = 0.0f, z = 0.0f;
+    bool cand = false;
+    if (i < M) {
+        x = xyzs[(size_t)i * 3]; y = xyzs[(size_t)i * 3 + 1]; z = xyzs[(size_t)i * 3 + 2];
+        if (x != 0.0f && y != 0.0f && z != 0.0f) {
+            for (uint32_t b = 0; b < A.n_bounds; b++)
+                cand |= (A.bounds[b][3] > x) & (x > A.bounds[b][0]) & (A.bounds[b][4] > y) & (y > A.bounds[b][1]) & (A.bounds[b][5] > z) & (z > A.bounds[b][2]);
+        }
+        if (!cand) mask[i] = 0;
+    }
+    // pack the candidates of the workgroup into its leading lanes
+    const unsigned long long vote = __ballot(cand ? 1 : 0);
+    if (lane == 0u) s_count[wave] = (uint32_t)__popcll(vote);
+    __syncthreads();
+    uint32_t base = 0, total = 0;
+    #pragma unroll
+    for (uint32_t w = 0; w < kBrushBlock / 64; w++) {
+        base += w < wave ? s_count[w] : 0u;
+        total += s_count[w];
+    }
+    if (total == 0u) return;                                   // workgroup-uniform
+    if (cand) {
+        const uint32_t k = base + (uint32_t)__popcll(vote & ((1ull << lane) - 1ull));
+        s_p[k][0] = x; s_p[k][1] = y; s_p[k][2] = z;
+        s_slot[k] = i;
+    }
+    __syncthreads();
+    if ((tid & ~63u) >= total) return;                         // wave-uniform: no candidate left for this wave
+    const bool act = tid < total;
+    const float px = act ? s_p[tid][0] : 0.0f, py = act ? s_p[tid][1] : 0.0f, pz = act ? s_p[tid][2] : 0.0f;
+    const uint32_t slot = act ? s_slot[tid] : 0u;
+    const float dx = A.test_dir[0], dy = A.test_dir[1], dz = A.test_dir[2];
+    bool hit_pos = false, hit_neg = false;
+    // The wave's own LDS tile of kBrushTile triangle records: each lane fetches kBrushTriVec4 float4 of the NEXT tile (coalesced) while
+    // the wave walks the current one, whose records every lane then reads at the same address (LDS broadcast).  The tile belongs to
+    // one wave, so a wave-level fence orders its stores and loads and no workgroup barrier stands between the waves.
+    float4 *tile = s_tile[wave];
+    const uint32_t n_vec = A.n_tris * kBrushTriVec4;
+    const float4 pad = make_float4(NAN, NAN, NAN, NAN);   // a record past the list: every comparison with it is false
+    const auto fetch = [&](size_t first, uint32_t j) -> float4 {
+        const size_t v = first + j * 64u + lane;
+        float4 r = pad;
+        if (v < n_vec) r = tris[v];
+        return r;
+    };
+    float4 pre0 = fetch(0, 0), pre1 = fetch(0, 1), pre2 = fetch(0, 2), pre3 = fetch(0, 3);
+    bool done = false;
+    for (uint32_t t0 = 0; t0 < A.n_tris && !done; t0 += kBrushTile) {
+        brush_wave_sync();                                     // the walk of the previous tile is over
+        tile[lane] = pre0; tile[64u + lane] = pre1; tile[128u + lane] = pre2; tile[192u + lane] = pre3;
+        const size_t next = (size_t)(t0 + kBrushTile) * kBrushTriVec4;
+        pre0 = fetch(next, 0); pre1 = fetch(next, 1); pre2 = fetch(next, 2); pre3 = fetch(next, 3);
+        brush_wave_sync();
+        const uint32_t count = min(kBrushTile, A.n_tris - t0);
+        for (uint32_t f0 = 0; f0 < count; f0 += kBrushChunk) {
+            // whole chunks, unrolled, so that the LDS reads of several records are in flight at once (the tile's tail is padded)
+            #pragma unroll 8
+            for (uint32_t k = 0; k < kBrushChunk; k++) {
+                const uint32_t f = f0 + k;
+                const float4 r0 = tile[kBrushTriVec4 * f], r1 = tile[kBrushTriVec4 * f + 1], r2 = tile[kBrushTriVec4 * f + 2], r3 = tile[kBrushTriVec4 * f + 3];
+                const float a0x = px - r0.x, a0y = py - r0.y, a0z = pz - r0.z;
+                const float cx = a0y * dz - a0z * dy, cy = a0z * dx - a0x * dz, cz = a0x * dy - a0y * dx;   // A0 x d; A0 x (-d) is its negation
+                const float ce2 = dot3(cx, cy, cz, r1.z, r1.w, r2.x);
+                const float ce1 = dot3(cx, cy, cz, r0.w, r1.x, r1.y);
+                const float an = dot3(a0x, a0y, a0z, r2.y, r2.z, r2.w);
+                const float up = ce2 * r3.x, vp = -ce1 * r3.x, tp = an * r3.x;
+                const float un = -ce2 * r3.y, vn = ce1 * r3.y, tn = an * r3.y;
+                hit_pos |= (tp >= 0.0f) & (up >= 0.0f) & (vp >= 0.0f) & ((up + vp) <= 1.0f);
+                hit_neg |= (tn >= 0.0f) & (un >= 0.0f) & (vn >= 0.0f) & ((un + vn) <= 1.0f);
+            }
+            if (__ballot((act && !(hit_pos && hit_neg)) ? 1 : 0) == 0ull) { done = true; break; }      // wave-uniform
+        }
+    }
+    if (!act) return;
+    const bool in = hit_pos && hit_neg;
+    mask[slot] = in ? 1 : 0;
+    if (!in || A.mode != 0u) return;                           // dry brush: the mask only, no space mapping
+    const float nx = A.normal_expand[0], ny = A.normal_expand[1], nz = A.normal_expand[2];
+    // project_points(normal_expand, center, p), :736-744
+    const float along = dot3(px - A.center[0], py - A.center[1], pz - A.center[2], nx, ny, nz) / dot3(nx, ny, nz, nx, ny, nz);
+    const float qx = px - along * nx, qy = py - along * ny, qz = pz - along * nz;
+    // distance to the nearest border point from coordinate differences (the minimum of the squares has the minimum's root)
+    float best = INFINITY;
+    for (uint32_t b = 0; b < A.n_border; b++) {
+        const float ex = qx - border[3 * (size_t)b], ey = qy - border[3 * (size_t)b + 1], ez = qz - border[3 * (size_t)b + 2];
+        best = fminf(best, dot3(ex, ey, ez, ex, ey, ez));
+    }
+    const float dist = sqrtf(best);
+    float ox = px - nx, oy = py - ny, oz = pz - nz;
+    if (A.attenuation_distance > dist) {
+        const float k = fabsf(A.attenuation_distance - dist) / A.attenuation_distance;
+        ox += k * nx; oy += k * ny; oz += k * nz;
+    }
+    xyzs[(size_t)slot * 3] = ox; xyzs[(size_t)slot * 3 + 1] = oy; xyzs[(size_t)slot * 3 + 2] = oz;
 }
 
 // color_utils.py:31-46 for one colour: (h / 6, s, v)
@@ -487,6 +631,27 @@ int sdn_seal_anchor_map(float *xyzs, float *dirs, uint32_t M, const float *bound
     hipLaunchKernelGGL(k_seal_box_mask, grid, block, 0, (hipStream_t)stream, (const float *)xyzs, M, b, mask);
     hipLaunchKernelGGL(k_seal_any, grid, block, 0, (hipStream_t)stream, (const uint8_t *)mask, L, flag, tag);
     hipLaunchKernelGGL(k_seal_anchor_apply, grid, block, 0, (hipStream_t)stream, xyzs, M, a, mask);
+    return sdn_launch_status();
+}
+
+// SealBrushMapper.map_to_origin (seal_utils.py:415-461), in place on xyzs; dirs are not read or written.  Every slot is mapped on its own:
+// no flag word, no live list.  One launch, no host synchronisation.
+int sdn_seal_brush_map(float *xyzs, float *dirs, uint32_t M, const float *bounds, uint32_t n_bounds, const float *tris, uint32_t n_tris,
+                       const float *test_dir, const float *normal_expand, const float *center, float attenuation_distance, uint32_t mode,
+                       const float *border, uint32_t n_border, uint8_t *mask, void *stream) {
+    (void)dirs;
+    if (M == 0) return 0;
+    if (!xyzs || !bounds || !tris || !test_dir || !normal_expand || !center || !mask || ((uintptr_t)tris & 15u) != 0) return SDN_E_BADARG;
+    if (n_bounds == 0 || n_bounds > 4 || n_tris == 0 || mode > 1u) return SDN_E_UNSUPPORTED;
+    if (mode == 0u && (!border || n_border == 0)) return SDN_E_BADARG;
+    SealBrushArgs a;
+    for (uint32_t k = 0; k < n_bounds; k++)
+        for (int j = 0; j < 6; j++) a.bounds[k][j] = bounds[6 * k + j];
+    a.n_bounds = n_bounds; a.n_tris = n_tris; a.n_border = n_border;
+    for (int k = 0; k < 3; k++) { a.test_dir[k] = test_dir[k]; a.normal_expand[k] = normal_expand[k]; a.center[k] = center[k]; }
+    a.attenuation_distance = attenuation_distance; a.mode = mode;
+    hipLaunchKernelGGL(k_seal_brush_map, dim3(sdn_div_up(M, kBrushBlock)), dim3(kBrushBlock), 0, (hipStream_t)stream, xyzs, M, a, (const float4 *)tris, border,
+                       mask);
     return sdn_launch_status();
 }
 

@@ -577,30 +577,39 @@ class DeviceLoop:
         self.set_mapper(mapper)
 
     def set_mapper(self, mapper):
-        """Hooks a SealD seal mapper (`dnerf_amd.seal_mapper.SealBBoxMapper` / `SealAnchorMapper`, or None) into every iteration of the
+        """Hooks a SealD seal mapper (`dnerf_amd.seal_mapper.SealBBoxMapper` / `SealAnchorMapper` / `SealBrushMapper`, or None) into every iteration of the
         native loop: samples are mapped back to their origin before the field kernel, colours of the mapped samples re-mapped after it."""
         import ctypes
-        from sdn_backend import SdnSealBox, SEAL_ANCHOR, SEAL_BBOX
-        from .seal_mapper import SealAnchorMapper
+        from sdn_backend import SdnSealBox, SdnSealBrush, SEAL_ANCHOR, SEAL_BBOX, SEAL_BRUSH
+        from .seal_mapper import SealAnchorMapper, SealBrushMapper
         c = self.ctx
         self.mapper = mapper
         if mapper is None:
-            c.seal, c.seal_mask, self._seal = None, None, None
+            c.seal, c.seal_mask, c.seal_brush, self._seal = None, None, None, None
             return
         dev = self.buf["xyzs"].device
         mapper.map_data_conversion(self.buf["xyzs"])
         a = mapper._native_args(dev)
-        anchor = isinstance(mapper, SealAnchorMapper)
+        anchor, brush = isinstance(mapper, SealAnchorMapper), isinstance(mapper, SealBrushMapper)
         if self.frames > 1 and (anchor or mapper.redirects_source or "rgb" in mapper.map_data):
             # these look at ALL samples of a loop iteration (the mean brightness of the masked ones, "does the call map anything" of
             # mapSource and of the anchor mapper): in a frame group an iteration holds several frames' samples, which the reference never mixes
+            # (the brush maps every sample on its own: without a tint it runs on frame groups)
             raise NotImplementedError("mapSource / rgb tint / the anchor mapper depend on the set of samples of an iteration: render such edits one frame per loop")
         box = SdnSealBox()
         for k in range(6 * a["n_bounds"]):
             box.bounds[k] = a["bounds"][k]
         box.n_bounds, box.n_tris, box.tris = a["n_bounds"], a["n_tris"], a["tris"].data_ptr()
-        box.kind = SEAL_ANCHOR if anchor else SEAL_BBOX
-        if anchor:
+        box.kind = SEAL_ANCHOR if anchor else SEAL_BRUSH if brush else SEAL_BBOX
+        rec = None
+        if brush:
+            fields = (("test_dir", 3),)
+            rec = SdnSealBrush()
+            for k in range(3):
+                rec.normal_expand[k], rec.center[k] = a["normal_expand"][k], a["center"][k]
+            rec.attenuation_distance, rec.mode = a["attenuation_distance"], a["mode"]
+            rec.border, rec.n_border = a["border"].data_ptr(), a["n_border"]
+        elif anchor:
             fields = (("test_dir", 3), ("scale", 3), ("v_anchor", 3), ("v_offset", 3), ("v_h", 3))
             box.len_h, box.radius = a["len_h"], a["radius"]
         else:
@@ -625,8 +634,9 @@ class DeviceLoop:
         scratch = torch.zeros(32, dtype=torch.uint8, device=dev)
         box.scratch = scratch.data_ptr()
         mask = torch.empty(self.buf["sigmas"].shape[0], dtype=torch.uint8, device=dev)
-        self._seal = (box, mask, a, scratch)      # keep the record, the mask, the triangle tensor and the scratch alive
+        self._seal = (box, mask, a, scratch, rec)      # keep the records, the mask, the triangle / border tensors and the scratch alive
         c.seal, c.seal_mask = ctypes.addressof(box), mask.data_ptr()
+        c.seal_brush = ctypes.addressof(rec) if rec is not None else None
 
     def prepare_timing(self, frames):
         """Pre-creates (outside any timed region) the HIP event pairs for `frames` timed renders: MAX_TIMED pairs per frame,

@@ -1,10 +1,12 @@
-"""SealD-NeRF bounding-box and anchor (control-point) mappers on the device (scope row "next" #1): the objects the teacher /
+"""SealD-NeRF bounding-box, anchor (control-point) and brush mappers on the device (scope row "next" #1): the objects the teacher /
 student renderers hook between the marcher and the field network (`map_to_origin`) and after it (`map_color`).
 
 Mirrors, with the same names and `map_data` keys, the pieces of the reference that sit inside the render loop:
   * `SealMapper.map_mask` / `map_color` / `map_data_conversion`      SealNeRF/seal_utils.py:40-153
   * `SealBBoxMapper.__init__` / `map_to_origin`                      SealNeRF/seal_utils.py:156-286
   * `SealAnchorMapper.__init__` / `map_to_origin`, `project_points`  SealNeRF/seal_utils.py:464-578, 736-744
+  * `SealBrushMapper.__init__` / `map_to_origin`, `get_trimesh_fit`,
+    `mesh_surface_points_mask`                                       SealNeRF/seal_utils.py:304-461, 599-631, 720-733
   * `moller_trumbore`, `points_in_mesh`                              SealNeRF/seal_utils.py:638-693
   * `modify_hsv`, `modify_rgb`                                       SealNeRF/seal_utils.py:747-777
   * `rgb2hsv_torch`, `hsv2rgb_torch` ([N,3] form)                    SealNeRF/color_utils.py:31-63
@@ -149,9 +151,13 @@ class SealMapper:
         elif not force:
             return
         for k, v in self.map_data.items():
+            if isinstance(v, str):             # (the brush's `attenuation_mode`)
+                continue
             self.map_data[k] = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(self.device, self.dtype)
         if self.map_triangles is not None:
             self.map_triangles = self.map_triangles.to(self.device, self.dtype)
+        if self.map_test_dir is not None:
+            self.map_test_dir = self.map_test_dir.to(self.device, self.dtype)
 
     def map_mask(self, points):
         bounds = self.map_data["map_bound"]
@@ -200,7 +206,7 @@ class SealMapper:
             f32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32))  # noqa: E731
             cfl = lambda a: (ctypes.c_float * a.size)(*a.reshape(-1).tolist())                          # noqa: E731
             md = {k: (v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64))
-                  for k, v in self.map_data.items()}
+                  for k, v in self.map_data.items() if not isinstance(v, str)}
             tri = self.map_triangles.detach().cpu().double().numpy()
             e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
             tris12 = np.concatenate([tri[:, 0], e1, e2, np.cross(e1, e2)], axis=1)
@@ -504,13 +510,242 @@ class SealAnchorMapper(SealMapper):
             return points_copy, dirs, valid_mask
 
 
+def knn_prism_faces(points, k=10):
+    """The faces of `get_trimesh_fit` (seal_utils.py:603-617) for N points -> int64 [N * (k-1)(k-2)/2 * 4, 3] over the 2N vertices
+    (bottom copy 0..N-1, top copy N..2N-1): each point with every pair of its k-1 nearest neighbours spans a bottom triangle, the top
+    triangle above it and two triangles of the wall over the edge to the first neighbour of the pair.  The neighbours are found by
+    brute force (no scikit-learn), ordered by (distance, index), the point itself first."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    n = p.shape[0]
+    if n < k:
+        raise ValueError(f"a curve stroke needs at least {k} points for its {k}-nearest-neighbour mesh, got {n}")
+    d2 = ((p[:, None] - p[None]) ** 2).sum(-1)
+    d2[np.arange(n), np.arange(n)] = -1.0
+    indices = np.lexsort((np.broadcast_to(np.arange(n), (n, n)), d2), axis=1)[:, :k]
+    jj, kk = np.triu_indices(k, 1)
+    jj, kk = jj[jj >= 1], kk[jj >= 1]
+    x = np.repeat(np.arange(n), jj.size)
+    y, z = indices[:, jj].reshape(-1), indices[:, kk].reshape(-1)
+    faces = np.stack([np.stack([x, y, z], 1), np.stack([x + n, y + n, z + n], 1), np.stack([x, y, x + n], 1), np.stack([x + n, y, y + n], 1)], 1)
+    return faces.reshape(-1, 3).astype(np.int64)
+
+
+def cluster_vertices(vertices, faces, voxel_size):
+    """Vertex clustering with averaging (what open3d's `simplify_vertex_clustering(contraction=Average)` does): the vertices of one
+    voxel of the grid with origin min bound - voxel_size / 2 become their mean; faces with a repeated vertex and duplicate faces
+    (the same vertex cycle) go.  -> (vertices [V,3], faces [F,3]).  open3d is not available: this is a restatement -- clusters are
+    numbered by voxel key (x, y, z lexicographic) and faces sorted, where open3d's hash containers give an unspecified order, and a
+    vertex exactly on a voxel boundary may fall to the other side.  Neither changes the surface the ray test sees."""
+    v = np.asarray(vertices, dtype=np.float64)
+    origin = v.min(0) - 0.5 * voxel_size
+    key = np.floor((v - origin) / voxel_size).astype(np.int64)
+    _, cluster, count = np.unique(key, axis=0, return_inverse=True, return_counts=True)
+    cluster = cluster.reshape(-1)
+    merged = np.zeros((count.shape[0], 3))
+    np.add.at(merged, cluster, v)
+    merged /= count[:, None]
+    f = cluster[np.asarray(faces, dtype=np.int64)]
+    f = f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])]
+    first = np.argmin(f, axis=1)                               # rotate the cycle so that its smallest vertex comes first
+    f = np.stack([f[np.arange(f.shape[0]), (first + r) % 3] for r in range(3)], 1)
+    return merged, np.unique(f, axis=0)
+
+
+def fit_prism_mesh(points, normal, growth, simplify_voxel=16):
+    """`get_trimesh_fit` (seal_utils.py:599-631) in numpy -> (vertices, faces): the k-nearest-neighbour prism over `points` between
+    points + normal * growth[0] and points + normal * growth[1], simplified by vertex clustering with a voxel of the largest extent /
+    simplify_voxel."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    faces = knn_prism_faces(p)
+    verts = np.concatenate([p + normal * growth[0], p + normal * growth[1]])
+    voxel = (verts.max(0) - verts.min(0)).max() / simplify_voxel
+    return cluster_vertices(verts, faces, voxel)
+
+
+def mesh_surface_points_mask(triangles, points):
+    """seal_utils.py:720-733: the points from which some +-1e-4 step along an axis leaves the mesh (default test direction)."""
+    offset_value = 1e-4
+    offsets = torch.from_numpy(np.array([[0, 0, offset_value], [0, 0, -offset_value], [0, offset_value, 0], [0, -offset_value, 0],
+                                         [offset_value, 0, 0], [-offset_value, 0, 0]])).to(points.device, points.dtype)
+    return torch.sum(torch.stack([~points_in_mesh(points + offsets[i], triangles) for i in range(offsets.shape[0])]), 0) > 0
+
+
+def brush_triangle_records(triangles, test_dir):
+    """The [F,16] fp32 triangle records of `sdn_seal_brush_map`: v0, E1, E2, N = E1 x E2, then moller_trumbore's inverse determinant
+    1 / -(d . N + eps) for the ray along `test_dir` and for the opposite ray (fp32 arithmetic, eps = 1e-8: one direction serves all
+    points, so neither depends on the point), two zeros of padding."""
+    tri = np.asarray(triangles, dtype=np.float64)
+    e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    rec = np.zeros((tri.shape[0], 16), dtype=np.float32)
+    rec[:, :12] = np.concatenate([tri[:, 0], e1, e2, np.cross(e1, e2)], axis=1).astype(np.float32)
+    d = np.asarray(test_dir, dtype=np.float64).reshape(3).astype(np.float32)
+    n = rec[:, 9:12]
+    dn = n[:, 0] * d[0] + n[:, 1] * d[1] + n[:, 2] * d[2]
+    with np.errstate(divide="ignore"):
+        rec[:, 12] = np.float32(1.0) / -(dn + np.float32(1e-8))
+        rec[:, 13] = np.float32(1.0) / -(-dn + np.float32(1e-8))
+    return rec
+
+
+_BRUSH_MODES = {"linear": 0, "dry": 1}
+
+
+class SealBrushMapper(SealMapper):
+    """seal_utils.py:289-461, the brush tool: the surface under a stroke is raised (or, with a negative pressure, lowered) along the
+    stroke plane's normal.  seal_config: {type: 'brush', raw: [N,3] stroke points or a list of strokes [B][N_b,3] (B <= 4), normal: [3]
+    the positive side of the plane, brushType: 'line' | 'curve' or one per stroke, simplifyVoxel: 16, brushDepth, brushPressure,
+    attenuationDistance, attenuationMode: 'linear' | 'dry', hsv / rgb / rgbLightOffset optional}.
+
+    Per stroke: the best-fit plane of its points, the normal turned towards `normal`, normal_expand = normal * brushPressure.  A 'line'
+    stroke's mesh is the oriented box of the points moved by 2 normal_expand and by -brushDepth normal_expand (`oriented_box`: the
+    documented PCA stand-in for trimesh's minimum-volume box); a 'curve' stroke's is `fit_prism_mesh` of its projected points between
+    the same two offsets.  The stroke's border points are its projected points from which a 1e-4 step along some axis leaves its mesh.
+
+    `map_to_origin` takes a sample inside one of the meshes back by normal_expand -- less towards the stroke's border: within
+    attenuationDistance of the nearest border point the shift falls off linearly to zero.  'dry' changes colours only.  The map is
+    per sample: which samples are mapped is `map_mask` alone, so, unlike the anchor mapper and `mapSource`, it also runs on frame
+    groups.
+
+    As in the reference, `normal_expand`, `center` and the ray test's direction (`map_test_dir`, not normalised) are the LAST stroke's:
+    all strokes are assumed to lie in one plane.  Not built: `imageConfig` (the texture stamp, needs cv2) and the 'ease-in' /
+    'ease-out' modes (unimplemented in the reference too) raise NotImplementedError here, at construction; `to.obj` is not written."""
+
+    MAX_STROKES = 4        # the device box test holds 4 bounds
+
+    def __init__(self, seal_config, config_path=None):
+        super().__init__(seal_config)
+        missing = [k for k in ("raw", "brushType", "brushDepth", "brushPressure", "attenuationDistance", "attenuationMode") if k not in seal_config]
+        if missing:
+            raise NotImplementedError(f"seal mapper type 'brush' without the config keys {missing}: there is nothing to build a stroke from")
+        if "imageConfig" in seal_config:
+            raise NotImplementedError("the brush's `imageConfig` texture stamp is not built")
+        mode = seal_config["attenuationMode"]
+        if mode in ("ease-in", "ease-out"):
+            raise NotImplementedError(f"attenuationMode {mode!r} (the reference leaves it unimplemented)")
+        if mode not in _BRUSH_MODES:
+            raise ValueError(f"attenuationMode {mode!r}")
+        points = seal_config["raw"]
+        if np.asarray(points[0]).ndim == 1:
+            points = [points]
+        if len(points) > self.MAX_STROKES:
+            raise ValueError(f"a brush edit holds at most {self.MAX_STROKES} strokes, got {len(points)}")
+        brush_type = seal_config["brushType"]
+        if isinstance(brush_type, str):
+            brush_type = [brush_type for _ in range(len(points))]
+        if len(brush_type) != len(points):
+            raise ValueError(f"{len(brush_type)} brush types for {len(points)} strokes")
+        self.stroke_triangles, bounds, border_points = [], [], []
+        for i in range(len(points)):
+            current_points = np.asarray(points[i], dtype=np.float64).reshape(-1, 3)
+            plane_point, normal = best_fit_plane(current_points)
+            if "normal" in seal_config and normal @ np.array(seal_config["normal"], dtype=np.float64) < 0:
+                normal = -normal
+            normal_expand = normal * seal_config["brushPressure"]
+            projected_points = project_points(torch.from_numpy(normal), torch.from_numpy(plane_point), torch.from_numpy(current_points))
+            if brush_type[i] == "line":
+                verts, _ = oriented_box(np.vstack([current_points + 2 * normal_expand, current_points - seal_config["brushDepth"] * normal_expand]))
+                tri = verts[_BOX_FACES]
+            elif brush_type[i] == "curve":
+                verts, faces = fit_prism_mesh(projected_points.numpy(), normal_expand, [-seal_config["brushDepth"], 2], seal_config.get("simplifyVoxel", 16))
+                if faces.shape[0] == 0:
+                    raise ValueError(f"stroke {i}: the simplified mesh has no face left (simplifyVoxel {seal_config.get('simplifyVoxel', 16)})")
+                tri = verts[faces]
+            else:
+                raise ValueError(f"brushType {brush_type[i]!r}")
+            self.stroke_triangles.append(tri)
+            bounds.append(_bounds(tri.reshape(-1, 3)))
+            border_mask = mesh_surface_points_mask(torch.from_numpy(tri).to(self.dtype), projected_points.to(self.dtype))
+            border_points.append(projected_points[border_mask])
+        border_points = torch.cat(border_points)
+        if border_points.shape[0] == 0:
+            raise ValueError("no stroke point lies on the border of its mesh: there is no border to attenuate towards")
+        self.map_triangles = torch.from_numpy(np.concatenate(self.stroke_triangles))
+        self.map_test_dir = torch.from_numpy(normal_expand[None])
+        self.map_data = {
+            "force_fill_bound": np.array(bounds),
+            "map_bound": np.array(bounds),
+            "normal_expand": normal_expand,             # from the last stroke's plane, as is `center`
+            "center": plane_point,
+            "border_points": border_points,             # from all strokes
+            "attenuation_distance": seal_config["attenuationDistance"],
+            "attenuation_mode": mode,
+        }
+        if "hsv" in seal_config:
+            self.map_data["hsv"] = seal_config["hsv"]
+        if "rgb" in seal_config:
+            self.map_data["rgb"] = seal_config["rgb"]
+            self.map_data["rgb_light_offset"] = seal_config.get("rgbLightOffset", 0)
+        self.map_data_conversion(force=True)
+
+    def _native_map_args(self, md, f32, cfl):
+        device = self._native["tris"].device
+        records = brush_triangle_records(self.map_triangles.detach().cpu().double().numpy(), md["normal_expand"])
+        border = f32(md["border_points"].reshape(-1, 3))
+        # the brush kernel's triangle records replace the 12-float ones of the box test
+        return dict(tris=torch.from_numpy(records).to(device), normal_expand=cfl(f32(md["normal_expand"].reshape(3))), center=cfl(f32(md["center"].reshape(3))),
+                    attenuation_distance=float(np.float32(md["attenuation_distance"])), mode=_BRUSH_MODES[self.map_data["attenuation_mode"]],
+                    border=torch.from_numpy(border).to(device), n_border=int(border.shape[0]))
+
+    @torch.no_grad()
+    def map_to_origin_(self, points, dirs):
+        """In-place `map_to_origin` on the sample buffers (CUDA fp32 contiguous) -> bool mask [M]; `sdn_seal_brush_map` of csrc/seal.hip.
+        `dirs` are neither read nor written."""
+        from sdn_backend import lib, check, ptr, stream
+        a = self._native_args(points.device)
+        M = points.shape[0]
+        mask = torch.empty(M, dtype=torch.uint8, device=points.device)
+        check(lib.sdn_seal_brush_map(ptr(points), None, M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"], a["normal_expand"],
+                                     a["center"], a["attenuation_distance"], a["mode"], ptr(a["border"]), a["n_border"], ptr(mask), stream()),
+              "seal_brush_map")
+        return mask.view(torch.bool)
+
+    @torch.no_grad()
+    def map_to_origin(self, points, dirs=None):
+        """-> (points', dirs, mask): the samples inside the strokes' meshes taken back along the normal.  CUDA fp32 inputs take the HIP
+        kernel (on copies, as the reference returns copies); everything else the torch restatement below."""
+        if self._native_ok(points, dirs):
+            self.map_data_conversion(points)
+            p, d = points.clone(), dirs.clone()
+            return p, d, self.map_to_origin_(p, d)
+        return self._map_to_origin_torch(points, dirs)
+
+    @torch.no_grad()
+    def _map_to_origin_torch(self, points, dirs=None):
+        """seal_utils.py:415-461, statement by statement (`linear` and `dry`)."""
+        with torch.autocast(points.device.type if points.device.type != "cpu" else "cpu", enabled=False):
+            self.map_data_conversion(points)
+            md = self.map_data
+            map_mask = self.map_mask(points)
+            if not map_mask.any():
+                return points, dirs, map_mask
+            inner_points = points[map_mask]
+            mode = md["attenuation_mode"]
+            if mode == "linear":
+                projected_points = project_points(md["normal_expand"], md["center"], inner_points)
+                brush_border_distance = torch.cdist(projected_points, md["border_points"]).min(1)[0]
+                points_mapped = inner_points - md["normal_expand"]
+                distance_filter = md["attenuation_distance"] > brush_border_distance
+                points_compensation = (torch.abs(md["attenuation_distance"] - brush_border_distance[distance_filter]) /
+                                       md["attenuation_distance"])[None].T @ md["normal_expand"][None]
+                points_mapped[distance_filter] += points_compensation
+            elif mode == "dry":
+                points_mapped = inner_points              # for a dry brush no space mapping is applied
+            else:
+                raise NotImplementedError(mode)
+            points_copy = points.clone()
+            points_copy[map_mask] = points_mapped
+            return points_copy, dirs, map_mask
+
+
 def get_seal_mapper(seal_config, config_path=None):
     """seal_utils.py:581-592 for the mapper types built here."""
     if seal_config.get("type") == "bbox":
         return SealBBoxMapper(seal_config, config_path)
     if seal_config.get("type") == "anchor":
         return SealAnchorMapper(seal_config, config_path)
-    raise NotImplementedError(f"seal mapper type {seal_config.get('type')!r} (the brush mapper needs trimesh + pytorch3d + open3d mesh fitting)")
+    if seal_config.get("type") == "brush":
+        return SealBrushMapper(seal_config, config_path)
+    raise NotImplementedError(f"seal mapper type {seal_config.get('type')!r}")
 
 
 @torch.no_grad()

@@ -55,6 +55,7 @@ PROTOTYPES = {
     "sdn_seal_modify_hsv": [_vp, _vp, _u32, _f32, _f32, _f32, _vp],
     "sdn_seal_bbox_map_source": [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sdn_seal_anchor_map": [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sdn_seal_brush_map": [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _f32, _u32, _vp, _u32, _vp, _vp],
     "sdn_seal_modify_rgb": [_vp, _vp, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
     "sdn_whole_rays_schedule": [_vp, _vp, _vp, _u32, _u32, _f32, _u32, _vp, _vp, _vp, _vp],
     "sdn_seal_modify_rgb_whole_rays": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
@@ -95,7 +96,7 @@ class SdnRenderCtx(ctypes.Structure):
                 + [(n, _f32) for n in ("bound", "dt_gamma", "T_thresh", "density_scale")]
                 + [("zero_deform", ctypes.c_int32), ("aabb", _vp), ("min_near", _f32), ("reserved_", ctypes.c_int32), ("rays_tend", _vp), ("seal", _vp), ("seal_mask", _vp),
                    ("n_group_frames", _u32), ("rays_per_frame", _u32), ("frame_bitfield", _vp * MAX_GROUP_FRAMES), ("slot_frame", _vp),
-                   ("frame_cull", _vp * MAX_GROUP_FRAMES), ("field_f32", _i32), ("reserved2_", _i32)])
+                   ("frame_cull", _vp * MAX_GROUP_FRAMES), ("field_f32", _i32), ("reserved2_", _i32), ("seal_brush", _vp)])
 
 
 # Word indices of `SdnLoopRecord` (include/sdn_hip.h: the 16 ints of `SdnRenderCtx.state`, one name per word, same order)
@@ -114,7 +115,17 @@ class SdnSealBox(ctypes.Structure):
                 ("v_anchor", _f32 * 3), ("v_offset", _f32 * 3), ("v_h", _f32 * 3), ("len_h", _f32), ("radius", _f32)]
 
 
-SEAL_BBOX, SEAL_ANCHOR = 0, 1   # SdnSealBox.kind: SDN_SEAL_BBOX, SDN_SEAL_ANCHOR
+SEAL_BBOX, SEAL_ANCHOR, SEAL_BRUSH = 0, 1, 2   # SdnSealBox.kind: SDN_SEAL_BBOX, SDN_SEAL_ANCHOR, SDN_SEAL_BRUSH
+
+
+class SdnSealBrush(ctypes.Structure):
+    """Mirror of `SdnSealBrush` in include/sdn_hip.h: the brush mapper's own arguments (`SdnRenderCtx.seal_brush`)."""
+    _fields_ = [("normal_expand", _f32 * 3), ("center", _f32 * 3), ("attenuation_distance", _f32), ("mode", _u32), ("border", _vp),
+                ("n_border", _u32), ("reserved_", _u32)]
+
+
+BRUSH_LINEAR, BRUSH_DRY = 0, 1   # SdnSealBrush.mode
+BRUSH_TRI_FLOATS = 16            # floats per triangle record of sdn_seal_brush_map
 
 
 TRAIN_N_PARAMS = 14   # SDN_TRAIN_N_PARAMS
