@@ -419,12 +419,26 @@ typedef struct SdnSealBox {
     float source_bound[6], map_source[3];
     uint32_t reserved_;
     void *scratch;             /* device, 32 bytes, zeroed once by the caller: [0..15] modify_rgb's sum / count, [16..19] the flag word
-                                * of `mapSource` / of the anchor mapper ("did this iteration map anything") */
+                                * of `mapSource` / of the anchor mapper ("did this iteration map anything"); 48 bytes with a brush's
+                                * texture stamp (SdnSealBrush::image): [32..47] its sum / count */
     /* SDN_SEAL_BBOX: the fields above.  SDN_SEAL_ANCHOR (SealAnchorMapper, seal_utils.py:464-578): bounds / tris / test_dir are the
      * mapper's one box, `scale` its per-axis scale about v_anchor; tinv, rinv, center and the mapSource fields are not read */
     uint32_t kind;
     float v_anchor[3], v_offset[3], v_h[3], len_h, radius;
 } SdnSealBox;
+
+/* The brush's `imageConfig` texture stamp (seal_utils.py:58-79, :389-411; sdn_seal_modify_image), for SdnSealBrush.image.  The texture
+ * lies on the parallelogram o, w, h in space: a sample is projected onto the plane through v_o with normal v_norm, and its texel is
+ * column clamp(floor(v_op . v_ow / len_ow_sq * W), 0, W - 1), row likewise with v_oh and H.  Host memory except `texels`. */
+typedef struct SdnSealImage {
+    const float *texels;       /* device, [H][W][4], 16-byte aligned: hue / 6, saturation, value of the texel's colour and its alpha
+                                * (sdn_seal_image_texels makes them from r, g, b, alpha) */
+    uint32_t W, H;             /* H * W < 2^28 */
+    float v_o[3], v_norm[3];   /* `o` of the config; the normal of the plane through o, w, h (either sign, any length) */
+    float v_ow[3], v_oh[3];    /* w - o, h - o */
+    float norm_sq, len_ow_sq, len_oh_sq;   /* v_norm . v_norm, |v_ow|^2, |v_oh|^2, each as the reference's fp32 statements give it */
+    float light_offset;        /* `rgbLightOffset` */
+} SdnSealImage;
 
 /* The brush mapper's own arguments (sdn_seal_brush_map), for SdnRenderCtx.seal_brush: read when SdnSealBox::kind == SDN_SEAL_BRUSH.
  * The SdnSealBox then carries the bounds, test_dir, the colour fields and `tris` in the BRUSH layout, [n_tris][16] (see
@@ -435,6 +449,9 @@ typedef struct SdnSealBrush {
     uint32_t mode;             /* 0 linear, 1 dry */
     const float *border;       /* device, [n_border][3] */
     uint32_t n_border, reserved_;
+    /* optional `imageConfig` texture stamp (sdn_seal_modify_image), applied to the colours of the mapped samples after the hsv and rgb
+     * modifications; NULL = none.  With it SdnSealBox::scratch holds 48 bytes: [32..47] are the stamp's sum / count */
+    const struct SdnSealImage *image;
 } SdnSealBrush;
 
 /* Several frames may be rendered TOGETHER by one loop ("frame group": the shards of consecutive frames of a camera path / of
@@ -488,7 +505,7 @@ typedef struct SdnRenderCtx {
     float *rays_tend;
     /* optional SealD edit: a bounding-box, anchor or brush seal mapper (SdnSealBox::kind) applied to every iteration's samples between the
      * marcher and the field network (sdn_seal_bbox_map(_source) / sdn_seal_anchor_map / sdn_seal_brush_map) and to the colours of the mapped samples after
-     * it (sdn_seal_modify_hsv / _rgb); NULL = no edit */
+     * it (sdn_seal_modify_hsv / _rgb, then a brush's texture stamp, sdn_seal_modify_image); NULL = no edit */
     const struct SdnSealBox *seal;
     uint8_t *seal_mask;        /* [M_cap] scratch, required with `seal` */
     /* optional frame group (n_group_frames > 1; N = n_group_frames * rays_per_frame): frame f marches frame_bitfield[f], its field
@@ -634,6 +651,26 @@ int sdn_seal_modify_rgb_whole_rays(float *rgbs, const uint8_t *mask, const int32
                                    uint32_t M, uint32_t N, float T_thresh, uint32_t max_steps, float r, float g, float b,
                                    float light_offset, void *scratch, int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter,
                                    void *stream);
+/* The texel records of SdnSealImage::texels, in place: texels [n][4] (device, 16-byte aligned) = r, g, b, alpha per texel on entry,
+ * hue / 6, saturation, value (color_utils.py:31-46, the helper sdn_seal_modify_rgb converts its target colour with), alpha on return. */
+int sdn_seal_image_texels(float *texels, uint64_t n, void *stream);
+/* The brush's texture stamp, the `image` branch of SealMapper.map_color (seal_utils.py:58-79), on the masked samples, in place.  xyzs
+ * [M,3]: the MAPPED positions of the samples (the buffer sdn_seal_brush_map ran on).  Pass 1: the fixed-point sum and count of V over the
+ * call's masked samples, as in sdn_seal_modify_rgb -- all of them, whatever texel they land on.  Pass 2, per masked sample, the
+ * reference's fp32 statements in their order: project_points (:736-744), the texel index with its clamps, one 16-byte texel read,
+ * modify_rgb (:761-777) with the texel's colour as the target -- its hue and saturation, brightness V(texel) + (V(sample) - mean) +
+ * light_offset clamped to [0, 1] --, then alpha * modified + (1 - alpha) * colour.  A call without a masked sample changes nothing.
+ * scratch16: 16 bytes of device memory, 8-byte aligned (cleared by the call), not shared with a tint that may still be running;
+ * live_idx / live_count / state as for sdn_seal_modify_rgb.  Three stream operations, no host synchronisation. */
+int sdn_seal_modify_image(float *rgbs, const float *xyzs, const uint8_t *mask, uint32_t M, const SdnSealImage *image, void *scratch16,
+                          const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state, void *stream);
+/* sdn_seal_modify_image for the one-pass renderer, the counterpart of sdn_seal_modify_rgb_whole_rays: every masked sample is stamped
+ * with the mean V of the masked samples of ITS iteration of sdn_whole_rays_schedule (run by this call).  scratch: 16 * (max_steps + 8)
+ * bytes of device memory, 8-byte aligned (cleared by the call). */
+int sdn_seal_modify_image_whole_rays(float *rgbs, const float *xyzs, const uint8_t *mask, const int32_t *rays, const float *sigmas,
+                                     const float *deltas, uint32_t M, uint32_t N, float T_thresh, uint32_t max_steps,
+                                     const SdnSealImage *image, void *scratch, int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter,
+                                     void *stream);
 
 /* Read-back memory for the frame drivers: 32 bytes per ray group of coherent, device-mapped host memory.  When `host_snap`
  * comes from here the loop kernels publish every iteration's survivor count into it with one 64-bit system-scope store and

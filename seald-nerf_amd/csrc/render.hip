@@ -87,6 +87,11 @@ static int seal_color(const SdnRenderCtx &c, uint32_t m_slots, hipStream_t st) {
         rc = sdn_seal_modify_rgb(c.rgbs, c.seal_mask, m_slots, s->rgb[0], s->rgb[1], s->rgb[2], s->rgb_light_offset, s->scratch, c.live_idx,
                                  sdn_int::live_counters(c), c.state, st);
     }
+    if (!rc && s->kind == SDN_SEAL_BRUSH && c.seal_brush && c.seal_brush->image) {     // the texture stamp, on the MAPPED positions: xyzs were mapped in place
+        if (!s->scratch) return SDN_E_BADARG;
+        rc = sdn_seal_modify_image(c.rgbs, c.xyzs, c.seal_mask, m_slots, c.seal_brush->image, (char *)s->scratch + 32, c.live_idx,
+                                   sdn_int::live_counters(c), c.state, st);
+    }
     return rc;
 }
 

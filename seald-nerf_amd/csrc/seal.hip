@@ -11,6 +11,7 @@
 //   only in calls that map at least one sample: the early return of :251-252 comes first)
 //   SealAnchorMapper.map_to_origin :522-578 with project_points :736-744 (the cone / plane-side deformation, see k_seal_anchor_apply)
 //   SealBrushMapper.map_to_origin :415-461 (the surface pushed along the stroke's normal, attenuated towards the stroke's border, see k_seal_brush_map)
+//   the `image` branch of map_color :58-79 (the brush's `imageConfig` texture stamp: a texel per sample is modify_rgb's target, alpha-blended, see seal_image_stamp)
 // The reference evaluates this with boolean-mask gathers / scatters and O(points x triangles) temporaries in torch, inside the
 // render loop; here it is one lane per sample slot, in place, between the marcher and the field kernel.  Dot products are
 // accumulated x, y, z in fp32 (torch's einsum order is library-defined): masks agree with the torch restatement except for
@@ -524,6 +525,72 @@ __global__ void __launch_bounds__(256) k_seal_rgb_apply_iter(float *__restrict__
     seal_rgb_tint(rgbs, i, tr, tg, tb, light_offset, acc + 2 * (size_t)it);
 }
 
+// ---- the brush's texture stamp, the `image` branch of SealMapper.map_color, seal_utils.py:58-79 -------------------------------------------
+// A streaming pass: per masked sample 12 + 12 bytes of position and colour in, one 16-byte texel record, 12 bytes out.  The texture is
+// read straight from global memory (a 256 x 256 stamp is 1 MiB of records: it stays in L2); nothing is staged in LDS.
+struct SealImageArgs {
+    const float4 *texels;      // [H][W]: hue / 6, saturation, value of the texel (rgb_to_hsv, once, k_seal_image_texels), alpha
+    uint32_t W, H;
+    float v_o[3], v_norm[3], v_ow[3], v_oh[3];
+    float norm_sq, len_ow_sq, len_oh_sq, light_offset;
+};
+
+// r, g, b, alpha -> hue / 6, saturation, value, alpha, in place: what modify_rgb's `rgb2hsv_torch(modification)` gives for this texel,
+// by the helper the per-sample conversion uses -- the same values as converting the texel for every sample
+__global__ void __launch_bounds__(256) k_seal_image_texels(float4 *__restrict__ texels, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 t = texels[i];
+    float h, s, v;
+    rgb_to_hsv(t.x, t.y, t.z, h, s, v);
+    texels[i] = make_float4(h, s, v, t.w);
+}
+
+// pass 2 of one sample, the reference's fp32 statements in their order (dot products accumulated x, y, z).  acc: the {sum, count} pair of
+// the call the slot belongs to (count != 0)
+__device__ __forceinline__ void seal_image_stamp(float *__restrict__ rgbs, const float *__restrict__ xyzs, uint32_t i, const SealImageArgs &A,
+                                                 const unsigned long long *__restrict__ acc) {
+    const float mean = (float)(((double)acc[0] / 1099511627776.0) / (double)acc[1]);
+    const float px = xyzs[(size_t)i * 3], py = xyzs[(size_t)i * 3 + 1], pz = xyzs[(size_t)i * 3 + 2];
+    // project_points(v_image_norm, v_image_o, points), :736-744
+    const float along = dot3(px - A.v_o[0], py - A.v_o[1], pz - A.v_o[2], A.v_norm[0], A.v_norm[1], A.v_norm[2]) / A.norm_sq;
+    const float qx = px - along * A.v_norm[0], qy = py - along * A.v_norm[1], qz = pz - along * A.v_norm[2];
+    const float ox = qx - A.v_o[0], oy = qy - A.v_o[1], oz = qz - A.v_o[2];                      // v_op
+    // idx = min(max(0, floor(v_op . v_ow / len_ow^2 * W)), W - 1), :72-75 (fmaxf sends a NaN to texel 0: the index stays in bounds)
+    const float fw = floorf(dot3(ox, oy, oz, A.v_ow[0], A.v_ow[1], A.v_ow[2]) / A.len_ow_sq * (float)A.W);
+    const float fh = floorf(dot3(ox, oy, oz, A.v_oh[0], A.v_oh[1], A.v_oh[2]) / A.len_oh_sq * (float)A.H);
+    // (the upper clamp is taken on integers: (float)(W - 1) may round up for W > 2^24; W, H < 2^28)
+    const uint32_t iw = min((uint32_t)fminf(fmaxf(fw, 0.0f), 268435456.0f), A.W - 1u);
+    const uint32_t ih = min((uint32_t)fminf(fmaxf(fh, 0.0f), 268435456.0f), A.H - 1u);
+    const float4 tex = A.texels[(size_t)ih * A.W + iw];
+    // modify_rgb(colors, image[idx_h, idx_w], rgb_light_offset), :761-777
+    const float r = rgbs[(size_t)i * 3], g = rgbs[(size_t)i * 3 + 1], b = rgbs[(size_t)i * 3 + 2];
+    float h, s, v;
+    rgb_to_hsv(r, g, b, h, s, v);
+    const float nv = fminf(1.0f, fmaxf(0.0f, (tex.z + (v - mean)) + A.light_offset));
+    float o0, o1, o2;
+    hsv_to_rgb(tex.x, tex.y, nv, o0, o1, o2);
+    // colors = mask * modified + (1 - mask) * colors, :79
+    const float a = tex.w, na = 1.0f - tex.w;
+    rgbs[(size_t)i * 3] = a * o0 + na * r; rgbs[(size_t)i * 3 + 1] = a * o1 + na * g; rgbs[(size_t)i * 3 + 2] = a * o2 + na * b;
+}
+__global__ void __launch_bounds__(256) k_seal_image_apply(float *__restrict__ rgbs, const float *__restrict__ xyzs, const uint8_t *__restrict__ mask, uint32_t M,
+                                                          SealImageArgs A, const unsigned long long *__restrict__ acc) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M || !mask[i] || acc[1] == 0ull) return;      // (as k_seal_rgb_apply: none of the call's samples is masked -> nothing changes)
+    seal_image_stamp(rgbs, xyzs, i, A, acc);
+}
+// the stamp of a whole-ray sample list: a masked slot is stamped with the mean of its own iteration (as k_seal_rgb_apply_iter)
+__global__ void __launch_bounds__(256) k_seal_image_apply_iter(float *__restrict__ rgbs, const float *__restrict__ xyzs, const uint8_t *__restrict__ mask,
+                                                               const int32_t *__restrict__ slot_iter, uint32_t M, SealImageArgs A,
+                                                               const unsigned long long *__restrict__ acc) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M || !mask[i]) return;
+    const int32_t it = slot_iter[i];
+    if (it == kNoIteration || acc[2 * (size_t)it + 1] == 0ull) return;
+    seal_image_stamp(rgbs, xyzs, i, A, acc + 2 * (size_t)it);
+}
+
 // color_utils.py:31-63 + seal_utils.py:747-758 on the masked samples, in place
 __global__ void __launch_bounds__(256) k_seal_hsv(float *__restrict__ rgbs, const uint8_t *__restrict__ mask, uint32_t M, float mh, float ms, float mv) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -567,6 +634,15 @@ int fill_box_test(SealBoxTest &b, const float *bounds, uint32_t n_bounds, const 
         for (int j = 0; j < 6; j++) b.bounds[k][j] = bounds[6 * k + j];
     b.n_bounds = n_bounds; b.tris = tris; b.n_tris = n_tris;
     for (int k = 0; k < 3; k++) b.test_dir[k] = test_dir[k];
+    return 0;
+}
+
+int fill_image_args(SealImageArgs &a, const SdnSealImage *im) {
+    if (!im || !im->texels || ((uintptr_t)im->texels & 15u) != 0) return SDN_E_BADARG;
+    if (im->W == 0 || im->H == 0 || (uint64_t)im->W * im->H >= (1ull << 28)) return SDN_E_UNSUPPORTED;
+    a.texels = (const float4 *)im->texels; a.W = im->W; a.H = im->H;
+    for (int k = 0; k < 3; k++) { a.v_o[k] = im->v_o[k]; a.v_norm[k] = im->v_norm[k]; a.v_ow[k] = im->v_ow[k]; a.v_oh[k] = im->v_oh[k]; }
+    a.norm_sq = im->norm_sq; a.len_ow_sq = im->len_ow_sq; a.len_oh_sq = im->len_oh_sq; a.light_offset = im->light_offset;
     return 0;
 }
 
@@ -706,6 +782,49 @@ int sdn_seal_modify_rgb_whole_rays(float *rgbs, const uint8_t *mask, const int32
     hipLaunchKernelGGL(k_seal_rgb_sum_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, (const float *)rgbs, mask, (const int32_t *)slot_iter, M,
                        (unsigned long long *)scratch);
     hipLaunchKernelGGL(k_seal_rgb_apply_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, rgbs, mask, (const int32_t *)slot_iter, M, r, g, b, light_offset,
+                       (const unsigned long long *)scratch);
+    return sdn_launch_status();
+}
+
+int sdn_seal_image_texels(float *texels, uint64_t n, void *stream) {
+    if (n == 0) return 0;
+    if (!texels || ((uintptr_t)texels & 15u) != 0) return SDN_E_BADARG;
+    if (n >= (1ull << 28)) return SDN_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_seal_image_texels, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream, (float4 *)texels, n);
+    return sdn_launch_status();
+}
+
+// The `image` branch of map_color (seal_utils.py:58-79) on the masked samples, in place; xyzs: their mapped positions.  The sum pass is
+// sdn_seal_modify_rgb's (k_seal_rgb_sum: every masked sample of the call, wherever it lands on the texture).  Three stream operations.
+int sdn_seal_modify_image(float *rgbs, const float *xyzs, const uint8_t *mask, uint32_t M, const SdnSealImage *image, void *scratch16,
+                          const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state, void *stream) {
+    if (M == 0) return 0;
+    if (!rgbs || !xyzs || !mask || !scratch16 || ((uintptr_t)scratch16 & 7u) != 0 || (live_idx && !live_count)) return SDN_E_BADARG;
+    SealImageArgs a;
+    if (int rc = fill_image_args(a, image)) return rc;
+    if (hipMemsetAsync(scratch16, 0, 16, (hipStream_t)stream) != hipSuccess) return sdn_launch_status();
+    const SealSlots L{live_idx, live_count, state, M};
+    hipLaunchKernelGGL(k_seal_rgb_sum, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, (const float *)rgbs, mask, L, (unsigned long long *)scratch16);
+    hipLaunchKernelGGL(k_seal_image_apply, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, rgbs, xyzs, mask, M, a,
+                       (const unsigned long long *)scratch16);
+    return sdn_launch_status();
+}
+
+// The stamp on a whole-ray sample list, as the inference loop applies it: sdn_whole_rays_schedule, the per-iteration sum pass of
+// sdn_seal_modify_rgb_whole_rays, then the per-iteration stamp.  scratch: 16 * (max_steps + 8) bytes, 8-byte aligned (cleared here).
+int sdn_seal_modify_image_whole_rays(float *rgbs, const float *xyzs, const uint8_t *mask, const int32_t *rays, const float *sigmas, const float *deltas,
+                                     uint32_t M, uint32_t N, float T_thresh, uint32_t max_steps, const SdnSealImage *image, void *scratch,
+                                     int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter, void *stream) {
+    if (M == 0 || N == 0) return 0;
+    if (!rgbs || !xyzs || !mask || !scratch || ((uintptr_t)scratch & 7u) != 0) return SDN_E_BADARG;
+    SealImageArgs a;
+    if (int rc = fill_image_args(a, image)) return rc;
+    if (int rc = sdn_whole_rays_schedule(rays, sigmas, deltas, M, N, T_thresh, max_steps, ray_stop, slot_iter, n_iter, stream)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(scratch, 0, 16 * ((size_t)max_steps + 8), st) != hipSuccess) return sdn_launch_status();
+    hipLaunchKernelGGL(k_seal_rgb_sum_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, (const float *)rgbs, mask, (const int32_t *)slot_iter, M,
+                       (unsigned long long *)scratch);
+    hipLaunchKernelGGL(k_seal_image_apply_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, rgbs, xyzs, mask, (const int32_t *)slot_iter, M, a,
                        (const unsigned long long *)scratch);
     return sdn_launch_status();
 }

@@ -467,7 +467,7 @@ def render_frame(model, rays_o, rays_d, time, fp16=False, dt_gamma=0.0, max_step
         else:
             sigmas, rgbs = evaluate(q_xyzs, q_dirs)
         if native_map:
-            mapper.map_color_(rgbs, mapped)
+            mapper.map_color_(rgbs, mapped, points=xyzs)      # (xyzs were mapped in place: the reference's `mapped_xyzs`, what a texture stamp looks up)
         elif mapped is not None and bool(mapped.any()):
             rgbs[mapped] = mapper.map_color(q_xyzs[mapped], q_dirs[mapped], rgbs[mapped]).to(rgbs.dtype)
         check(lib.sdn_composite_rays(n_alive, n_step, float(T_thresh), ptr(alive), ptr(ws.rays_t), ptr(sigmas), ptr(rgbs), ptr(deltas),
@@ -591,11 +591,12 @@ class DeviceLoop:
         mapper.map_data_conversion(self.buf["xyzs"])
         a = mapper._native_args(dev)
         anchor, brush = isinstance(mapper, SealAnchorMapper), isinstance(mapper, SealBrushMapper)
-        if self.frames > 1 and (anchor or mapper.redirects_source or "rgb" in mapper.map_data):
-            # these look at ALL samples of a loop iteration (the mean brightness of the masked ones, "does the call map anything" of
-            # mapSource and of the anchor mapper): in a frame group an iteration holds several frames' samples, which the reference never mixes
-            # (the brush maps every sample on its own: without a tint it runs on frame groups)
-            raise NotImplementedError("mapSource / rgb tint / the anchor mapper depend on the set of samples of an iteration: render such edits one frame per loop")
+        if self.frames > 1 and (anchor or mapper.redirects_source or "rgb" in mapper.map_data or "image" in mapper.map_data):
+            # these look at ALL samples of a loop iteration (the mean brightness of the masked ones -- the tint's and the texture stamp's --,
+            # "does the call map anything" of mapSource and of the anchor mapper): in a frame group an iteration holds several frames'
+            # samples, which the reference never mixes (the brush maps every sample on its own: without a tint or a stamp it runs on frame groups)
+            raise NotImplementedError("mapSource / rgb tint / texture stamp / the anchor mapper depend on the set of samples of an iteration: "
+                                      "render such edits one frame per loop")
         box = SdnSealBox()
         for k in range(6 * a["n_bounds"]):
             box.bounds[k] = a["bounds"][k]
@@ -609,6 +610,7 @@ class DeviceLoop:
                 rec.normal_expand[k], rec.center[k] = a["normal_expand"][k], a["center"][k]
             rec.attenuation_distance, rec.mode = a["attenuation_distance"], a["mode"]
             rec.border, rec.n_border = a["border"].data_ptr(), a["n_border"]
+            rec.image = ctypes.addressof(a["image"]) if "image" in a else None      # the texture stamp (`a` is kept alive below)
         elif anchor:
             fields = (("test_dir", 3), ("scale", 3), ("v_anchor", 3), ("v_offset", 3), ("v_h", 3))
             box.len_h, box.radius = a["len_h"], a["radius"]
@@ -628,10 +630,11 @@ class DeviceLoop:
             for k in range(3):
                 box.map_source[k] = a["map_source"][k]
             box.has_map_source = 1
-        # the record's 32 scratch bytes (modify_rgb's sum / count, the mapSource / anchor flag word) belong to THIS loop, zeroed once: the loops
-        # of a PipelinedDeviceLoop share the mapper and run on their own streams, and one buffer between them would let one loop's
-        # memset / sums land in another's mean brightness, and a later loop's mapSource tag cancel an earlier one's redirect
-        scratch = torch.zeros(32, dtype=torch.uint8, device=dev)
+        # the record's scratch bytes (modify_rgb's sum / count, the mapSource / anchor flag word, the texture stamp's sum / count in
+        # [32..47]) belong to THIS loop, zeroed once: the loops of a PipelinedDeviceLoop share the mapper and run on their own streams, and
+        # one buffer between them would let one loop's memset / sums land in another's mean brightness, and a later loop's mapSource tag
+        # cancel an earlier one's redirect
+        scratch = torch.zeros(48, dtype=torch.uint8, device=dev)
         box.scratch = scratch.data_ptr()
         mask = torch.empty(self.buf["sigmas"].shape[0], dtype=torch.uint8, device=dev)
         self._seal = (box, mask, a, scratch, rec)      # keep the records, the mask, the triangle / border tensors and the scratch alive
@@ -997,7 +1000,8 @@ class RayBatchRenderer:
     iteration follows from the sample counts, the sigmas and the rule n_step = max(min(N // n_alive, 8), 1) -- colours never decide
     when a ray dies -- so after the field launch `sdn_seal_modify_rgb_whole_rays` replays the loop's schedule on the device
     (`loop_schedule` below states it in Python) and tints every masked sample by the mean of its own iteration: the loop's colours bit
-    for bit, six more stream operations, no read-back.  `mapSource` stays with the loops: its redirect moves samples, so it changes the
+    for bit, six more stream operations, no read-back.  A brush's texture stamp (`imageConfig`) re-centres on the same kind of mean and takes
+    the same replay (`sdn_seal_modify_image_whole_rays`).  `mapSource` stays with the loops: its redirect moves samples, so it changes the
     sigmas that decide the schedule that decides which calls redirect.
 
     `samples_per_ray` sizes the sample buffer (N * samples_per_ray slots); a batch that needs more loses its last rays -- `render(...,
@@ -1011,9 +1015,9 @@ class RayBatchRenderer:
             #  decide the iterations: nothing to replay after the fact.  The tint is replayed, see above.  The anchor mapper's early return
             #  is no such case: its box contains its cone, so an iteration without a sample in the box holds no sample to map either)
             raise NotImplementedError("mapSource depends on the loop's iterations: use render_frame / DeviceLoop for such edits")
-        tint = mapper is not None and "rgb" in mapper.map_data
+        tint = mapper is not None and ("rgb" in mapper.map_data or "image" in mapper.map_data)      # (the brush's texture stamp takes a mean per iteration too)
         if tint and int(N) > int(B.lib.sdn_whole_rays_schedule_max_rays()):
-            raise NotImplementedError(f"the rgb tint's schedule replay holds at most {int(B.lib.sdn_whole_rays_schedule_max_rays())} rays "
+            raise NotImplementedError(f"the rgb tint's / texture stamp's schedule replay holds at most {int(B.lib.sdn_whole_rays_schedule_max_rays())} rays "
                                       f"(N = {N}): render larger batches with DeviceLoop")
         self.model, self.field, self.N, self.device, self.mapper = model, field, int(N), torch.device(device), mapper
         self.max_steps, self.T_thresh, self.dt_gamma = int(max_steps), float(T_thresh), float(dt_gamma)
@@ -1041,6 +1045,7 @@ class RayBatchRenderer:
             i32 = torch.int32
             self._tint = SimpleNamespace(rays=self.rays, sigmas=None, deltas=self.deltas, N=self.N, T_thresh=self.T_thresh, max_steps=self.max_steps,
                                          scratch=torch.zeros(16 * (self.max_steps + 8), dtype=torch.uint8, device=dev),
+                                         image_scratch=torch.zeros(16 * (self.max_steps + 8), dtype=torch.uint8, device=dev),      # the stamp's own sums
                                          ray_stop=torch.zeros(self.N, 2, dtype=i32, device=dev),
                                          slot_iter=torch.full((self.M,), -1, dtype=i32, device=dev), n_iter=torch.zeros(1, dtype=i32, device=dev))
 
@@ -1066,9 +1071,9 @@ class RayBatchRenderer:
         sigmas, rgbs = self.field(self.xyzs, self.dirs, live_idx=self.identity, live_count=self.count)
         if self._tint is not None:
             self._tint.sigmas = sigmas
-            self.mapper.map_color_(rgbs, mask, whole_rays=self._tint)
+            self.mapper.map_color_(rgbs, mask, whole_rays=self._tint, points=self.xyzs)
         elif mask is not None:
-            self.mapper.map_color_(rgbs, mask)
+            self.mapper.map_color_(rgbs, mask, points=self.xyzs)
         B.check(lib.sdn_composite_whole_rays(B.ptr(sigmas), B.ptr(rgbs), B.ptr(self.deltas), B.ptr(self.rays), B.ptr(self.nears), self.M, self.N,
                                              self.T_thresh, B.ptr(self.weights_sum), B.ptr(self.depth), B.ptr(self.image), st), "composite_whole_rays")
         bg = bg_color if isinstance(bg_color, torch.Tensor) else float(bg_color)

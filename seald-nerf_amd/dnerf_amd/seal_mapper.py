@@ -2,7 +2,8 @@
 student renderers hook between the marcher and the field network (`map_to_origin`) and after it (`map_color`).
 
 Mirrors, with the same names and `map_data` keys, the pieces of the reference that sit inside the render loop:
-  * `SealMapper.map_mask` / `map_color` / `map_data_conversion`      SealNeRF/seal_utils.py:40-153
+  * `SealMapper.map_mask` / `map_color` (hsv, rgb and the brush's
+    `image` texture stamp) / `map_data_conversion`                   SealNeRF/seal_utils.py:40-153
   * `SealBBoxMapper.__init__` / `map_to_origin`                      SealNeRF/seal_utils.py:156-286
   * `SealAnchorMapper.__init__` / `map_to_origin`, `project_points`  SealNeRF/seal_utils.py:464-578, 736-744
   * `SealBrushMapper.__init__` / `map_to_origin`, `get_trimesh_fit`,
@@ -19,6 +20,7 @@ PCA-aligned box.  Everything is plain torch on whatever device the points live o
 operators; colour conversions are pinned by vectors generated from the reference's pure-torch `color_utils` (tests/golden).
 """
 import itertools
+import os
 
 import numpy as np
 import torch
@@ -64,6 +66,7 @@ def modify_hsv(rgb, modification):
 
 
 def modify_rgb(rgb, modification, light_offset=0.0):
+    """modification: one target colour [3], or one per sample [N,3] (the texture stamp's texels, seal_utils.py:77-78)."""
     if rgb.shape[0] == 0:
         return rgb
     hsl = rgb2hsv(rgb)
@@ -178,6 +181,25 @@ class SealMapper:
             colors = modify_hsv(colors, self.map_data["hsv"])
         if "rgb" in self.map_data:
             colors = modify_rgb(colors, self.map_data["rgb"], float(self.map_data["rgb_light_offset"]))
+        if "image" in self.map_data:
+            # seal_utils.py:58-79, statement by statement.  points: the MAPPED positions of the samples `colors` belongs to
+            if points is None:
+                raise ValueError("map_color: a mapper with an `image` needs the (mapped) points of the colours")
+            image = self.map_data["image"]
+            H, W, C = image.shape
+            v_norm, v_o, v_w, v_h = (self.map_data[k] for k in ("v_image_norm", "v_image_o", "v_image_w", "v_image_h"))
+            projected_points = project_points(v_norm, v_o, points)
+            v_op = projected_points - v_o
+            v_ow = v_w - v_o
+            v_oh = v_h - v_o
+            len_ow = torch.norm(v_ow, 2)
+            len_oh = torch.norm(v_oh, 2)
+            zero = torch.tensor(0., device=points.device)
+            idx_w = torch.min(torch.max(zero, torch.floor(v_op @ v_ow.T / len_ow ** 2 * W)), torch.tensor(W - 1, device=points.device)).to(torch.long)
+            idx_h = torch.min(torch.max(zero, torch.floor(v_op @ v_oh.T / len_oh ** 2 * H)), torch.tensor(H - 1, device=points.device)).to(torch.long)
+            mask = self.map_data["image_mask"][idx_h, idx_w][None].T
+            modified_colors = modify_rgb(colors, image[idx_h, idx_w], float(self.map_data["rgb_light_offset"]))    # the mean V: of ALL colours of the call
+            colors = mask * modified_colors + (1 - mask) * colors
         return colors
 
     def map_to_origin(self, points, dirs=None):
@@ -221,22 +243,56 @@ class SealMapper:
             if "rgb" in md:
                 self._native["rgb"] = [float(v) for v in f32(md["rgb"].reshape(3))]
                 self._native["rgb_light_offset"] = float(np.float32(md["rgb_light_offset"]))
+            if "image" in md:
+                self._native.update(self._native_image_args(md, f32, device))
             self._native_key = key
         return self._native
+
+    def _native_image_args(self, md, f32, device):
+        """The texture stamp's device record (`SdnSealImage`): the texels as 16-byte records {hue / 6, saturation, value, alpha} -- converted
+        once, on the device, by the helper the kernels convert colours with -- and the plane constants, each taken in fp32 as the
+        reference's statements take it (v_w - v_o, torch.norm(.)**2, plane_norm @ plane_norm on fp32 tensors).  Also 16 bytes of scratch
+        of the stamp's own (its sum / count is not the tint's)."""
+        from sdn_backend import SdnSealImage, lib, check, ptr, stream
+        H, W = md["image"].shape[:2]
+        texels = torch.from_numpy(np.concatenate([f32(md["image"]), f32(md["image_mask"])[..., None]], axis=-1).reshape(-1, 4)).to(device).contiguous()
+        check(lib.sdn_seal_image_texels(ptr(texels), H * W, stream()), "seal_image_texels")
+        torch.cuda.current_stream().synchronize()        # once per mapper and device: later calls may come on other streams
+        v_o, v_w, v_h, v_n = (torch.from_numpy(f32(md[k].reshape(3))) for k in ("v_image_o", "v_image_w", "v_image_h", "v_image_norm"))
+        v_ow, v_oh = v_w - v_o, v_h - v_o
+        rec = SdnSealImage()
+        rec.texels, rec.W, rec.H = texels.data_ptr(), W, H
+        for k in range(3):
+            rec.v_o[k], rec.v_norm[k], rec.v_ow[k], rec.v_oh[k] = float(v_o[k]), float(v_n[k]), float(v_ow[k]), float(v_oh[k])
+        rec.norm_sq, rec.len_ow_sq, rec.len_oh_sq = float(v_n @ v_n), float(torch.norm(v_ow, 2) ** 2), float(torch.norm(v_oh, 2) ** 2)
+        rec.light_offset = float(np.float32(md["rgb_light_offset"]))
+        return dict(image=rec, image_texels=texels, image_scratch=torch.zeros(16, dtype=torch.uint8, device=device))
 
     def map_to_origin_(self, points, dirs):
         raise NotImplementedError()
 
     @torch.no_grad()
-    def map_color_(self, rgbs, mask, whole_rays=None):
-        """In-place `map_color` of the masked samples (seal_utils.py:48-57: the hsv modification, then the rgb tint): HIP kernels on CUDA
-        fp32 buffers, the torch restatement otherwise (and for an `image` modification, which the mappers of this build do not carry).
+    def map_color_(self, rgbs, mask, whole_rays=None, points=None):
+        """In-place `map_color` of the masked samples (seal_utils.py:48-79: the hsv modification, then the rgb tint, then the brush's
+        texture stamp): HIP kernels on CUDA fp32 buffers, the torch restatement otherwise.
+
+        points: the MAPPED positions [M,3] of the samples (the buffer `map_to_origin_` ran on; the reference's `mapped_xyzs`), required
+        when the mapper carries an `image`: the stamp looks its texel up by position.
 
         whole_rays: the buffers hold EVERY sample of a ray batch (march_rays_train's layout; `RayBatchRenderer`), not one loop iteration's:
         the record of that list -- rays [N,3], sigmas, deltas, N, T_thresh, max_steps and the renderer's work buffers scratch, ray_stop,
         slot_iter, n_iter (`sdn_seal_modify_rgb_whole_rays`) -- so that the tint re-centres each sample on the mean brightness of the
-        loop iteration it would have been part of.  Only the tint looks at it; there is no torch restatement of that form."""
-        if rgbs.is_cuda and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and "image" not in self.map_data:
+        loop iteration it would have been part of.  Only the tint and the stamp look at it (both take one mean per iteration); there is no
+        torch restatement of that form."""
+        stamp = "image" in self.map_data
+        if stamp and points is None:
+            raise ValueError("map_color_: a mapper with an `image` needs the (mapped) points of the samples")
+        native = rgbs.is_cuda and rgbs.dtype == torch.float32 and rgbs.is_contiguous()
+        if stamp:
+            if points.shape[0] != rgbs.shape[0]:
+                raise ValueError(f"map_color_: {points.shape[0]} points for {rgbs.shape[0]} colours")
+            native = native and points.is_cuda and points.dtype == torch.float32 and points.is_contiguous()
+        if native:
             from sdn_backend import lib, check, ptr, stream
             m8 = mask.view(torch.uint8)
             if "hsv" in self.map_data:
@@ -255,10 +311,24 @@ class SealMapper:
                 else:
                     check(lib.sdn_seal_modify_rgb(ptr(rgbs), ptr(m8), rgbs.shape[0], c[0], c[1], c[2], a["rgb_light_offset"], ptr(a["scratch"]),
                                                   None, None, None, stream()), "seal_modify_rgb")
-        elif whole_rays is not None and "rgb" in self.map_data:
-            raise NotImplementedError("the whole-ray rgb tint is a device kernel (CUDA fp32 contiguous colours)")
+            if stamp:         # after the tint, on the tinted colours; its sum / count in scratch of its own
+                import ctypes
+                a = self._native_args(rgbs.device)
+                rec = ctypes.addressof(a["image"])
+                if whole_rays is not None:
+                    w = whole_rays
+                    check(lib.sdn_seal_modify_image_whole_rays(ptr(rgbs), ptr(points), ptr(m8), ptr(w.rays, torch.int32, "rays"), ptr(w.sigmas, torch.float32, "sigmas"),
+                                                               ptr(w.deltas, torch.float32, "deltas"), rgbs.shape[0], w.N, w.T_thresh, w.max_steps, rec,
+                                                               ptr(w.image_scratch), ptr(w.ray_stop, torch.int32, "ray_stop"),
+                                                               ptr(w.slot_iter, torch.int32, "slot_iter"), ptr(w.n_iter, torch.int32, "n_iter"), stream()),
+                          "seal_modify_image_whole_rays")
+                else:
+                    check(lib.sdn_seal_modify_image(ptr(rgbs), ptr(points), ptr(m8), rgbs.shape[0], rec, ptr(a["image_scratch"]), None, None, None, stream()),
+                          "seal_modify_image")
+        elif whole_rays is not None and ("rgb" in self.map_data or stamp):
+            raise NotImplementedError("the whole-ray rgb tint / texture stamp is a device kernel (CUDA fp32 contiguous colours and points)")
         elif bool(mask.any()):
-            rgbs[mask] = self.map_color(None, None, rgbs[mask]).to(rgbs.dtype)
+            rgbs[mask] = self.map_color(points[mask] if stamp else None, None, rgbs[mask]).to(rgbs.dtype)
         return rgbs
 
 
@@ -588,6 +658,41 @@ def brush_triangle_records(triangles, test_dir):
 
 
 _BRUSH_MODES = {"linear": 0, "dry": 1}
+MAX_STAMP_TEXELS = 1 << 28     # the device record's texel index (SdnSealImage: H * W below this)
+
+
+def load_stamp(path, config_path=None):
+    """The brush's texture file as the reference's constructor holds it (seal_utils.py:392-401) -> (image [H,W,3] float32 = RGB / 255,
+    image_mask [H,W] float64 = alpha / 255, or ones without an alpha channel).  Loaded with PIL (the reference uses cv2, which only
+    decodes): an 8-bit RGB or RGBA file; for a lossless format (PNG) the arrays are what cv2 hands over, no parity is claimed for
+    lossy ones.  `path` is tried as given, then relative to `config_path` (the edit's directory, or a file in it).  Anything that cannot
+    be loaded here -- no such file, not an image, no PIL, 16-bit or palette-free grayscale data -- raises NotImplementedError naming
+    the path and the cause."""
+    tried = [path]
+    if config_path is not None and not os.path.isabs(path):
+        base = config_path if os.path.isdir(config_path) else os.path.dirname(config_path)
+        tried.append(os.path.join(base, path))
+    found = next((p for p in tried if os.path.isfile(p)), None)
+    if found is None:
+        raise NotImplementedError(f"the brush's `imageConfig` texture {path!r}: no such file (tried {tried})")
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise NotImplementedError(f"the brush's `imageConfig` texture {found!r}: PIL is needed to load it ({e})") from e
+    try:
+        with Image.open(found) as im:
+            mode, (width, height) = im.mode, im.size
+            raw = np.asarray(im) if mode in ("RGB", "RGBA") and width * height < MAX_STAMP_TEXELS else None
+    except Exception as e:
+        raise NotImplementedError(f"the brush's `imageConfig` texture {found!r} cannot be decoded: {e}") from e
+    if width * height >= MAX_STAMP_TEXELS:
+        raise ValueError(f"the brush's `imageConfig` texture {found!r} has {height} x {width} texels: at most 2^28 - 1")
+    if raw is None or raw.dtype != np.uint8 or raw.ndim != 3 or raw.shape[2] not in (3, 4):
+        raise NotImplementedError(f"the brush's `imageConfig` texture {found!r}: mode {mode!r} -- only 8-bit RGB / RGBA files are loaded "
+                                  "(16-bit data, palettes and grayscale without a channel axis are not)")
+    image = raw[:, :, :3].astype(np.float32) / 255
+    alpha = raw[:, :, 3] / 255 if raw.shape[2] == 4 else np.ones(raw.shape[:2])
+    return image, alpha
 
 
 class SealBrushMapper(SealMapper):
@@ -607,8 +712,16 @@ class SealBrushMapper(SealMapper):
     groups.
 
     As in the reference, `normal_expand`, `center` and the ray test's direction (`map_test_dir`, not normalised) are the LAST stroke's:
-    all strokes are assumed to lie in one plane.  Not built: `imageConfig` (the texture stamp, needs cv2) and the 'ease-in' /
-    'ease-out' modes (unimplemented in the reference too) raise NotImplementedError here, at construction; `to.obj` is not written."""
+    all strokes are assumed to lie in one plane.
+
+    `imageConfig: {path, o, w, h}` stamps a texture onto the mapped samples' colours (`map_color`'s `image` branch, after hsv and rgb):
+    the file (8-bit RGB / RGBA, loaded with PIL, see `load_stamp`) lies on the parallelogram with corner `o` and edges to `w` and `h`;
+    a sample takes the texel its mapped position projects to (clamped at the edges) as `modify_rgb`'s target colour -- brightness
+    re-centred on the mean of ALL masked samples of the call, plus `rgbLightOffset` -- blended in by the texel's alpha.  On the device:
+    `sdn_seal_modify_image`.  A file this build cannot load raises NotImplementedError, a texture of 2^28 texels or more ValueError.
+
+    Not built: the 'ease-in' / 'ease-out' modes (unimplemented in the reference too) raise NotImplementedError here, at construction;
+    `to.obj` is not written."""
 
     MAX_STROKES = 4        # the device box test holds 4 bounds
 
@@ -617,8 +730,6 @@ class SealBrushMapper(SealMapper):
         missing = [k for k in ("raw", "brushType", "brushDepth", "brushPressure", "attenuationDistance", "attenuationMode") if k not in seal_config]
         if missing:
             raise NotImplementedError(f"seal mapper type 'brush' without the config keys {missing}: there is nothing to build a stroke from")
-        if "imageConfig" in seal_config:
-            raise NotImplementedError("the brush's `imageConfig` texture stamp is not built")
         mode = seal_config["attenuationMode"]
         if mode in ("ease-in", "ease-out"):
             raise NotImplementedError(f"attenuationMode {mode!r} (the reference leaves it unimplemented)")
@@ -675,6 +786,17 @@ class SealBrushMapper(SealMapper):
         if "rgb" in seal_config:
             self.map_data["rgb"] = seal_config["rgb"]
             self.map_data["rgb_light_offset"] = seal_config.get("rgbLightOffset", 0)
+        if "imageConfig" in seal_config:               # :389-411
+            image_conf = seal_config["imageConfig"]
+            self.map_data["rgb_light_offset"] = seal_config.get("rgbLightOffset", 0)
+            image, alpha = load_stamp(image_conf["path"], config_path)
+            v_o, v_w, v_h = (np.asarray(image_conf[k], dtype=np.float64).reshape(3) for k in ("o", "w", "h"))
+            self.map_data["image"] = image
+            self.map_data["image_mask"] = alpha
+            self.map_data["v_image_norm"] = best_fit_plane([v_o, v_w, v_h])[1]      # (either sign: project_points divides by n . n)
+            self.map_data["v_image_o"] = v_o
+            self.map_data["v_image_w"] = v_w
+            self.map_data["v_image_h"] = v_h
         self.map_data_conversion(force=True)
 
     def _native_map_args(self, md, f32, cfl):

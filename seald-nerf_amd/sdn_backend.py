@@ -59,6 +59,9 @@ PROTOTYPES = {
     "sdn_seal_modify_rgb": [_vp, _vp, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
     "sdn_whole_rays_schedule": [_vp, _vp, _vp, _u32, _u32, _f32, _u32, _vp, _vp, _vp, _vp],
     "sdn_seal_modify_rgb_whole_rays": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "sdn_seal_image_texels": [_vp, _u64, _vp],
+    "sdn_seal_modify_image": [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sdn_seal_modify_image_whole_rays": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
     "sdn_field_forward_f16": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp],
     "sdn_field_forward_f32": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
     "sdn_field_forward_f32x3": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
@@ -121,11 +124,18 @@ SEAL_BBOX, SEAL_ANCHOR, SEAL_BRUSH = 0, 1, 2   # SdnSealBox.kind: SDN_SEAL_BBOX,
 class SdnSealBrush(ctypes.Structure):
     """Mirror of `SdnSealBrush` in include/sdn_hip.h: the brush mapper's own arguments (`SdnRenderCtx.seal_brush`)."""
     _fields_ = [("normal_expand", _f32 * 3), ("center", _f32 * 3), ("attenuation_distance", _f32), ("mode", _u32), ("border", _vp),
-                ("n_border", _u32), ("reserved_", _u32)]
+                ("n_border", _u32), ("reserved_", _u32), ("image", _vp)]
+
+
+class SdnSealImage(ctypes.Structure):
+    """Mirror of `SdnSealImage` in include/sdn_hip.h: the brush's `imageConfig` texture stamp (`SdnSealBrush.image`)."""
+    _fields_ = [("texels", _vp), ("W", _u32), ("H", _u32), ("v_o", _f32 * 3), ("v_norm", _f32 * 3), ("v_ow", _f32 * 3), ("v_oh", _f32 * 3),
+                ("norm_sq", _f32), ("len_ow_sq", _f32), ("len_oh_sq", _f32), ("light_offset", _f32)]
 
 
 BRUSH_LINEAR, BRUSH_DRY = 0, 1   # SdnSealBrush.mode
 BRUSH_TRI_FLOATS = 16            # floats per triangle record of sdn_seal_brush_map
+SEAL_IMAGE_MAX_TEXELS = 1 << 28  # SdnSealImage: H * W below this
 
 
 TRAIN_N_PARAMS = 14   # SDN_TRAIN_N_PARAMS
