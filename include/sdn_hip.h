@@ -791,6 +791,19 @@ typedef struct SdnTrainLayout {
     uint64_t sigmas;                                           /* [M] f32 (density_scale applied) */
     uint64_t weights_sum, depth, image;                        /* [N] [N] [N,3] f32, before the background mix */
     uint64_t found_inf;                                        /* f32 [1] */
+    /* The step's intermediates, for stage-by-stage checks (appended; elements are fp16 in the fp16 step, f32 in the fp32 step, unless
+     * a type is given).  A step that has no such buffer reports 0 (enc_rm in the fp32 step). */
+    uint64_t enc_in, def_hidden, def_out;                      /* [M,80] freq(x,10) ++ freq(t,6), [7][M,128] after ReLU, [M,16] (3 used) */
+    uint64_t xdef, grid_out, enc_rm;                           /* [M,3] f32 in [0,1]; [16][M][2] level-major; fp16 step: [M,32] row-major copy */
+    uint64_t h1, hout;                                         /* sigma MLP: [M,64] after ReLU, [M,16] (column 0: log density) */
+    uint64_t col_in, col_hidden, col_out;                      /* [M,32] SH 16 ++ hout, [2][M,64] after ReLU, [M,16] (3 used, pre-sigmoid) */
+    uint64_t sq_err;                                           /* [N] f32: sum over channels of (pred - target)^2 */
+    uint64_t dcol_out, dh0;                                    /* compositing backward: [M,16] (3 used), [M]; zero where no ray owns the sample */
+    uint64_t col_bwd, dcol_in;                                 /* colour MLP backward: [2][M,64], [M,32] */
+    uint64_t dh, dh1, denc;                                    /* sigma MLP backward: [M,16], [M,64], [16][M][2] level-major */
+    uint64_t dx, ddef, def_bwd;                                /* [M,3] grid input gradient, [M,16] (3 used), [7][M,128].  col_bwd / def_bwd hold
+                                                                * the hidden layers' gradients last layer first in the fp16 step, first
+                                                                * layer first in the fp32 step; dx .. def_bwd are not written at time == 0 */
 } SdnTrainLayout;
 
 int sdn_train_layout(uint32_t N, uint32_t M, uint32_t max_steps, const int32_t *grid_offsets, SdnTrainLayout *out);

@@ -145,8 +145,16 @@ def march_rays_train(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
     return xyzs, dirs, deltas, rays
 
 
-def composite_rays_train_forward(sigmas, rgbs, deltas, rays, T_thresh=1e-4):
-    """raymarching.py:241-269 + raymarching.cu:501-577."""
+def composite_rays_train_forward(sigmas, rgbs, deltas, rays, T_thresh=1e-4, dtype=np.float32):
+    """raymarching.py:241-269 + raymarching.cu:501-577.  dtype=np.float64: the same sequential loop with every variable a double."""
+    if dtype == np.float64:
+        sigmas, rgbs, deltas = (np.ascontiguousarray(a, dtype=np.float64) for a in (sigmas, rgbs, deltas))
+        rays = _i(rays)
+        M, N = sigmas.shape[0], rays.shape[0]
+        ws, depth, image = np.empty(N), np.empty(N), np.empty((N, 3))
+        lib().orc_composite_rays_train_forward_f64(_p(sigmas), _p(rgbs), _p(deltas), _p(rays), u32(M), u32(N),
+                                                   ctypes.c_double(T_thresh), _p(ws), _p(depth), _p(image))
+        return ws, depth, image
     sigmas = _f(sigmas)
     rgbs = _f(rgbs)
     deltas = _f(deltas)
@@ -160,8 +168,17 @@ def composite_rays_train_forward(sigmas, rgbs, deltas, rays, T_thresh=1e-4):
     return ws, depth, image
 
 
-def composite_rays_train_backward(grad_ws, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, T_thresh=1e-4):
-    """raymarching.py:273-288 + raymarching.cu:602-682 (grad_depth is ignored by the reference)."""
+def composite_rays_train_backward(grad_ws, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, T_thresh=1e-4, dtype=np.float32):
+    """raymarching.py:273-288 + raymarching.cu:602-682 (grad_depth is ignored by the reference).  dtype=np.float64: all in double."""
+    if dtype == np.float64:
+        d = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        grad_ws, grad_image, sigmas, rgbs, deltas, weights_sum, image = (d(a) for a in (grad_ws, grad_image, sigmas, rgbs, deltas, weights_sum, image))
+        rays = _i(rays)
+        M, N = sigmas.shape[0], rays.shape[0]
+        gs, gc = np.zeros_like(sigmas), np.zeros_like(rgbs)
+        lib().orc_composite_rays_train_backward_f64(_p(grad_ws), _p(grad_image), _p(sigmas), _p(rgbs), _p(deltas), _p(rays), _p(weights_sum),
+                                                    _p(image), u32(M), u32(N), ctypes.c_double(T_thresh), _p(gs), _p(gc))
+        return gs, gc
     sigmas = _f(sigmas)
     rgbs = _f(rgbs)
     deltas = _f(deltas)

@@ -373,6 +373,62 @@ void orc_composite_rays_train_backward(const float *grad_weights_sum, const floa
     }
 }
 
+/* The same two loops with every variable a double (inputs and outputs double): the sequential order and the early stop of
+ * raymarching.cu:501-577 / :602-682 without float32 rounding, for checks of float64 restatements of the operator. */
+void orc_composite_rays_train_forward_f64(const double *sigmas, const double *rgbs, const double *deltas, const int32_t *rays,
+                                          uint32_t M, uint32_t N, double T_thresh, double *weights_sum, double *depth, double *image) {
+    for (uint32_t n = 0; n < N; n++) {
+        uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
+        weights_sum[index] = 0; depth[index] = 0;
+        image[index * 3] = 0; image[index * 3 + 1] = 0; image[index * 3 + 2] = 0;
+        if (num_steps == 0 || offset + num_steps > M) continue;
+        const double *s = sigmas + offset, *c = rgbs + (size_t)offset * 3, *dl = deltas + (size_t)offset * 2;
+        uint32_t step = 0;
+        double T = 1.0, r = 0, g = 0, b = 0, ws = 0, t = 0, d = 0;
+        while (step < num_steps) {
+            const double alpha = 1.0 - exp(-s[0] * dl[0]);
+            const double weight = alpha * T;
+            r += weight * c[0]; g += weight * c[1]; b += weight * c[2];
+            t += dl[1];
+            d += weight * t;
+            ws += weight;
+            T *= 1.0 - alpha;
+            if (T < T_thresh) break;
+            s++; c += 3; dl += 2; step++;
+        }
+        weights_sum[index] = ws; depth[index] = d;
+        image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
+    }
+}
+
+void orc_composite_rays_train_backward_f64(const double *grad_weights_sum, const double *grad_image, const double *sigmas,
+                                           const double *rgbs, const double *deltas, const int32_t *rays,
+                                           const double *weights_sum, const double *image, uint32_t M, uint32_t N,
+                                           double T_thresh, double *grad_sigmas, double *grad_rgbs) {
+    for (uint32_t n = 0; n < N; n++) {
+        uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
+        if (num_steps == 0 || offset + num_steps > M) continue;
+        const double *gws = grad_weights_sum + index, *gi = grad_image + (size_t)index * 3;
+        const double *s = sigmas + offset, *c = rgbs + (size_t)offset * 3, *dl = deltas + (size_t)offset * 2;
+        double *gs = grad_sigmas + offset, *gc = grad_rgbs + (size_t)offset * 3;
+        uint32_t step = 0;
+        double T = 1.0, r = 0, g = 0, b = 0;
+        const double r_final = image[(size_t)index * 3], g_final = image[(size_t)index * 3 + 1], b_final = image[(size_t)index * 3 + 2];
+        const double ws_final = weights_sum[index];
+        while (step < num_steps) {
+            const double alpha = 1.0 - exp(-s[0] * dl[0]);
+            const double weight = alpha * T;
+            r += weight * c[0]; g += weight * c[1]; b += weight * c[2];
+            T *= 1.0 - alpha;
+            gc[0] = gi[0] * weight; gc[1] = gi[1] * weight; gc[2] = gi[2] * weight;
+            gs[0] = dl[0] * (gi[0] * (T * c[0] - (r_final - r)) + gi[1] * (T * c[1] - (g_final - g)) +
+                             gi[2] * (T * c[2] - (b_final - b)) + gws[0] * (1 - ws_final));
+            if (T < T_thresh) break;
+            s++; c += 3; dl += 2; gs++; gc += 3; step++;
+        }
+    }
+}
+
 /* march_rays (raymarching.cu:701-805) */
 void orc_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t,
                     const float *rays_o, const float *rays_d, float bound, float dt_gamma, uint32_t max_steps,

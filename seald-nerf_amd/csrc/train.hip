@@ -889,6 +889,10 @@ int fill_layout(uint32_t N, uint32_t M, uint32_t max_steps, const int32_t *grid_
     out->sample_set_stride = L.set_stride;
     out->sigmas = L.sigmas; out->weights_sum = L.weights_sum; out->depth = L.depth; out->image = L.image;
     out->found_inf = L.hyper + offsetof(Hyper, found_inf);
+    out->enc_in = L.enc_in; out->def_hidden = L.def_hidden; out->def_out = L.def_out; out->xdef = L.xdef; out->grid_out = L.grid_out;
+    out->enc_rm = L.enc_rm; out->h1 = L.h1; out->hout = L.hout; out->col_in = L.col_in; out->col_hidden = L.col_hidden; out->col_out = L.col_out;
+    out->sq_err = L.sq_err; out->dcol_out = L.dcol_out; out->dh0 = L.dh0; out->col_bwd = L.col_bwd; out->dcol_in = L.dcol_in;
+    out->dh = L.dh; out->dh1 = L.dh1; out->denc = L.denc; out->dx = L.dx; out->ddef = L.ddef; out->def_bwd = L.def_bwd;
     return 0;
 }
 

@@ -264,9 +264,11 @@ class NativeTrainStep:
 
     def view(self, name, dtype, shape):
         """A tensor view of a workspace buffer named in `SdnTrainLayout` (gradients `g_*`, fp16 parameter copies `w_*`, samples...).
-        The fp32 step keeps fp32 gradients at the same flat shapes and has no `w_*` copies."""
+        The fp32 step keeps fp32 gradients and intermediates at the same shapes, and has no `w_*` copies and no `enc_rm`."""
         if self.fp32 and name.startswith("w_"):
             raise ValueError(f"NativeTrainStep.view({name!r}): the fp32 step keeps no parameter copies")
+        if self.fp32 and name == "enc_rm":
+            raise ValueError("NativeTrainStep.view('enc_rm'): the fp32 step reads the grid features level-major (grid_out) and keeps no row-major copy")
         off = int(getattr(self.layout, name)) + (self._ws_ptr - self._ws.data_ptr())
         n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
         return self._ws[off:off + n].view(dtype).view(*shape)

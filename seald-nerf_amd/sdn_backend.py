@@ -167,7 +167,11 @@ class SdnTrainLayout(ctypes.Structure):
     """Mirror of `SdnTrainLayout` in include/sdn_hip.h."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("total_bytes", "w_table", "w_deform", "w_sigma0", "w_sigma1", "w_color", "g_table", "g_deform",
                                                 "g_sigma0", "g_sigma1", "g_color", "xyzs", "dirs", "deltas", "rays", "sample_set_stride", "sigmas",
-                                                "weights_sum", "depth", "image", "found_inf")]
+                                                "weights_sum", "depth", "image", "found_inf",
+                                                # the step's intermediates (appended; a buffer a step does not have is 0)
+                                                "enc_in", "def_hidden", "def_out", "xdef", "grid_out", "enc_rm", "h1", "hout", "col_in",
+                                                "col_hidden", "col_out", "sq_err", "dcol_out", "dh0", "col_bwd", "dcol_in", "dh", "dh1",
+                                                "denc", "dx", "ddef", "def_bwd")]
 
 
 PROTOTYPES.update({
