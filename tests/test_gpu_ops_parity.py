@@ -881,3 +881,63 @@ def test_large_batches_are_batch_independent():
     for i, r in enumerate(k.tolist()):
         assert torch.equal(xs[r * 8:r * 8 + 8], x2[i * 8:i * 8 + 8]) and torch.equal(dl[r * 8:r * 8 + 8], dl2[i * 8:i * 8 + 8])
     assert bool((dl2[:24, 0] > 0).all())
+
+
+RUN_BLOCKS = (1, 2, 3, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200, 313)
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
+def test_grid_encode_backward_run_merge_on_engineered_runs(half):
+    """k_grid_bwd's wave-level run merge (consecutive lanes that hit the same row are summed with a segmented shuffle scan, the run's
+    last lane issues one atomic) on runs built for its edges: blocks of identical points of 1 .. 313 lanes, so that runs start, end
+    and continue at lane 63 / 64 and at the 256-thread workgroup boundary, two blocks with one out-of-range point (an idle lane) in
+    their middle, then 100 distinct random points -- 1 291 points, neither a multiple of 64 nor of 256 (the blocks alone are 1 191).
+    Small tiled grid (D = 3, C = 2, 4 levels, H = 4, log2T = 8), called through the C ABI.  Reference: the float64 scatter of
+    tests/train_stage_support.py.  fp32: the fp32 bar per level; fp16: the half-atomic bar of test_grid_encode_backward.  The same
+    inputs through the fixed-point path (sdn_grid_encode_backward_det: exact sums up to 2^-40 / 2^-24 per term, one rounding): the
+    fp32 bar, 1.5 fp16 ulp + B * 2^-25 in fp16, and two runs bit-identical.
+    Measured: fp32 0.004 (float atomics) and 0.002 (fixed point) of the fp32 bar; fp16 0.043 of the half-atomic bar, 0.21 of the
+    fixed-point bar."""
+    import sdn_backend as sdn
+    import train_stage_support as S
+    offsets, pls = O.grid_offsets(3, 4, 2, 2, 4, 8, None, False)
+    Sg = float(np.float32(np.log2(pls)))
+    rng = np.random.default_rng(21)
+    x = np.repeat(rng.random((len(RUN_BLOCKS), 3), dtype=np.float32), RUN_BLOCKS, axis=0)
+    starts = np.concatenate([[0], np.cumsum(RUN_BLOCKS)[:-1]])
+    x[starts[-2] + 100, 0] = 1.25          # idle lanes inside the runs of 200 and of 313
+    x[starts[-1] + 150, 2] = -0.25
+    x = np.concatenate([x, rng.random((100, 3), dtype=np.float32)])
+    B, L, rows = x.shape[0], 4, int(offsets[-1])
+    assert B == 1291 and B % 64 and B % 256
+    g = rng.standard_normal((L, B, 2)).astype(np.float32)
+    if half:
+        g = (g * 1e-2).astype(np.float16)
+    c = S.tiled_corners(x, offsets, Sg, 4)
+    assert c.valid.sum() == B - 2
+    rs = S.run_structure(np.where(c.valid, c.rows[0, :, 0], -1))
+    assert rs["longest"] == 64 and rs["crossings"] >= 8 and rs["merging_waves"] >= 15, rs
+    ref = S.grid_table_gradient64(g, c)
+    dt = torch.float16 if half else torch.float32
+    xt, gt = _dev(x), _dev(g)
+    off_host = np.ascontiguousarray(offsets.astype(np.int32))
+
+    def run(det):
+        ge = torch.zeros(rows, 2, dtype=dt, device="cuda")
+        scratch = torch.empty(rows * 2, dtype=torch.int64, device="cuda") if det else None
+        sdn.check(sdn.lib.sdn_grid_encode_backward_det(sdn.ptr(gt), sdn.ptr(xt), off_host.ctypes.data, sdn.ptr(ge), B, 3, 2, L, Sg, 4, sdn.ptr(None),
+                                                        sdn.ptr(None), 1, 0, 0, sdn.dtype_id(dt), sdn.ptr(scratch), sdn.stream()), "grid_encode_backward")
+        torch.cuda.synchronize()
+        return ge.cpu().numpy()
+
+    plain, det0, det1 = run(False), run(True), run(True)
+    assert np.array_equal(det0.view(np.uint16 if half else np.uint32), det1.view(np.uint16 if half else np.uint32))
+    if half:
+        S.half_atomic_close(plain, ref, "engineered runs, half atomics", max(1.0, float(np.abs(ref).max())))
+        S.ulp16_close(det0, ref, "engineered runs, fixed point (fp16)", ulps=1.5, extra=B * 2.0 ** -25)
+    else:
+        S.table_gradient_close(plain, ref, offsets, "engineered runs, float atomics", fp32=True)
+        S.table_gradient_close(det0, ref, offsets, "engineered runs, fixed point (fp32)", fp32=True)
+    touched = np.zeros(rows, bool)
+    touched[c.rows[:, c.valid].reshape(-1)] = True
+    assert np.all(plain[~touched] == 0) and np.all(det0[~touched] == 0) and np.abs(ref).max() > 0

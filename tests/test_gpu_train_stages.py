@@ -112,13 +112,26 @@ def _step(fp32, short):
                   sq_err=(f, (n,)), dcol_out=(e, (M, 16)), dh0=(e, (M,)), col_bwd=(e, (2, M, 64)), dcol_in=(e, (M, 32)), dh=(e, (M, 16)),
                   dh1=(e, (M, 64)), denc=(e, (16, M, 2)), dx=(e, (M, 3)), ddef=(e, (M, 16)), def_bwd=(e, (7, M, 128)),
                   g_deform=(e, (S.DEF_FLAT,)), g_color=(e, (S.COL_FLAT,)), g_sigma0=(e, (64 * 32,)), g_sigma1=(e, (16 * 64,)))
+    rows = int(model.encoder.offsets[-1].item())
+    shapes.update(g_table=(e, (rows, 2)))
     if not fp32:
-        shapes.update(enc_rm=(e, (M, 32)), w_sigma0=(e, (64, 32)), w_sigma1=(e, (16, 64)))
+        shapes.update(enc_rm=(e, (M, 32)), w_sigma0=(e, (64, 32)), w_sigma1=(e, (16, 64)), w_table=(e, (rows, 2)), w_deform=(e, (S.DEF_FLAT,)),
+                      w_color=(e, (S.COL_FLAT,)))
     r = SimpleNamespace(**{k: _np(step.view(k, dt, shape)) for k, (dt, shape) in shapes.items()})
     if fp32:
         with pytest.raises(ValueError):
             step.view("enc_rm", e, (M, 32))
         r.w_sigma0, r.w_sigma1 = _np(model.sigma_net[0].weight), _np(model.sigma_net[1].weight)
+        # the fp32 step reads the model's parameters: the table in place, the MLPs padded into the flat geometry as k_f32_pack reads them
+        r.table = _np(model.encoder.embeddings)
+        r.def_mats = S.flat_from_parameters([_np(l.weight) for l in model.deform_net], S.DEF_IN, S.DEF_W, S.DEF_L)
+        r.col_mats = S.flat_from_parameters([_np(l.weight) for l in model.color_net], S.COL_IN, S.COL_W, S.COL_L, split=16)
+    else:
+        r.table = r.w_table
+        r.def_mats, r.col_mats = S.split_flat(r.w_deform, S.DEF_IN, S.DEF_W, S.DEF_L), S.split_flat(r.w_color, S.COL_IN, S.COL_W, S.COL_L)
+    enc = model.encoder
+    r.grid = SimpleNamespace(offsets=_np(enc.offsets).astype(np.int32), pls=enc.per_level_scale, H=int(enc.base_resolution),
+                             S=float(np.float32(np.log2(enc.per_level_scale))))
     r.fp32, r.short, r.M, r.N, r.owned = fp32, short, M, n, owned
     r.time, r.bound, r.density_scale = float(sc.time.item()), float(model.bound), float(model.density_scale)
     r.target, r.pred, r.loss = _np(target), _np(step.image), float(loss)
@@ -300,3 +313,141 @@ def test_weight_gradient_products(fp32):
         else:
             assert np.abs(want).max() < 6e4, (what, "leaves fp16: lower LOSS_SCALE", float(np.abs(want).max()))
             S.mfma16_close(got, want, what, 1)
+
+
+# ---- the packed MLP chains, layer by layer: every layer from the GPU's own stored input of THAT layer (depth 1 in the bar) --------------------------
+def _at(r, L):
+    """Where the gradient of hidden layer l's pre-activation is stored: [L - 1 - l] in the fp16 step, [l] in the fp32 step."""
+    return (lambda l: l) if r.fp32 else (lambda l: L - 1 - l)
+
+
+@STEPS
+def test_deformation_mlp_forward(fp32):
+    """sdn_ffh::forward_packed (fp16) / k_f32_chain_fwd (fp32) on 80 -> 128 x 7 -> 16: def_hidden[0] from enc_in, def_hidden[l] from
+    def_hidden[l - 1], def_out from def_hidden[6]; output columns 3..15 and (fp16) the padding of the weight copy are exactly zero.
+    Measured, fp16: no element of any layer beyond 4 ulp, norm-wise 2.07e-4 .. 2.08e-4 per hidden layer (tail tile up to 2.2e-4), def_out
+    3.8e-4 (tail tile 5.2e-4); fp32: at most 0.017 of the fp32 bar (def_hidden[2]), def_out 0.009."""
+    r = _run(fp32, False)
+    m = r.def_mats
+    if not fp32:
+        assert np.all(m[0][:, 76:] == 0) and np.all(m[7][3:] == 0) and np.any(m[0][:, :76] != 0) and np.any(m[7][:3] != 0)
+    x = r.enc_in
+    for l in range(S.DEF_L):
+        _close(r, r.def_hidden[l], S.mlp_layer_forward(x, m[l]), f"def_hidden[{l}]", 1)
+        x = r.def_hidden[l]
+    _close(r, r.def_out, S.mlp_layer_forward(x, m[S.DEF_L], relu=False), "def_out", 1)
+    assert np.all(r.def_out[:, 3:] == 0) and np.any(r.def_out[:, :3] != 0)
+
+
+@STEPS
+def test_colour_mlp_forward(fp32):
+    """forward_packed / k_f32_chain_fwd on 32 -> 64 x 2 -> 16: col_hidden[0] from col_in with the weight's input column 16 (the
+    log-density column) zero, col_hidden[1], col_out; output columns 3..15 exactly zero.
+    Measured, fp16: no element beyond 4 ulp, norm-wise 2.09e-4 / 2.07e-4 / 2.12e-4 (tail tile up to 2.7e-4); fp32: 0.012 / 0.015 / 0.007 of
+    the fp32 bar."""
+    r = _run(fp32, False)
+    m = r.col_mats
+    assert np.all(m[0][:, 16] == 0) and np.all(m[2][3:] == 0) and np.any(r.col_in[:, 16] != 0)
+    _close(r, r.col_hidden[0], S.mlp_layer_forward(r.col_in, m[0]), "col_hidden[0]", 1)
+    _close(r, r.col_hidden[1], S.mlp_layer_forward(r.col_hidden[0], m[1]), "col_hidden[1]", 1)
+    _close(r, r.col_out, S.mlp_layer_forward(r.col_hidden[1], m[2], relu=False), "col_out", 1)
+    assert np.all(r.col_out[:, 3:] == 0)
+
+
+@STEPS
+def test_colour_mlp_backward(fp32):
+    """backward_packed with the input gradient / k_f32_chain_bwd: the two pre-activation gradients of col_bwd from dcol_out, gated
+    by the GPU's own col_hidden, and dcol_in, whose column 16 is exactly zero (the weight column is structurally zero).
+    Measured, fp16: no element beyond 4 ulp, norm-wise 2.1e-4 / 2.2e-4 / 2.3e-4 (the last tile with a gradient holds fp16 subnormals only: no element
+    beyond the bar, norm-wise up to 8.8e-2 of a norm of ~1e-7, inside the bar's absolute 1e-6 term); fp32:
+    0.002 / 0.004 / 0.007 of the fp32 bar."""
+    r = _run(fp32, False)
+    m, at = r.col_mats, _at(r, S.COL_L)
+    _close(r, r.col_bwd[at(1)], S.mlp_layer_backward(r.dcol_out, m[2], r.col_hidden[1]), "col_bwd (layer 1)", 1, backward=True)
+    _close(r, r.col_bwd[at(0)], S.mlp_layer_backward(r.col_bwd[at(1)], m[1], r.col_hidden[0]), "col_bwd (layer 0)", 1, backward=True)
+    _close(r, r.dcol_in, S.mlp_layer_backward(r.col_bwd[at(0)], m[0]), "dcol_in", 1, backward=True)
+    assert np.all(r.dcol_in[:, 16] == 0) and np.any(r.dcol_in[:, 17:] != 0)
+
+
+@STEPS
+def test_deformation_mlp_backward(fp32):
+    """backward_packed WITHOUT the input gradient / k_f32_chain_bwd, seven layers deep: def_bwd layer 6 from ddef, layer l from the
+    GPU's def_bwd layer l + 1, each gated by def_hidden[l]; rows of samples without a gradient are exactly zero.
+    Measured, fp16: no element of any layer beyond 4 ulp, norm-wise 1.96e-4 (layer 6) .. 4.3e-4 (layer 0) (the
+    last tile with a gradient holds values at the fp16 subnormal spacing: norm-wise up to 0.86 of a norm below 1e-7, inside the bar's
+    absolute 1e-6 term); fp32: at most 0.008 of the
+    fp32 bar (layer 0)."""
+    r = _run(fp32, False)
+    m, at = r.def_mats, _at(r, S.DEF_L)
+    g = r.ddef
+    for l in range(S.DEF_L - 1, -1, -1):
+        _close(r, r.def_bwd[at(l)], S.mlp_layer_backward(g, m[l + 1], r.def_hidden[l]), f"def_bwd (layer {l})", 1, backward=True)
+        g = r.def_bwd[at(l)]
+    none = ~np.any(r.ddef != 0, axis=1)
+    assert none.sum() > 0 and (~none).sum() > 0 and np.all(r.def_bwd[:, none] == 0)
+
+
+# ---- the grid encoder inside the step ----------------------------------------------------------------------------------------------------------------
+def _corners(r):
+    if not hasattr(r, "corners"):
+        r.corners = S.tiled_corners(r.xdef, r.grid.offsets, r.grid.S, r.grid.H)
+    return r.corners
+
+
+@STEPS
+def test_grid_forward_in_step(fp32):
+    """sdn_grid_encode_forward as the step calls it: grid_out (level-major) is bit-identical to the oracle on the GPU's xdef and the
+    table the step read (the fp16 copy w_table / the fp32 parameter).
+    Measured: bit-identical in both steps; the fp32 step's grid_out 0.010 of the fp32 bar from the float64 restatement."""
+    from oracle import oracle as O
+    r = _run(fp32, False)
+    ref, _ = O.grid_encode_forward(r.xdef, r.table, r.grid.offsets, r.grid.pls, r.grid.H, False, 1, False, 0)
+    got = S.level_major_to_rows(r.grid_out)
+    bits = np.uint32 if fp32 else np.uint16
+    assert got.dtype == ref.dtype and np.array_equal(got.view(bits), ref.view(bits))
+    if fp32:      # and the float64 restatement the table-gradient tests rest on sees the same rows and weights
+        S.fp32_close(got, S.level_major_to_rows(S.grid_forward64(_corners(r), r.table)), "grid_out against the float64 restatement")
+    assert np.any(got != 0)
+
+
+@STEPS
+def test_grid_input_gradient_in_step(fp32):
+    """k_grid_input_bwd: dx against the float64 sum of denc x the restated dy_dx.  fp32: the fp32 bar.  fp16: the kernel rounds every
+    product and every partial sum to fp16 (Num<T>::rnd), 32 terms per element: 33 * 2^-11 * sum |g dy_dx| per element, plus 2^-24.
+    Measured: fp32 0.002 of the fp32 bar; fp16 0.92 of the derived bound (which also has to cover the fp16 rounding of the kernel's own
+    dy_dx, not restated here), and bit-equal to the oracle's serial fp16 grad_inputs."""
+    from oracle import oracle as O
+    r = _run(fp32, False)
+    c = _corners(r)
+    ref, mag = S.grid_input_gradient64(r.denc, S.grid_dy_dx64(c, r.table))
+    assert np.abs(ref).max() > 0
+    if fp32:
+        S.fp32_close(r.dx, ref, "dx")
+    else:
+        _, dd = O.grid_encode_forward(r.xdef, r.table, r.grid.offsets, r.grid.pls, r.grid.H, True, 1, False, 0)
+        _, gi = O.grid_encode_backward(S.level_major_to_rows(r.denc), r.xdef, r.table, r.grid.offsets, r.grid.pls, r.grid.H, dd, 1, False, 0)
+        print("[stage] fp16 dx bit-equal to the oracle's serial fp16 grad_inputs:", bool(np.array_equal(r.dx.astype(np.float32), gi)))
+        S.bound_close(r.dx, ref, 33 * 2.0 ** -11 * mag + S.F16_TINY, "dx", "33 * 2^-11 * sum |g dy_dx| + 2^-24")
+
+
+@STEPS
+def test_table_gradient_in_step(fp32):
+    """k_grid_bwd's wave-level run merge on ray-ordered samples: g_table per level against the float64 scatter of denc at the GPU's
+    own xdef.  fp32: the fp32 bar per level (the tight check of the merge: one template for both types, sums in fp32); fp16: the
+    half-atomic bar of test_grid_encode_backward per level.  Rows no sample touches are exactly zero.  The batch must exercise the
+    merge: on each of levels 0..3 a run of >= 8 lanes, >= 8 waves that merge, >= 1 row run continuing across a wave boundary.
+    Measured on the wedge batch (corner 0, owned samples): longest run 54 / 39 / 29 / 20 lanes on levels 0 / 1 / 2 / 3, merging in all
+    1080 waves, 1029 / 1030 / 994 / 960 row runs continuing across a wave boundary.  fp32: at most 0.001 of the fp32 bar on every
+    level; fp16: 0.013 .. 0.056 of the half-atomic bar (level 0 the largest)."""
+    r = _run(fp32, False)
+    c = _corners(r)
+    for l in range(4):
+        rs = S.run_structure(np.where(c.valid, c.rows[l, :, 0], -1)[:r.owned])        # (owned samples only: the zero-filled padding rows behind them are one long run)
+        print(f"[stage] level {l} corner 0: longest run {rs['longest']} lanes, {rs['merging_waves']} merging waves, {rs['crossings']} runs across a wave boundary")
+        assert rs["longest"] >= 8 and rs["merging_waves"] >= 8 and rs["crossings"] >= 1, (l, rs["longest"], rs["merging_waves"], rs["crossings"])
+    ref = S.grid_table_gradient64(r.denc, c)
+    assert np.abs(ref).max() > 0
+    touched = np.zeros(c.n_rows, bool)
+    touched[c.rows[:, c.valid].reshape(-1)] = True
+    assert (~touched).sum() > 0 and np.all(r.g_table[~touched] == 0)
+    S.table_gradient_close(r.g_table, ref, r.grid.offsets, "g_table", fp32)

@@ -2,6 +2,7 @@
 compositing loops (in double), its frequency and SH encoders, and float64 torch autograd.  The GPU tests
 (tests/test_gpu_train_stages.py) then hold each kernel of the native training steps to these functions."""
 import numpy as np
+import pytest
 import torch
 
 import train_stage_support as S
@@ -292,3 +293,226 @@ def test_synthetic_long_ray_batch_has_the_coverage_and_few_threshold_flips():
     fwd = S.composite_forward(sig, np.full((M, 2), dt), np.full((M, 3), 0.5), rays, T_THRESH)
     S.assert_coverage(*S.coverage(fwd, T_THRESH))
     assert S.flip_rays(fwd, T_THRESH).mean() <= 0.02
+
+
+# ---- the packed MLP chains, the grid encoder, the optimizer pass ---------------------------------------------------------------------------------------
+from oracle import ffmlp as FF  # noqa: E402
+
+
+def _chain_case(seed, in_dim, W, L, B=37):
+    rng = np.random.default_rng(seed)
+    n = W * in_dim + (L - 1) * W * W + 16 * W
+    flat = (rng.standard_normal(n) * (1.5 / np.sqrt(W))).astype(np.float16)
+    x = rng.standard_normal((B, in_dim)).astype(np.float16)
+    dy = (rng.standard_normal((B, 16)) * 0.1).astype(np.float16)
+    return flat, x, dy
+
+
+@pytest.mark.parametrize("in_dim,W,L", [(80, 128, 7), (32, 64, 2)], ids=["deformation", "colour"])
+def test_one_layer_restatements_compose_to_the_ffmlp_oracle(in_dim, W, L):
+    """mlp_layer_forward / mlp_layer_backward, composed with ONE fp16 rounding after each layer (of the float32
+    accumulator, as the oracle rounds), reproduce the oracle's forward
+    buffer, outputs, backward buffer (output side first) and input gradient bit for bit."""
+    flat, x, dy = _chain_case(7, in_dim, W, L)
+    mats = S.split_flat(flat, in_dim, W, L)
+    assert [m.shape for m in mats] == [m.shape for m in FF.split_weights(flat, in_dim, W, L)] and all(np.array_equal(a, b) for a, b in zip(mats, FF.split_weights(flat, in_dim, W, L)))
+    out_o, fwd_o = FF.ffmlp_forward(x, flat, in_dim, W, L, 0)
+    h, hidden = x, []
+    for l in range(L):
+        h = S.round16_acc32(S.mlp_layer_forward(h, mats[l]))
+        hidden.append(h)
+        assert np.array_equal(h, fwd_o[l].astype(np.float64)), l
+    assert np.array_equal(S.round16_acc32(S.mlp_layer_forward(h, mats[L], relu=False)), out_o.astype(np.float64))
+    gi_o, _, bwd_o = FF.ffmlp_backward(dy, x, flat, fwd_o, in_dim, W, L, 0)
+    g = dy
+    for k in range(L):                                   # k-th backward layer: matrix L - k, gate: hidden layer L - 1 - k
+        g = S.round16_acc32(S.mlp_layer_backward(g, mats[L - k], hidden[L - 1 - k]))
+        assert np.array_equal(g, bwd_o[k].astype(np.float64)), k
+        assert np.abs(g).max() > 0
+    assert np.array_equal(S.round16_acc32(S.mlp_layer_backward(g, mats[0])), gi_o.astype(np.float64))
+
+
+def test_flat_from_parameters_pads_and_splits_as_the_steps_pack():
+    rng = np.random.default_rng(8)
+    col = [rng.standard_normal((64, 31)), rng.standard_normal((64, 64)), rng.standard_normal((3, 64))]
+    m = S.flat_from_parameters(col, 32, 64, 2, split=16)
+    assert [a.shape for a in m] == [(64, 32), (64, 64), (16, 64)]
+    assert np.array_equal(m[0][:, :16], col[0][:, :16]) and np.all(m[0][:, 16] == 0) and np.array_equal(m[0][:, 17:], col[0][:, 16:])
+    assert np.array_equal(m[2][:3], col[2]) and np.all(m[2][3:] == 0)
+    d = S.flat_from_parameters([rng.standard_normal((128, 76))] + [rng.standard_normal((128, 128))] * 6 + [rng.standard_normal((3, 128))], 80, 128, 7)
+    assert d[0].shape == (128, 80) and np.all(d[0][:, 76:] == 0) and d[7].shape == (16, 128) and np.all(d[7][3:] == 0)
+
+
+def _dnerf_grid():
+    offsets, pls = oracle.grid_offsets(3, 16, 2, 2, 16, 19, 2048, False)
+    return offsets, pls, float(np.float32(np.log2(pls))), 16
+
+
+def _grid_points(rng, n):
+    x = rng.random((n, 3), dtype=np.float32)
+    x[0], x[1] = 0.0, 1.0
+    x[2, 0], x[3, 2] = -1e-3, 1.0 + 1e-3
+    x[4:40] = x[4] + rng.random((36, 3), dtype=np.float32) * 1e-3          # neighbours in one coarse cell
+    return x
+
+
+def test_level_scales_are_the_oracles():
+    import ctypes
+    offsets, pls, Sg, H = _dnerf_grid()
+    scale, res = S.level_scales(16, Sg, H)
+    for l in range(16):
+        s, r = ctypes.c_float(), ctypes.c_uint32()
+        oracle.lib().orc_grid_level_params(ctypes.c_uint32(l), ctypes.c_float(Sg), ctypes.c_uint32(H), ctypes.byref(s), ctypes.byref(r))
+        assert np.float32(s.value) == scale[l] and int(r.value) == int(res[l]), l
+
+
+def test_tiled_grid_restatements_match_the_oracle_on_500_points():
+    """Indices exactly (a one-hot gradient through the oracle's backward names the rows it touches), values at the fp32 bar."""
+    rng = np.random.default_rng(9)
+    offsets, pls, Sg, H = _dnerf_grid()
+    x = _grid_points(rng, 500)
+    table = rng.uniform(-1, 1, (int(offsets[-1]), 2)).astype(np.float32)
+    c = S.tiled_corners(x, offsets, Sg, H)
+    assert not c.valid[2] and not c.valid[3] and c.valid[0] and c.valid[1] and c.valid.sum() == 498
+    assert np.allclose(c.weights.sum(2)[:, c.valid], 1.0, atol=1e-12) and np.all(c.weights[:, ~c.valid] == 0)
+    out_o, dd_o = oracle.grid_encode_forward(x, table, offsets, pls, H, True, 1, False, 0)
+    S.fp32_close(S.level_major_to_rows(S.grid_forward64(c, table)), out_o, "grid forward")
+    dd = S.grid_dy_dx64(c, table)
+    S.fp32_close(dd.reshape(500, -1), dd_o, "dy_dx")
+    g = rng.standard_normal((500, 32)).astype(np.float32)
+    ge_o, gi_o = oracle.grid_encode_backward(g, x, table, offsets, pls, H, dd_o, 1, False, 0)
+    denc = S.rows_to_level_major(g)
+    ge = S.grid_table_gradient64(denc, c)
+    S.table_gradient_close(ge_o, ge, offsets, "table gradient", fp32=True)
+    gi, mag = S.grid_input_gradient64(denc, dd)
+    S.fp32_close(gi, gi_o, "input gradient")
+    assert np.all(mag >= np.abs(gi) - 1e-12)
+    # indices: the rows the oracle's backward touches for a gradient of ones are exactly the restated rows, level by level
+    ones = np.ones((500, 32), np.float32)
+    touched_o, _ = oracle.grid_encode_backward(ones, x, table, offsets, pls, H, None, 1, False, 0)
+    touched = np.zeros(int(offsets[-1]), bool)
+    touched[c.rows[:, c.valid].reshape(-1)] = True
+    nz = touched_o[:, 0] != 0
+    assert np.array_equal(nz | ~touched, np.ones_like(nz)) and not (nz & ~touched).any()
+    # (a corner of weight exactly 0 is restated but adds 0.0 in the oracle: every other restated row must be touched)
+    w_row = np.zeros(int(offsets[-1]))
+    np.add.at(w_row, c.rows[:, c.valid].reshape(-1), c.weights[:, c.valid].reshape(-1))
+    assert np.array_equal(nz, w_row > 0)
+    S.fp32_close(touched_o[:, 0], w_row, "row weights")
+
+
+def test_run_structure_counts_runs_inside_waves_and_across_them():
+    rows = np.array([5] * 3 + [7] * 61 + [7] * 2 + [-1] + [7] * 4 + [9] * 57 + [9] * 64 + [2] * 10)
+    rs = S.run_structure(rows)
+    assert rs["lengths"][:2].tolist() == [3, 61] and rs["lengths"][2:6].tolist() == [2, 1, 4, 57]
+    assert rs["longest"] == 64 and rs["crossings"] == 2 and rs["merging_waves"] == 4
+    assert int(rs["lengths"].sum()) == 256           # padded to whole waves with idle lanes
+    assert S.run_structure(np.arange(100))["merging_waves"] == 0 and S.run_structure(-np.ones(70))["longest"] == 1
+
+
+def _merge_case():
+    """A ray-like batch on the small directed grid: blocks of identical points and a slow drift, so that runs start, end and continue
+    at wave boundaries."""
+    rng = np.random.default_rng(11)
+    offsets, pls = oracle.grid_offsets(3, 4, 2, 2, 4, 8, None, False)
+    Sg = float(np.float32(np.log2(pls)))
+    x = np.repeat(rng.random((12, 3), dtype=np.float32), [1, 2, 3, 31, 32, 33, 63, 64, 65, 127, 128, 129], axis=0)
+    x[300, 1] = 1.5
+    denc = rng.standard_normal((4, x.shape[0], 2))
+    return offsets, S.tiled_corners(x, offsets, Sg, 4), denc
+
+
+@pytest.mark.parametrize("variant", ["last_lane", "cut_at_63"])
+def test_table_gradient_bars_reject_a_wrong_run_merge(variant):
+    """A run's last lane dropped from its sum / a run ending on lane 63 never issued: both bars (fp32, and the half-atomic bar the
+    fp16 step gets) fail on the mutated restatement."""
+    offsets, c, denc = _merge_case()
+    ref = S.grid_table_gradient64(denc, c)
+    drop = S.merge_mutation(c, variant)
+    assert drop.any() and not drop[:, ~c.valid].any()
+    wrong = S.grid_table_gradient64(denc, c, drop=drop)
+    S.table_gradient_close(ref.astype(np.float32), ref, offsets, "table gradient", fp32=True)
+    for fp32 in (True, False):
+        with pytest.raises(AssertionError):
+            S.table_gradient_close(wrong, ref, offsets, f"table gradient ({variant})", fp32=fp32)
+
+
+def test_mlp_bars_reject_an_unzeroed_column_16_and_a_gate_from_the_wrong_layer():
+    flat, x, dy = _chain_case(12, 32, 64, 2, B=64)
+    mats = [m.astype(np.float64) for m in S.split_flat(flat, 32, 64, 2)]
+    zeroed = mats[0].copy()
+    zeroed[:, 16] = 0
+    x = x.astype(np.float64)
+    x[:, 16] = 3.0                                       # the log-density column carries a value
+    ref = S.mlp_layer_forward(x, zeroed)
+    wrong = S.mlp_layer_forward(x, mats[0])
+    S.mfma16_close(S.round16(ref), ref, "col_hidden[0]", 1)
+    S.fp32_close(ref.astype(np.float32), ref, "col_hidden[0]")
+    for close in (lambda a, b: S.mfma16_close(S.round16(a), b, "col_hidden[0], column 16 kept", 1), lambda a, b: S.fp32_close(a, b, "col_hidden[0], column 16 kept")):
+        with pytest.raises(AssertionError):
+            close(wrong, ref)
+    h0 = S.round16(ref)
+    h1 = S.round16(S.mlp_layer_forward(h0, mats[1]))
+    g_ref = S.mlp_layer_backward(dy, mats[2], h1)
+    g_wrong = S.mlp_layer_backward(dy, mats[2], h0)
+    assert (h0 > 0).mean() > 0.2 and ((h0 > 0) != (h1 > 0)).mean() > 0.1
+    for close in (lambda a, b: S.mfma16_close(S.round16(a), b, "col_bwd, gate of the wrong layer", 1), lambda a, b: S.fp32_close(a, b, "col_bwd, gate of the wrong layer")):
+        with pytest.raises(AssertionError):
+            close(g_wrong, g_ref)
+    # and the input gradient's column 16: exactly zero only with the zeroed weight column
+    assert np.all(S.mlp_layer_backward(g_ref, zeroed)[:, 16] == 0) and np.any(S.mlp_layer_backward(g_ref, mats[0])[:, 16] != 0)
+
+
+def test_adam_pass64_is_torch_adam_over_three_steps():
+    rng = np.random.default_rng(13)
+    p0 = rng.standard_normal(300)
+    p_t = torch.tensor(p0.copy(), requires_grad=True)
+    opt = torch.optim.Adam([p_t], lr=1e-2, betas=(0.9, 0.99), eps=1e-15, foreach=False)
+    p, m, v = p0.copy(), np.zeros(300), np.zeros(300)
+    for step in (1, 2, 3):
+        g16 = (rng.standard_normal(300) * 1024).astype(np.float16)
+        g16[::10] = 0
+        p_t.grad = torch.tensor(g16.astype(np.float64) / 1024.0)
+        opt.step()
+        p, m, v = S.adam_pass64(p, m, v, g16, 1.0 / 1024.0, step, 1e-2, 0.9, 0.99, 1e-15)
+        st = opt.state[p_t]
+        assert _rel(p, p_t.detach().numpy()) <= 1e-13 and _rel(m, st["exp_avg"].numpy()) <= 1e-13 and _rel(v, st["exp_avg_sq"].numpy()) <= 1e-13
+
+
+def test_adam_bars_reject_the_other_groups_step_count_and_a_missing_divisor():
+    rng = np.random.default_rng(14)
+    p0, m0, v0 = rng.standard_normal(500) * 0.1, rng.standard_normal(500) * 1e-3, rng.random(500) * 1e-6
+    g16 = (rng.standard_normal(500) * 1024 * 1e-3).astype(np.float16)
+    args = (1e-3, 0.9, 0.99, 1e-15)
+    p, m, v = S.adam_pass64(p0, m0, v0, g16, 1.0 / 2048.0, 3, *args)
+    for what, (pw, mw, vw) in (("step 2 for step 3", S.adam_pass64(p0, m0, v0, g16, 1.0 / 2048.0, 2, *args)),
+                               ("no divisor", S.adam_pass64(p0, m0, v0, g16, 1.0 / 1024.0, 3, *args))):
+        S.fp32_close((p - p0).astype(np.float32), p - p0, "update")
+        with pytest.raises(AssertionError):
+            S.fp32_close(pw - p0, p - p0, f"update ({what})", extra=2.0 ** -24 * np.abs(p0))
+        if what == "no divisor":
+            for got, ref in ((mw, m), (vw, v)):
+                with pytest.raises(AssertionError):
+                    S.fp32_close(got, ref, f"moment ({what})")
+
+
+def test_nonfinite16_and_the_scaler_rule():
+    g = np.zeros(64, np.float16)
+    assert not S.nonfinite16(g)
+    g[:] = 65504
+    g[1::2] = -65504
+    g[5] = np.float16(6e-8)
+    assert not S.nonfinite16(g)
+    for bad in (np.inf, -np.inf, np.nan):
+        h = g.copy()
+        h[63] = bad
+        assert S.nonfinite16(h)
+    # torch's own rule on the CPU, the sequence of the optimizer test: three clean steps grow, a found inf backs off
+    scale, tracker = torch.tensor([1024.0]), torch.tensor([0], dtype=torch.int32)
+    seen = []
+    for found in (0.0, 0.0, 0.0, 1.0):
+        torch._amp_update_scale_(scale, tracker, torch.tensor([found]), 2.0, 0.5, 3)
+        seen.append((float(scale), int(tracker)))
+    assert seen == [(1024.0, 1), (1024.0, 2), (2048.0, 0), (1024.0, 0)]
+    assert S.ema_decay_of(0.95, 1) == 2.0 / 11.0 and S.ema_decay_of(0.95, 1000) == 0.95
+    assert np.allclose(S.ema_pass64(np.ones(3), np.zeros(3), 0.75), 0.75)

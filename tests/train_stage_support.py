@@ -32,6 +32,12 @@ def round16(a):
     return np.asarray(a, np.float64).astype(np.float16).astype(np.float64)
 
 
+def round16_acc32(a):
+    """float64 -> float32 -> fp16: the rounding of a layer whose sums sit in a float32 accumulator before the store (what the
+    matrix cores and oracle/ffmlp.py's `_linear` do; differs from `round16` only where the float32 rounding lands on an fp16 tie)."""
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float16).astype(np.float64)
+
+
 # ---- encode and deformed position -----------------------------------------------------------------------------------------------------
 def encode(xyzs, time):
     """freq(x, 10) ++ freq(t, 6), padded to 80 columns (dnerf/network.py:123-138; freqencoder.cu:30-58: x, then per frequency
@@ -293,6 +299,254 @@ def weight_gradients(bufs, fp32):
         assert A.shape[1] == rows and B.shape[1] == cols, (g, off, A.shape, B.shape)
         out[g][off:off + rows * cols] = (A.T @ B).reshape(-1)
     return out, jobs
+
+
+# ---- the packed MLP chains, one layer at a time ---------------------------------------------------------------------------------------------------
+def split_flat(flat, in_ld, W, L):
+    """The flat weight layout [W, in_ld] ++ (L - 1) x [W, W] ++ [16, W] (ffmlp.cu:631) -> the L + 1 matrices [out, in], in layer order."""
+    w = np.asarray(flat).reshape(-1)
+    mats, off = [], 0
+    for r, c in [(W, in_ld)] + [(W, W)] * (L - 1) + [(16, W)]:
+        mats.append(w[off:off + r * c].reshape(r, c))
+        off += r * c
+    assert off == w.size, (off, w.size)
+    return mats
+
+
+def flat_from_parameters(params, in_ld, W, L, split=None):
+    """The same L + 1 matrices from the model's parameters ([W, in], ..., [3, W]), padded with zeros as the steps pack them: the input
+    layer to in_ld columns, the output layer to 16 rows; split: the flat input column that is structurally zero (the colour MLP's
+    log-density column 16: the columns behind it sit one further right)."""
+    mats = []
+    for i, p in enumerate(params):
+        p = f64(p)
+        rows, cols = (W if i < L else 16), (in_ld if i == 0 else W)
+        m = np.zeros((rows, cols))
+        if i == 0 and split is not None:
+            m[:p.shape[0], :split] = p[:, :split]
+            m[:p.shape[0], split + 1:split + 1 + p.shape[1] - split] = p[:, split:]
+        else:
+            m[:p.shape[0], :p.shape[1]] = p
+        mats.append(m)
+    assert len(mats) == L + 1
+    return mats
+
+
+def mlp_layer_forward(x, W, relu=True):
+    """ONE layer: x W^T, through the ReLU for a hidden layer.  Exact products, float64 sums, no rounding."""
+    y = f64(x) @ f64(W).T
+    return np.maximum(y, 0.0) if relu else y
+
+
+def mlp_layer_backward(dy, W, act_out=None):
+    """ONE layer backwards: dy W (W the [out, in] matrix dy came out of), gated by `act_out > 0` -- the stored post-activation of
+    the layer the gradient arrives at (ReLU's derivative from its output, utils.h:538-541); None: the network's input, no gate."""
+    g = f64(dy) @ f64(W)
+    return g if act_out is None else g * (f64(act_out) > 0)
+
+
+# ---- the tiled grid of the dnerf network: D = 3, C = 2, tiled, no align_corners, linear interpolation ------------------------------------------------
+def level_scales(n_levels, S, H):
+    """gridencoder.cu:138-139 as the host code evaluates it in float32: scale = exp2f(level * S) * H - 1, resolution = ceil(scale) + 1.
+    (exp2 is taken in double and rounded once: the correctly rounded float32 result; tests/test_train_stages_cpu.py checks it against
+    the oracle's own exp2f level by level.)"""
+    p = (np.arange(n_levels, dtype=np.float32) * np.float32(S)).astype(np.float32)
+    e = np.exp2(p.astype(np.float64)).astype(np.float32)
+    scale = (e * np.float32(H)).astype(np.float32) - np.float32(1)
+    return scale.astype(np.float32), np.ceil(scale.astype(np.float64)).astype(np.int64) + 1
+
+
+class Corners:
+    """What `tiled_corners` returns: rows [L, B, 8] (table row, level offset included; 0 where the point is out of range), weights
+    [L, B, 8] float64 (0 there), frac [L, B, 3] the float32 in-cell position as float64, scale [L] float64, valid [B]."""
+
+    def __init__(self, rows, weights, frac, scale, valid, n_rows):
+        self.rows, self.weights, self.frac, self.scale, self.valid, self.n_rows = rows, weights, frac, scale, valid, n_rows
+
+
+def tiled_corners(x, offsets, S, H):
+    """Per level the 8 corner rows and trilinear weights of every point (gridencoder.cu:143-189, :66-84 with gridtype tiled): pos =
+    x * scale + 0.5f and its floor are taken in FLOAT32, operation by operation, exactly as k_grid_bwd and the oracle take them (the
+    cell a point falls in must not depend on who computes it); the in-cell position pos - floor is exact in float32, and the weights
+    are its products in float64.  Corner idx has bit d set <=> +1 along d.  The row index is the tiled one: sum of pos_grid[d] *
+    stride over the dimensions whose stride still fits the level, modulo the level's row count (uint32 arithmetic)."""
+    x = np.asarray(x, np.float32).reshape(-1, 3)
+    off = np.asarray(offsets).astype(np.int64)
+    L, B = off.size - 1, x.shape[0]
+    scale, res = level_scales(L, S, H)
+    valid = ~((x < 0) | (x > 1)).any(1)
+    rows, weights, frac = np.zeros((L, B, 8), np.int64), np.zeros((L, B, 8)), np.zeros((L, B, 3))
+    for l in range(L):
+        pos = ((x * scale[l]).astype(np.float32) + np.float32(0.5)).astype(np.float32)
+        fl = np.floor(pos).astype(np.float32)
+        pg = np.where(valid[:, None], fl, 0).astype(np.int64)
+        fr = (pos - fl).astype(np.float32).astype(np.float64)
+        frac[l] = fr
+        size = int(off[l + 1] - off[l])
+        for idx in range(8):
+            w, index, stride = np.ones(B), np.zeros(B, np.int64), 1
+            for d in range(3):
+                up = (idx >> d) & 1
+                w = w * (fr[:, d] if up else 1.0 - fr[:, d])
+                if stride <= size:
+                    index = (index + (pg[:, d] + up) * stride) & 0xFFFFFFFF
+                    stride = (stride * (int(res[l]) + 1)) & 0xFFFFFFFF
+            rows[l, :, idx] = np.where(valid, off[l] + index % size, 0)
+            weights[l, :, idx] = np.where(valid, w, 0.0)
+    return Corners(rows, weights, frac, scale.astype(np.float64), valid, int(off[-1]))
+
+
+def grid_forward64(corners, table):
+    """[L, B, 2]: sum over the corners of weight x table row (gridencoder.cu:187-189), float64."""
+    return (corners.weights[..., None] * f64(table)[corners.rows]).sum(2)
+
+
+def grid_table_gradient64(denc, corners, drop=None):
+    """[rows, 2]: every sample adds weight x its level's gradient to each of its 8 rows (gridencoder.cu:248-340), float64.
+    denc: [L, B, 2].  drop: bool [L, B, 8], contributions to leave out (the wrong variants of the run merge)."""
+    out = np.zeros((corners.n_rows, 2))
+    contrib = corners.weights[..., None] * f64(denc)[:, :, None, :]
+    keep = np.broadcast_to(corners.valid[None, :, None], corners.rows.shape)
+    if drop is not None:
+        keep = keep & ~drop
+    np.add.at(out, corners.rows[keep], contrib[keep])
+    return out
+
+
+def grid_dy_dx64(corners, table):
+    """[B, L, 3, 2]: d(feature) / d(x[gd]) = scale * sum over the 4 corners of the other two dimensions of their weights times
+    (table row one step along gd - table row) (gridencoder.cu:193-236), float64; zero for a point out of range."""
+    T = f64(table)[corners.rows]                                   # [L, B, 8, 2]
+    L, B = corners.rows.shape[:2]
+    out = np.zeros((B, L, 3, 2))
+    fr = corners.frac
+    for gd in range(3):
+        others = [d for d in range(3) if d != gd]
+        for idx in range(8):
+            if (idx >> gd) & 1:
+                continue
+            w = corners.scale[:, None] * np.ones((L, B))
+            for d in others:
+                w = w * (fr[:, :, d] if (idx >> d) & 1 else 1.0 - fr[:, :, d])
+            out[:, :, gd, :] += (w[..., None] * (T[:, :, idx | (1 << gd)] - T[:, :, idx])).transpose(1, 0, 2)
+    return out * corners.valid[:, None, None, None]
+
+
+def grid_input_gradient64(denc, dy_dx):
+    """[B, 3] = sum over levels and channels of denc[l, b, c] * dy_dx[b, l, d, c] (gridencoder.cu:343-369), and the sum of the
+    terms' magnitudes (what a rounded evaluation's error scales with).  denc: [L, B, 2]."""
+    terms = f64(denc).transpose(1, 0, 2)[:, :, None, :] * f64(dy_dx)
+    return terms.sum((1, 3)), np.abs(terms).sum((1, 3))
+
+
+def run_structure(rows, wave=64):
+    """The runs k_grid_bwd's wave-level merge sees on ONE corner of ONE level: rows[b] is sample b's row (negative: an idle lane --
+    a point out of range; idle lanes never merge), lane = b % wave.  A run is a maximal stretch of equal rows inside one wave.
+    -> dict: lengths (every run's length, in order), wave_of_run, longest, merging_waves (waves with a run longer than one lane),
+    crossings (wave boundaries at which the same row continues: a row run the merge must cut there and finish with two atomics)."""
+    r = np.asarray(rows).astype(np.int64).reshape(-1)
+    n = r.size
+    key = np.where(r < 0, -1 - np.arange(n), r)
+    pad = (-n) % wave
+    key = np.concatenate([key, -1 - n - np.arange(pad)])
+    k = key.reshape(-1, wave)
+    head = np.ones(k.shape, bool)
+    head[:, 1:] = k[:, 1:] != k[:, :-1]
+    starts = np.flatnonzero(head.ravel())
+    lengths = np.diff(np.append(starts, key.size))
+    wave_of_run = starts // wave
+    crossings = int((k[1:, 0] == k[:-1, -1]).sum())
+    return dict(lengths=lengths, wave_of_run=wave_of_run, longest=int(lengths.max()) if lengths.size else 0,
+                merging_waves=int(np.unique(wave_of_run[lengths > 1]).size), crossings=crossings)
+
+
+def merge_mutation(corners, variant, wave=64):
+    """bool [L, B, 8]: the contributions a WRONG run merge loses.  'last_lane': the last lane of every run longer than one lane is left
+    out of its run's sum (a scan that stops one offset early); 'cut_at_63': a run that ends on the wave's last lane is never issued (a
+    tail test that looks only at the next lane's head bit)."""
+    L, B, _ = corners.rows.shape
+    drop = np.zeros(corners.rows.shape, bool)
+    for l in range(L):
+        for idx in range(8):
+            rows = np.where(corners.valid, corners.rows[l, :, idx], -1)
+            rs = run_structure(rows, wave)
+            starts = np.concatenate([[0], np.cumsum(rs["lengths"])[:-1]])
+            ends = starts + rs["lengths"] - 1
+            if variant == "last_lane":
+                lost = ends[rs["lengths"] > 1]
+            elif variant == "cut_at_63":
+                sel = ends % wave == wave - 1
+                lost = np.concatenate([np.arange(s, e + 1) for s, e in zip(starts[sel], ends[sel])]) if sel.any() else np.zeros(0, np.int64)
+            else:
+                raise ValueError(variant)
+            lost = lost[lost < B].astype(np.int64)
+            drop[l, lost, idx] = corners.valid[lost]
+    return drop
+
+
+def table_gradient_close(got, ref, offsets, what, fp32):
+    """The table gradient's bar, level by level.  fp32: the project's fp32 bar.  fp16 (packed-half atomics, every atomic rounds the
+    running sum): the bar of tests/test_gpu_ops_parity.py::test_grid_encode_backward, rtol 2e-2 with atol 2e-3 x the level's largest
+    reference magnitude.  -> the worst error over the levels, in units of the bar."""
+    off = np.asarray(offsets).astype(np.int64)
+    worst = 0.0
+    for l in range(off.size - 1):
+        g, r = f64(got)[off[l]:off[l + 1]], f64(ref)[off[l]:off[l + 1]]
+        if fp32:
+            worst = max(worst, fp32_close(g, r, f"{what} level {l}"))
+        else:
+            worst = max(worst, half_atomic_close(g, r, f"{what} level {l}", float(np.abs(r).max())))
+    return worst
+
+
+def half_atomic_close(got, ref, what, atol_scale):
+    """rtol 2e-2 with atol 2e-3 x atol_scale: sums taken with packed-half atomics in the hardware's order."""
+    got, ref = f64(got), f64(ref)
+    tol = 2e-2 * np.abs(ref) + 2e-3 * float(atol_scale)
+    r = np.abs(got - ref) / np.maximum(tol, 1e-300)
+    worst = float(r.max()) if r.size else 0.0
+    print(f"[stage] {what}: worst error {worst:.3f} of the half-atomic bar (max |ref| {float(np.abs(ref).max()) if ref.size else 0:.3e})")
+    assert worst <= 1.0, f"{what}: {worst:.3f} x the half-atomic bar at {np.unravel_index(int(r.argmax()), r.shape)}"
+    return worst
+
+
+def bound_close(got, ref, tol, what, name):
+    """|got - ref| <= tol element by element, tol a derived per-element bound.  -> the worst error in units of the bound."""
+    got, ref, tol = f64(got), f64(ref), f64(tol)
+    r = np.abs(got - ref) / np.maximum(tol, 1e-300)
+    worst = float(r.max()) if r.size else 0.0
+    print(f"[stage] {what}: worst error {worst:.3f} of {name} (max |ref| {float(np.abs(ref).max()) if ref.size else 0:.3e})")
+    assert worst <= 1.0, f"{what}: {worst:.3f} x {name} at {np.unravel_index(int(r.argmax()), r.shape)}"
+    return worst
+
+
+# ---- the fp16 step's optimizer pass -------------------------------------------------------------------------------------------------------------------
+def nonfinite16(g):
+    """Is any fp16 element an inf or a NaN (all five exponent bits set)?"""
+    bits = np.ascontiguousarray(np.asarray(g, np.float16)).view(np.uint16)
+    return bool(((bits & 0x7C00) == 0x7C00).any())
+
+
+def adam_pass64(p, m, v, g16, inv_scale, step, lr, b1, b2, eps):
+    """torch.optim.Adam's single-tensor update (adam.py _single_tensor_adam; no weight decay, amsgrad or maximize) in float64 on the
+    gradient GradScaler.unscale_ hands it, float(g16) * inv_scale: m.lerp_(g, 1 - b1); v.mul_(b2).addcmul_(g, g, 1 - b2);
+    denom = sqrt(v) / sqrt(1 - b2^step) + eps; p.addcdiv_(m, denom, -lr / (1 - b1^step)).  -> (p, m, v)."""
+    p, m, v = f64(p), f64(m), f64(v)
+    g = f64(g16) * float(inv_scale)
+    m = m + (1.0 - b1) * (g - m)
+    v = v * b2 + (1.0 - b2) * g * g
+    denom = np.sqrt(v) / np.sqrt(1.0 - b2 ** step) + eps
+    return p - (lr / (1.0 - b1 ** step)) * (m / denom), m, v
+
+
+def ema_decay_of(decay, n_updates):
+    """torch_ema's effective decay at its n-th update (num_updates is incremented before use): min(decay, (1 + n) / (10 + n))."""
+    return min(float(decay), (1.0 + n_updates) / (10.0 + n_updates))
+
+
+def ema_pass64(shadow, p, decay):
+    """torch_ema: shadow -= (1 - decay) * (shadow - p)."""
+    return f64(shadow) - (1.0 - decay) * (f64(shadow) - f64(p))
 
 
 # ---- bars -------------------------------------------------------------------------------------------------------------------------------------
