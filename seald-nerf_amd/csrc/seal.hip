@@ -11,7 +11,9 @@
 //   only in calls that map at least one sample: the early return of :251-252 comes first)
 //   SealAnchorMapper.map_to_origin :522-578 with project_points :736-744 (the cone / plane-side deformation, see k_seal_anchor_apply)
 //   SealBrushMapper.map_to_origin :415-461 (the surface pushed along the stroke's normal, attenuated towards the stroke's border, see k_seal_brush_map)
-//   the `image` branch of map_color :58-79 (the brush's `imageConfig` texture stamp: a texel per sample is modify_rgb's target, alpha-blended, see seal_image_stamp)
+//   the `image` branch of map_color :58-79 (the brush's `imageConfig` texture stamp: a texel per sample is modify_rgb's target, alpha-blended, see SealStamp)
+// The mappers and colour edits share their steps: seal_in_aabb / seal_in_bounds, project_point, rgb_to_hsv / hsv_to_rgb, seal_mean_v, the
+// second colour pass k_seal_apply<per iteration?, SealTint | SealStamp>; on the host fill_bounds, launch_lanes, seal_recolour[_whole_rays].
 // The reference evaluates this with boolean-mask gathers / scatters and O(points x triangles) temporaries in torch, inside the
 // render loop; here it is one lane per sample slot, in place, between the marcher and the field kernel.  Dot products are
 // accumulated x, y, z in fp32 (torch's einsum order is library-defined): masks agree with the torch restatement except for
@@ -39,6 +41,13 @@ struct SealBoxArgs {
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return ax * bx + ay * by + az * bz; }
 
+// project_points(n, o, p), seal_utils.py:736-744: q = p - ((p - o) . n / n . n) n; n_sq: n . n, as the caller holds it
+__device__ __forceinline__ void project_point(float nx, float ny, float nz, float n_sq, float ox, float oy, float oz, float px, float py, float pz,
+                                              float &qx, float &qy, float &qz) {
+    const float along = dot3(px - ox, py - oy, pz - oz, nx, ny, nz) / n_sq;
+    qx = px - along * nx; qy = py - along * ny; qz = pz - along * nz;
+}
+
 __device__ __forceinline__ bool any_hit(const float *__restrict__ tris, uint32_t F, float ox, float oy, float oz, float dx, float dy, float dz) {
     bool hit = false;
     for (uint32_t f = 0; f < F; f++) {
@@ -54,14 +63,25 @@ __device__ __forceinline__ bool any_hit(const float *__restrict__ tris, uint32_t
     return hit;
 }
 
-// map_mask (seal_utils.py:132-153) of one point: non-zero in every coordinate (`points.all(1)`: empty slots and exact zeros are never
-// inside), strictly inside one of the AABBs, and inside the mesh
-__device__ __forceinline__ bool seal_in_box(const SealBoxTest &B, float x, float y, float z) {
+// strictly inside the box lo .. hi
+__device__ __forceinline__ bool seal_in_aabb(const float *lo, const float *hi, float x, float y, float z) {
+    return (hi[0] > x) & (x > lo[0]) & (hi[1] > y) & (y > lo[1]) & (hi[2] > z) & (z > lo[2]);
+}
+
+// The bound test of map_mask (seal_utils.py:132-153) of one point: non-zero in every coordinate (`points.all(1)`: empty slots and exact
+// zeros are never inside) and strictly inside one of the AABBs.  B: SealBoxTest or SealBrushArgs
+template <class Bounds>
+__device__ __forceinline__ bool seal_in_bounds(const Bounds &B, float x, float y, float z) {
     bool in = false;
     if (x != 0.0f && y != 0.0f && z != 0.0f) {
-        for (uint32_t b = 0; b < B.n_bounds; b++)
-            in |= (B.bounds[b][3] > x) & (x > B.bounds[b][0]) & (B.bounds[b][4] > y) & (y > B.bounds[b][1]) & (B.bounds[b][5] > z) & (z > B.bounds[b][2]);
+        for (uint32_t b = 0; b < B.n_bounds; b++) in |= seal_in_aabb(B.bounds[b], B.bounds[b] + 3, x, y, z);
     }
+    return in;
+}
+
+// map_mask of one point: the bound test, then inside the mesh
+__device__ __forceinline__ bool seal_in_box(const SealBoxTest &B, float x, float y, float z) {
+    bool in = seal_in_bounds(B, x, y, z);
     if (in)
         in = any_hit(B.tris, B.n_tris, x, y, z, B.test_dir[0], B.test_dir[1], B.test_dir[2]) &&
              any_hit(B.tris, B.n_tris, x, y, z, -B.test_dir[0], -B.test_dir[1], -B.test_dir[2]);
@@ -122,7 +142,7 @@ __global__ void __launch_bounds__(256) k_seal_source_redirect(float *__restrict_
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M || *S.flag != S.tag || mask[i]) return;
     const float x = xyzs[(size_t)i * 3], y = xyzs[(size_t)i * 3 + 1], z = xyzs[(size_t)i * 3 + 2];
-    if ((S.hi[0] > x) & (x > S.lo[0]) & (S.hi[1] > y) & (y > S.lo[1]) & (S.hi[2] > z) & (z > S.lo[2])) {
+    if (seal_in_aabb(S.lo, S.hi, x, y, z)) {
         xyzs[(size_t)i * 3] = S.to[0]; xyzs[(size_t)i * 3 + 1] = S.to[1]; xyzs[(size_t)i * 3 + 2] = S.to[2];
     }
 }
@@ -154,15 +174,11 @@ __global__ void __launch_bounds__(256) k_seal_anchor_apply(float *__restrict__ x
     if (i >= M) return;
     if (*A.flag != A.tag) { mask[i] = 0; return; }
     const float p[3] = {xyzs[(size_t)i * 3], xyzs[(size_t)i * 3 + 1], xyzs[(size_t)i * 3 + 2]};
-    // project_points(v_h, v_anchor, points), :736-744
-    const float along = dot3(p[0] - A.v_anchor[0], p[1] - A.v_anchor[1], p[2] - A.v_anchor[2], A.v_h[0], A.v_h[1], A.v_h[2]) /
-                        dot3(A.v_h[0], A.v_h[1], A.v_h[2], A.v_h[0], A.v_h[1], A.v_h[2]);
-    float proj[3], to_plane[3];
+    float proj[3], to_plane[3];                                // project_points(v_h, v_anchor, points)
+    project_point(A.v_h[0], A.v_h[1], A.v_h[2], dot3(A.v_h[0], A.v_h[1], A.v_h[2], A.v_h[0], A.v_h[1], A.v_h[2]), A.v_anchor[0], A.v_anchor[1], A.v_anchor[2],
+                  p[0], p[1], p[2], proj[0], proj[1], proj[2]);
     #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        proj[k] = p[k] - along * A.v_h[k];
-        to_plane[k] = proj[k] - p[k];
-    }
+    for (int k = 0; k < 3; k++) to_plane[k] = proj[k] - p[k];
     const float d = sqrtf(dot3(to_plane[0], to_plane[1], to_plane[2], to_plane[0], to_plane[1], to_plane[2]));   // points_plane_dist
     const float offset_scale = d / A.len_h;
     float pop[3], r[3];                                        // projected_offset_points, and their offset from the anchor
@@ -236,10 +252,7 @@ __global__ void __launch_bounds__(kBrushBlock) k_seal_brush_map(float *__restric
     bool cand = false;
     if (i < M) {
         x = xyzs[(size_t)i * 3]; y = xyzs[(size_t)i * 3 + 1]; z = xyzs[(size_t)i * 3 + 2];
-        if (x != 0.0f && y != 0.0f && z != 0.0f) {
-            for (uint32_t b = 0; b < A.n_bounds; b++)
-                cand |= (A.bounds[b][3] > x) & (x > A.bounds[b][0]) & (A.bounds[b][4] > y) & (y > A.bounds[b][1]) & (A.bounds[b][5] > z) & (z > A.bounds[b][2]);
-        }
+        cand = seal_in_bounds(A, x, y, z);
         if (!cand) mask[i] = 0;
     }
     // pack the candidates of the workgroup into its leading lanes
@@ -310,9 +323,8 @@ __global__ void __launch_bounds__(kBrushBlock) k_seal_brush_map(float *__restric
     mask[slot] = in ? 1 : 0;
     if (!in || A.mode != 0u) return;                           // dry brush: the mask only, no space mapping
     const float nx = A.normal_expand[0], ny = A.normal_expand[1], nz = A.normal_expand[2];
-    // project_points(normal_expand, center, p), :736-744
-    const float along = dot3(px - A.center[0], py - A.center[1], pz - A.center[2], nx, ny, nz) / dot3(nx, ny, nz, nx, ny, nz);
-    const float qx = px - along * nx, qy = py - along * ny, qz = pz - along * nz;
+    float qx, qy, qz;                                          // project_points(normal_expand, center, p)
+    project_point(nx, ny, nz, dot3(nx, ny, nz, nx, ny, nz), A.center[0], A.center[1], A.center[2], px, py, pz, qx, qy, qz);
     // distance to the nearest border point from coordinate differences (the minimum of the squares has the minimum's root)
     float best = INFINITY;
     for (uint32_t b = 0; b < A.n_border; b++) {
@@ -333,7 +345,7 @@ __device__ __forceinline__ void rgb_to_hsv(float r, float g, float b, float &h, 
     const float cmax = fmaxf(r, fmaxf(g, b)), cmin = fminf(r, fminf(g, b));
     const float delta = cmax - cmin;
     if (delta == 0.0f) h = 0.0f;
-    else if (r >= g && r >= b) { h = (g - b) / delta; h = h - 6.0f * floorf(h / 6.0f); }   // torch `% 6`; the first maximum wins ties
+    else if (r >= g && r >= b) { h = (g - b) / delta; h = h - 6.0f * floorf(h / 6.0f); }   // torch `% 6` (the result has the divisor's sign); the first maximum wins ties
     else if (g >= b) h = (b - r) / delta + 2.0f;
     else h = (r - g) / delta + 4.0f;
     h = h / 6.0f;
@@ -362,9 +374,10 @@ __device__ __forceinline__ void hsv_to_rgb(float h, float s, float v, float &o0,
 // integer: exact for the fp16- or fp32-valued colours of [0, 1] up to 2^-40 per sample and, above all, INDEPENDENT OF THE ORDER -- the
 // host-stepped loop and the device loop hold the same samples in different slots and must tint them by the same mean, bit for bit
 // (torch.mean's own fp32 pairwise order is library-defined; the two agree to ~1e-7, far inside the 1e-4 bar of the fixture test).
+constexpr double kSealFixedOne = 1099511627776.0;      // 1.0 in 2^-40 fixed point
 __device__ __forceinline__ unsigned long long seal_rgb_fixed_v(const float *__restrict__ rgbs, uint32_t i) {
     const float mx = fmaxf(rgbs[(size_t)i * 3], fmaxf(rgbs[(size_t)i * 3 + 1], rgbs[(size_t)i * 3 + 2]));
-    return (unsigned long long)((double)fminf(fmaxf(mx, 0.0f), 4.0f) * 1099511627776.0 + 0.5);
+    return (unsigned long long)((double)fminf(fmaxf(mx, 0.0f), 4.0f) * kSealFixedOne + 0.5);
 }
 __global__ void __launch_bounds__(256) k_seal_rgb_sum(const float *__restrict__ rgbs, const uint8_t *__restrict__ mask, SealSlots L,
                                                       unsigned long long *__restrict__ acc) {
@@ -385,25 +398,25 @@ __global__ void __launch_bounds__(256) k_seal_rgb_sum(const float *__restrict__ 
         atomicAdd(&acc[1], c);
     }
 }
-// pass 2: hue and saturation of the target colour, brightness re-centred on it (seal_utils.py:769-775), -> rgb, in place.  acc: the
-// {sum, count} pair of the call the slot belongs to
-__device__ __forceinline__ void seal_rgb_tint(float *__restrict__ rgbs, uint32_t i, float tr, float tg, float tb, float light_offset,
-                                              const unsigned long long *__restrict__ acc) {
-    const float mean = (float)(((double)acc[0] / 1099511627776.0) / (double)acc[1]);
-    float h, s, v, mh, ms, mv;
-    rgb_to_hsv(rgbs[(size_t)i * 3], rgbs[(size_t)i * 3 + 1], rgbs[(size_t)i * 3 + 2], h, s, v);
-    rgb_to_hsv(tr, tg, tb, mh, ms, mv);
-    const float nv = fminf(1.0f, fmaxf(0.0f, (mv + (v - mean)) + light_offset));
-    float o0, o1, o2;
-    hsv_to_rgb(mh, ms, nv, o0, o1, o2);
-    rgbs[(size_t)i * 3] = o0; rgbs[(size_t)i * 3 + 1] = o1; rgbs[(size_t)i * 3 + 2] = o2;
+// the mean V of a {sum, count} pair (count != 0)
+__device__ __forceinline__ float seal_mean_v(const unsigned long long *__restrict__ acc) {
+    return (float)(((double)acc[0] / kSealFixedOne) / (double)acc[1]);
 }
-__global__ void __launch_bounds__(256) k_seal_rgb_apply(float *__restrict__ rgbs, const uint8_t *__restrict__ mask, uint32_t M, float tr, float tg, float tb,
-                                                        float light_offset, const unsigned long long *__restrict__ acc) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M || !mask[i] || acc[1] == 0ull) return;      // (a masked slot outside the call's samples while none of them is masked: left alone)
-    seal_rgb_tint(rgbs, i, tr, tg, tb, light_offset, acc);
-}
+// pass 2 of one sample (k_seal_apply), the tint: hue and saturation of the target colour, brightness re-centred on it
+// (seal_utils.py:769-775), -> rgb, in place.  acc: the {sum, count} pair of the call the slot belongs to (count != 0)
+struct SealTint {
+    float r, g, b, light_offset;
+    __device__ __forceinline__ void operator()(float *__restrict__ rgbs, uint32_t i, const unsigned long long *__restrict__ acc) const {
+        const float mean = seal_mean_v(acc);
+        float h, s, v, mh, ms, mv;
+        rgb_to_hsv(rgbs[(size_t)i * 3], rgbs[(size_t)i * 3 + 1], rgbs[(size_t)i * 3 + 2], h, s, v);
+        rgb_to_hsv(r, g, b, mh, ms, mv);
+        const float nv = fminf(1.0f, fmaxf(0.0f, (mv + (v - mean)) + light_offset));
+        float o0, o1, o2;
+        hsv_to_rgb(mh, ms, nv, o0, o1, o2);
+        rgbs[(size_t)i * 3] = o0; rgbs[(size_t)i * 3 + 1] = o1; rgbs[(size_t)i * 3 + 2] = o2;
+    }
+};
 
 // ---- the tint of a WHOLE-RAY sample list (the one-pass renderer: march_rays_train's (offset, count) layout, every ray's samples up front) --
 // modify_rgb re-centres brightness on the mean V of the masked samples of ONE map_color call, and in the inference loop a call is one
@@ -514,16 +527,6 @@ __global__ void __launch_bounds__(256) k_seal_rgb_sum_iter(const float *__restri
         pending &= ~__ballot(now ? 1 : 0);
     }
 }
-// pass 2 per iteration: a masked slot is tinted by the mean of its own iteration
-__global__ void __launch_bounds__(256) k_seal_rgb_apply_iter(float *__restrict__ rgbs, const uint8_t *__restrict__ mask, const int32_t *__restrict__ slot_iter,
-                                                             uint32_t M, float tr, float tg, float tb, float light_offset,
-                                                             const unsigned long long *__restrict__ acc) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M || !mask[i]) return;
-    const int32_t it = slot_iter[i];
-    if (it == kNoIteration || acc[2 * (size_t)it + 1] == 0ull) return;
-    seal_rgb_tint(rgbs, i, tr, tg, tb, light_offset, acc + 2 * (size_t)it);
-}
 
 // ---- the brush's texture stamp, the `image` branch of SealMapper.map_color, seal_utils.py:58-79 -------------------------------------------
 // A streaming pass: per masked sample 12 + 12 bytes of position and colour in, one 16-byte texel record, 12 bytes out.  The texture is
@@ -546,49 +549,53 @@ __global__ void __launch_bounds__(256) k_seal_image_texels(float4 *__restrict__ 
     texels[i] = make_float4(h, s, v, t.w);
 }
 
-// pass 2 of one sample, the reference's fp32 statements in their order (dot products accumulated x, y, z).  acc: the {sum, count} pair of
-// the call the slot belongs to (count != 0)
-__device__ __forceinline__ void seal_image_stamp(float *__restrict__ rgbs, const float *__restrict__ xyzs, uint32_t i, const SealImageArgs &A,
-                                                 const unsigned long long *__restrict__ acc) {
-    const float mean = (float)(((double)acc[0] / 1099511627776.0) / (double)acc[1]);
-    const float px = xyzs[(size_t)i * 3], py = xyzs[(size_t)i * 3 + 1], pz = xyzs[(size_t)i * 3 + 2];
-    // project_points(v_image_norm, v_image_o, points), :736-744
-    const float along = dot3(px - A.v_o[0], py - A.v_o[1], pz - A.v_o[2], A.v_norm[0], A.v_norm[1], A.v_norm[2]) / A.norm_sq;
-    const float qx = px - along * A.v_norm[0], qy = py - along * A.v_norm[1], qz = pz - along * A.v_norm[2];
-    const float ox = qx - A.v_o[0], oy = qy - A.v_o[1], oz = qz - A.v_o[2];                      // v_op
-    // idx = min(max(0, floor(v_op . v_ow / len_ow^2 * W)), W - 1), :72-75 (fmaxf sends a NaN to texel 0: the index stays in bounds)
-    const float fw = floorf(dot3(ox, oy, oz, A.v_ow[0], A.v_ow[1], A.v_ow[2]) / A.len_ow_sq * (float)A.W);
-    const float fh = floorf(dot3(ox, oy, oz, A.v_oh[0], A.v_oh[1], A.v_oh[2]) / A.len_oh_sq * (float)A.H);
-    // (the upper clamp is taken on integers: (float)(W - 1) may round up for W > 2^24; W, H < 2^28)
-    const uint32_t iw = min((uint32_t)fminf(fmaxf(fw, 0.0f), 268435456.0f), A.W - 1u);
-    const uint32_t ih = min((uint32_t)fminf(fmaxf(fh, 0.0f), 268435456.0f), A.H - 1u);
-    const float4 tex = A.texels[(size_t)ih * A.W + iw];
-    // modify_rgb(colors, image[idx_h, idx_w], rgb_light_offset), :761-777
-    const float r = rgbs[(size_t)i * 3], g = rgbs[(size_t)i * 3 + 1], b = rgbs[(size_t)i * 3 + 2];
-    float h, s, v;
-    rgb_to_hsv(r, g, b, h, s, v);
-    const float nv = fminf(1.0f, fmaxf(0.0f, (tex.z + (v - mean)) + A.light_offset));
-    float o0, o1, o2;
-    hsv_to_rgb(tex.x, tex.y, nv, o0, o1, o2);
-    // colors = mask * modified + (1 - mask) * colors, :79
-    const float a = tex.w, na = 1.0f - tex.w;
-    rgbs[(size_t)i * 3] = a * o0 + na * r; rgbs[(size_t)i * 3 + 1] = a * o1 + na * g; rgbs[(size_t)i * 3 + 2] = a * o2 + na * b;
-}
-__global__ void __launch_bounds__(256) k_seal_image_apply(float *__restrict__ rgbs, const float *__restrict__ xyzs, const uint8_t *__restrict__ mask, uint32_t M,
-                                                          SealImageArgs A, const unsigned long long *__restrict__ acc) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M || !mask[i] || acc[1] == 0ull) return;      // (as k_seal_rgb_apply: none of the call's samples is masked -> nothing changes)
-    seal_image_stamp(rgbs, xyzs, i, A, acc);
-}
-// the stamp of a whole-ray sample list: a masked slot is stamped with the mean of its own iteration (as k_seal_rgb_apply_iter)
-__global__ void __launch_bounds__(256) k_seal_image_apply_iter(float *__restrict__ rgbs, const float *__restrict__ xyzs, const uint8_t *__restrict__ mask,
-                                                               const int32_t *__restrict__ slot_iter, uint32_t M, SealImageArgs A,
-                                                               const unsigned long long *__restrict__ acc) {
+// pass 2 of one sample (k_seal_apply), the stamp: the reference's fp32 statements in their order (dot products accumulated x, y, z).
+// xyzs: the samples' mapped positions; acc: the {sum, count} pair of the call the slot belongs to (count != 0)
+struct SealStamp {
+    const float *xyzs;
+    SealImageArgs A;
+    __device__ __forceinline__ void operator()(float *__restrict__ rgbs, uint32_t i, const unsigned long long *__restrict__ acc) const {
+        const float mean = seal_mean_v(acc);
+        const float px = xyzs[(size_t)i * 3], py = xyzs[(size_t)i * 3 + 1], pz = xyzs[(size_t)i * 3 + 2];
+        float qx, qy, qz;                                                                            // project_points(v_image_norm, v_image_o, points)
+        project_point(A.v_norm[0], A.v_norm[1], A.v_norm[2], A.norm_sq, A.v_o[0], A.v_o[1], A.v_o[2], px, py, pz, qx, qy, qz);
+        const float ox = qx - A.v_o[0], oy = qy - A.v_o[1], oz = qz - A.v_o[2];                      // v_op
+        // idx = min(max(0, floor(v_op . v_ow / len_ow^2 * W)), W - 1), :72-75 (fmaxf sends a NaN to texel 0: the index stays in bounds)
+        const float fw = floorf(dot3(ox, oy, oz, A.v_ow[0], A.v_ow[1], A.v_ow[2]) / A.len_ow_sq * (float)A.W);
+        const float fh = floorf(dot3(ox, oy, oz, A.v_oh[0], A.v_oh[1], A.v_oh[2]) / A.len_oh_sq * (float)A.H);
+        // (the upper clamp is taken on integers: (float)(W - 1) may round up for W > 2^24; W, H < 2^28)
+        const uint32_t iw = min((uint32_t)fminf(fmaxf(fw, 0.0f), 268435456.0f), A.W - 1u);
+        const uint32_t ih = min((uint32_t)fminf(fmaxf(fh, 0.0f), 268435456.0f), A.H - 1u);
+        const float4 tex = A.texels[(size_t)ih * A.W + iw];
+        // modify_rgb(colors, image[idx_h, idx_w], rgb_light_offset), :761-777
+        const float r = rgbs[(size_t)i * 3], g = rgbs[(size_t)i * 3 + 1], b = rgbs[(size_t)i * 3 + 2];
+        float h, s, v;
+        rgb_to_hsv(r, g, b, h, s, v);
+        const float nv = fminf(1.0f, fmaxf(0.0f, (tex.z + (v - mean)) + A.light_offset));
+        float o0, o1, o2;
+        hsv_to_rgb(tex.x, tex.y, nv, o0, o1, o2);
+        // colors = mask * modified + (1 - mask) * colors, :79
+        const float a = tex.w, na = 1.0f - tex.w;
+        rgbs[(size_t)i * 3] = a * o0 + na * r; rgbs[(size_t)i * 3 + 1] = a * o1 + na * g; rgbs[(size_t)i * 3 + 2] = a * o2 + na * b;
+    }
+};
+
+// pass 2, the tint (Op = SealTint) or the stamp (SealStamp) of the masked slots, each by the mean of the call it belongs to: acc is the
+// call's {sum, count} pair, or, for a whole-ray list (kPerIteration), the pairs of its iterations -- a slot takes that of its own.  A
+// masked slot of a call none of whose samples is masked (count == 0: the slot lies outside the call's live list) and a slot the loop
+// never marched are left alone
+template <bool kPerIteration, class Op>
+__global__ void __launch_bounds__(256) k_seal_apply(float *__restrict__ rgbs, const uint8_t *__restrict__ mask, const int32_t *__restrict__ slot_iter,
+                                                    uint32_t M, Op op, const unsigned long long *__restrict__ acc) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M || !mask[i]) return;
-    const int32_t it = slot_iter[i];
-    if (it == kNoIteration || acc[2 * (size_t)it + 1] == 0ull) return;
-    seal_image_stamp(rgbs, xyzs, i, A, acc + 2 * (size_t)it);
+    if (kPerIteration) {
+        const int32_t it = slot_iter[i];
+        if (it == kNoIteration) return;
+        acc += 2 * (size_t)it;
+    }
+    if (acc[1] == 0ull) return;
+    op(rgbs, i, acc);
 }
 
 // color_utils.py:31-63 + seal_utils.py:747-758 on the masked samples, in place
@@ -596,45 +603,37 @@ __global__ void __launch_bounds__(256) k_seal_hsv(float *__restrict__ rgbs, cons
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M || !mask[i]) return;
     const float r = rgbs[(size_t)i * 3], g = rgbs[(size_t)i * 3 + 1], b = rgbs[(size_t)i * 3 + 2];
-    const float cmax = fmaxf(r, fmaxf(g, b)), cmin = fminf(r, fminf(g, b));
-    const float delta = cmax - cmin;
-    float h;
-    if (delta == 0.0f) h = 0.0f;
-    else if (r >= g && r >= b) { h = (g - b) / delta; h = h - 6.0f * floorf(h / 6.0f); }   // torch `% 6` (result has the divisor's sign); first max wins ties
-    else if (g >= b) h = (b - r) / delta + 2.0f;
-    else h = (r - g) / delta + 4.0f;
-    h = h / 6.0f + mh;
-    const float s = (cmax == 0.0f ? 0.0f : delta / cmax) + ms;
-    const float v = cmax + mv;
-    const float c = v * s;
-    const float h6 = h * 6.0f;
-    const float xx = c * (-fabsf((h6 - 2.0f * floorf(h6 / 2.0f)) - 1.0f) + 1.0f);
-    const float m = v - c;
-    const uint32_t idx = ((uint32_t)(uint8_t)(int)h6) % 6u;   // `.type(torch.uint8)` truncation, then % 6
-    float o0, o1, o2;
-    switch (idx) {
-        case 0: o0 = c; o1 = xx; o2 = 0; break;
-        case 1: o0 = xx; o1 = c; o2 = 0; break;
-        case 2: o0 = 0; o1 = c; o2 = xx; break;
-        case 3: o0 = 0; o1 = xx; o2 = c; break;
-        case 4: o0 = xx; o1 = 0; o2 = c; break;
-        default: o0 = c; o1 = 0; o2 = xx; break;
-    }
-    rgbs[(size_t)i * 3] = o0 + m; rgbs[(size_t)i * 3 + 1] = o1 + m; rgbs[(size_t)i * 3 + 2] = o2 + m;
+    float h, s, v, o0, o1, o2;
+    rgb_to_hsv(r, g, b, h, s, v);
+    hsv_to_rgb(h + mh, s + ms, v + mv, o0, o1, o2);
+    rgbs[(size_t)i * 3] = o0; rgbs[(size_t)i * 3 + 1] = o1; rgbs[(size_t)i * 3 + 2] = o2;
 }
 
 // One tag per call that asks "did this call map anything": unique in the process, so any flag word sees increasing tags whichever entry
 // points share it (a wrap after 2^32 calls would need the flag cleared: not in this process's life)
 std::atomic<uint32_t> g_seal_tag{0};
 
-int fill_box_test(SealBoxTest &b, const float *bounds, uint32_t n_bounds, const float *tris, uint32_t n_tris, const float *test_dir) {
+// one lane per element (sample slot, ray): kernel(args...) over n lanes
+template <class... Params, class... Args>
+void launch_lanes(void (*kernel)(Params...), uint32_t n, void *stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3(sdn_div_up(n, 256u)), dim3(256), 0, (hipStream_t)stream, args...);
+}
+
+// checks and fills what the box test and the brush's arguments share: bounds, n_bounds, n_tris, test_dir (B: SealBoxTest or SealBrushArgs)
+template <class B>
+int fill_bounds(B &b, const float *bounds, uint32_t n_bounds, const float *tris, uint32_t n_tris, const float *test_dir) {
     if (!bounds || !tris || !test_dir) return SDN_E_BADARG;
     if (n_bounds == 0 || n_bounds > 4 || n_tris == 0) return SDN_E_UNSUPPORTED;
     for (uint32_t k = 0; k < n_bounds; k++)
         for (int j = 0; j < 6; j++) b.bounds[k][j] = bounds[6 * k + j];
-    b.n_bounds = n_bounds; b.tris = tris; b.n_tris = n_tris;
+    b.n_bounds = n_bounds; b.n_tris = n_tris;
     for (int k = 0; k < 3; k++) b.test_dir[k] = test_dir[k];
     return 0;
+}
+
+int fill_box_test(SealBoxTest &b, const float *bounds, uint32_t n_bounds, const float *tris, uint32_t n_tris, const float *test_dir) {
+    b.tris = tris;
+    return fill_bounds(b, bounds, n_bounds, tris, n_tris, test_dir);
 }
 
 int fill_image_args(SealImageArgs &a, const SdnSealImage *im) {
@@ -644,6 +643,29 @@ int fill_image_args(SealImageArgs &a, const SdnSealImage *im) {
     for (int k = 0; k < 3; k++) { a.v_o[k] = im->v_o[k]; a.v_norm[k] = im->v_norm[k]; a.v_ow[k] = im->v_ow[k]; a.v_oh[k] = im->v_oh[k]; }
     a.norm_sq = im->norm_sq; a.len_ow_sq = im->len_ow_sq; a.len_oh_sq = im->len_oh_sq; a.light_offset = im->light_offset;
     return 0;
+}
+
+// The two passes of modify_rgb with `op` (SealTint, SealStamp) as the second, on the masked samples of one call: clear the {sum, count}
+// pair in scratch16, sum V over the call's samples L, apply.  Three stream operations.
+template <class Op>
+int seal_recolour(float *rgbs, const uint8_t *mask, uint32_t M, const Op &op, void *scratch16, const SealSlots &L, void *stream) {
+    if (hipMemsetAsync(scratch16, 0, 16, (hipStream_t)stream) != hipSuccess) return sdn_launch_status();
+    launch_lanes(k_seal_rgb_sum, M, stream, rgbs, mask, L, (unsigned long long *)scratch16);
+    launch_lanes(k_seal_apply<false, Op>, M, stream, rgbs, mask, nullptr, M, op, (const unsigned long long *)scratch16);
+    return sdn_launch_status();
+}
+
+// The same on a whole-ray sample list, as the inference loop does it: sdn_whole_rays_schedule, then the two passes per iteration.
+// scratch: 16 * (max_steps + 8) bytes (cleared here).  Six stream operations.
+template <class Op>
+int seal_recolour_whole_rays(float *rgbs, const uint8_t *mask, const int32_t *rays, const float *sigmas, const float *deltas, uint32_t M, uint32_t N,
+                             float T_thresh, uint32_t max_steps, const Op &op, void *scratch, int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter,
+                             void *stream) {
+    if (int rc = sdn_whole_rays_schedule(rays, sigmas, deltas, M, N, T_thresh, max_steps, ray_stop, slot_iter, n_iter, stream)) return rc;
+    if (hipMemsetAsync(scratch, 0, 16 * ((size_t)max_steps + 8), (hipStream_t)stream) != hipSuccess) return sdn_launch_status();
+    launch_lanes(k_seal_rgb_sum_iter, M, stream, rgbs, mask, slot_iter, M, (unsigned long long *)scratch);
+    launch_lanes(k_seal_apply<true, Op>, M, stream, rgbs, mask, slot_iter, M, op, (const unsigned long long *)scratch);
+    return sdn_launch_status();
 }
 
 }  // namespace
@@ -660,7 +682,7 @@ int sdn_seal_bbox_map(float *xyzs, float *dirs, uint32_t M, const float *bounds,
     for (int k = 0; k < 3; k++) { a.scale[k] = scale[k]; a.center[k] = center[k]; }
     for (int k = 0; k < 12; k++) a.tinv[k] = tinv[k];
     for (int k = 0; k < 9; k++) a.rinv[k] = rinv[k];
-    hipLaunchKernelGGL(k_seal_bbox_map, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, xyzs, dirs, M, a, mask);
+    launch_lanes(k_seal_bbox_map, M, stream, xyzs, dirs, M, a, mask);
     return sdn_launch_status();
 }
 
@@ -680,8 +702,8 @@ int sdn_seal_bbox_map_source(float *xyzs, float *dirs, uint32_t M, const float *
     for (int k = 0; k < 3; k++) { sa.lo[k] = source_bound[k]; sa.hi[k] = source_bound[3 + k]; sa.to[k] = map_source[k]; }
     sa.tag = tag; sa.flag = flag;
     const SealSlots L{live_idx, live_count, state, M};
-    hipLaunchKernelGGL(k_seal_any, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)mask, L, flag, tag);
-    hipLaunchKernelGGL(k_seal_source_redirect, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, xyzs, (const uint8_t *)mask, M, sa);
+    launch_lanes(k_seal_any, M, stream, mask, L, flag, tag);
+    launch_lanes(k_seal_source_redirect, M, stream, xyzs, mask, M, sa);
     return sdn_launch_status();
 }
 
@@ -703,10 +725,9 @@ int sdn_seal_anchor_map(float *xyzs, float *dirs, uint32_t M, const float *bound
     a.len_h = len_h; a.radius = radius; a.flag = flag;
     const uint32_t tag = a.tag = ++g_seal_tag;
     const SealSlots L{live_idx, live_count, state, M};
-    const dim3 grid(sdn_div_up(M, 256u)), block(256);
-    hipLaunchKernelGGL(k_seal_box_mask, grid, block, 0, (hipStream_t)stream, (const float *)xyzs, M, b, mask);
-    hipLaunchKernelGGL(k_seal_any, grid, block, 0, (hipStream_t)stream, (const uint8_t *)mask, L, flag, tag);
-    hipLaunchKernelGGL(k_seal_anchor_apply, grid, block, 0, (hipStream_t)stream, xyzs, M, a, mask);
+    launch_lanes(k_seal_box_mask, M, stream, xyzs, M, b, mask);
+    launch_lanes(k_seal_any, M, stream, mask, L, flag, tag);
+    launch_lanes(k_seal_anchor_apply, M, stream, xyzs, M, a, mask);
     return sdn_launch_status();
 }
 
@@ -717,14 +738,13 @@ int sdn_seal_brush_map(float *xyzs, float *dirs, uint32_t M, const float *bounds
                        const float *border, uint32_t n_border, uint8_t *mask, void *stream) {
     (void)dirs;
     if (M == 0) return 0;
-    if (!xyzs || !bounds || !tris || !test_dir || !normal_expand || !center || !mask || ((uintptr_t)tris & 15u) != 0) return SDN_E_BADARG;
-    if (n_bounds == 0 || n_bounds > 4 || n_tris == 0 || mode > 1u) return SDN_E_UNSUPPORTED;
-    if (mode == 0u && (!border || n_border == 0)) return SDN_E_BADARG;
+    if (!xyzs || !normal_expand || !center || !mask || ((uintptr_t)tris & 15u) != 0) return SDN_E_BADARG;
     SealBrushArgs a;
-    for (uint32_t k = 0; k < n_bounds; k++)
-        for (int j = 0; j < 6; j++) a.bounds[k][j] = bounds[6 * k + j];
-    a.n_bounds = n_bounds; a.n_tris = n_tris; a.n_border = n_border;
-    for (int k = 0; k < 3; k++) { a.test_dir[k] = test_dir[k]; a.normal_expand[k] = normal_expand[k]; a.center[k] = center[k]; }
+    if (int rc = fill_bounds(a, bounds, n_bounds, tris, n_tris, test_dir)) return rc;      // (its NULL checks before every count check, as above)
+    if (mode > 1u) return SDN_E_UNSUPPORTED;
+    if (mode == 0u && (!border || n_border == 0)) return SDN_E_BADARG;
+    a.n_border = n_border;
+    for (int k = 0; k < 3; k++) { a.normal_expand[k] = normal_expand[k]; a.center[k] = center[k]; }
     a.attenuation_distance = attenuation_distance; a.mode = mode;
     hipLaunchKernelGGL(k_seal_brush_map, dim3(sdn_div_up(M, kBrushBlock)), dim3(kBrushBlock), 0, (hipStream_t)stream, xyzs, M, a, (const float4 *)tris, border,
                        mask);
@@ -738,12 +758,7 @@ int sdn_seal_modify_rgb(float *rgbs, const uint8_t *mask, uint32_t M, float r, f
                         const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state, void *stream) {
     if (M == 0) return 0;
     if (!rgbs || !mask || !scratch16 || ((uintptr_t)scratch16 & 7u) != 0 || (live_idx && !live_count)) return SDN_E_BADARG;
-    if (hipMemsetAsync(scratch16, 0, 16, (hipStream_t)stream) != hipSuccess) return sdn_launch_status();
-    const SealSlots L{live_idx, live_count, state, M};
-    hipLaunchKernelGGL(k_seal_rgb_sum, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, (const float *)rgbs, mask, L, (unsigned long long *)scratch16);
-    hipLaunchKernelGGL(k_seal_rgb_apply, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, rgbs, mask, M, r, g, b, light_offset,
-                       (const unsigned long long *)scratch16);
-    return sdn_launch_status();
+    return seal_recolour(rgbs, mask, M, SealTint{r, g, b, light_offset}, scratch16, SealSlots{live_idx, live_count, state, M}, stream);
 }
 
 uint32_t sdn_whole_rays_schedule_max_rays(void) { return kScheduleBlock * kScheduleMaxPerLane; }
@@ -757,7 +772,7 @@ int sdn_whole_rays_schedule(const int32_t *rays, const float *sigmas, const floa
     if (N > kScheduleBlock * kScheduleMaxPerLane) return SDN_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(slot_iter, 0xFF, (size_t)M * sizeof(int32_t), st) != hipSuccess) return sdn_launch_status();
-    hipLaunchKernelGGL(k_whole_rays_stop, dim3(sdn_div_up(N, 256u)), dim3(256), 0, st, sigmas, deltas, rays, M, N, T_thresh, ray_stop);
+    launch_lanes(k_whole_rays_stop, N, stream, sigmas, deltas, rays, M, N, T_thresh, ray_stop);
     const uint32_t per_lane = sdn_div_up(N, kScheduleBlock);
     #define SDN_SCHEDULE(R) hipLaunchKernelGGL(k_whole_rays_schedule<R>, dim3(1), dim3(kScheduleBlock), 0, st, rays, (const int32_t *)ray_stop, N, max_steps, slot_iter, n_iter)
     if (per_lane <= 1) SDN_SCHEDULE(1);
@@ -776,14 +791,8 @@ int sdn_seal_modify_rgb_whole_rays(float *rgbs, const uint8_t *mask, const int32
                                    int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter, void *stream) {
     if (M == 0 || N == 0) return 0;
     if (!rgbs || !mask || !scratch || ((uintptr_t)scratch & 7u) != 0) return SDN_E_BADARG;
-    if (int rc = sdn_whole_rays_schedule(rays, sigmas, deltas, M, N, T_thresh, max_steps, ray_stop, slot_iter, n_iter, stream)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(scratch, 0, 16 * ((size_t)max_steps + 8), st) != hipSuccess) return sdn_launch_status();
-    hipLaunchKernelGGL(k_seal_rgb_sum_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, (const float *)rgbs, mask, (const int32_t *)slot_iter, M,
-                       (unsigned long long *)scratch);
-    hipLaunchKernelGGL(k_seal_rgb_apply_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, rgbs, mask, (const int32_t *)slot_iter, M, r, g, b, light_offset,
-                       (const unsigned long long *)scratch);
-    return sdn_launch_status();
+    return seal_recolour_whole_rays(rgbs, mask, rays, sigmas, deltas, M, N, T_thresh, max_steps, SealTint{r, g, b, light_offset}, scratch, ray_stop, slot_iter,
+                                    n_iter, stream);
 }
 
 int sdn_seal_image_texels(float *texels, uint64_t n, void *stream) {
@@ -800,14 +809,9 @@ int sdn_seal_modify_image(float *rgbs, const float *xyzs, const uint8_t *mask, u
                           const uint32_t *live_idx, const uint32_t *live_count, const int32_t *state, void *stream) {
     if (M == 0) return 0;
     if (!rgbs || !xyzs || !mask || !scratch16 || ((uintptr_t)scratch16 & 7u) != 0 || (live_idx && !live_count)) return SDN_E_BADARG;
-    SealImageArgs a;
-    if (int rc = fill_image_args(a, image)) return rc;
-    if (hipMemsetAsync(scratch16, 0, 16, (hipStream_t)stream) != hipSuccess) return sdn_launch_status();
-    const SealSlots L{live_idx, live_count, state, M};
-    hipLaunchKernelGGL(k_seal_rgb_sum, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, (const float *)rgbs, mask, L, (unsigned long long *)scratch16);
-    hipLaunchKernelGGL(k_seal_image_apply, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, rgbs, xyzs, mask, M, a,
-                       (const unsigned long long *)scratch16);
-    return sdn_launch_status();
+    SealStamp op{xyzs, {}};
+    if (int rc = fill_image_args(op.A, image)) return rc;
+    return seal_recolour(rgbs, mask, M, op, scratch16, SealSlots{live_idx, live_count, state, M}, stream);
 }
 
 // The stamp on a whole-ray sample list, as the inference loop applies it: sdn_whole_rays_schedule, the per-iteration sum pass of
@@ -817,22 +821,15 @@ int sdn_seal_modify_image_whole_rays(float *rgbs, const float *xyzs, const uint8
                                      int32_t *ray_stop, int32_t *slot_iter, int32_t *n_iter, void *stream) {
     if (M == 0 || N == 0) return 0;
     if (!rgbs || !xyzs || !mask || !scratch || ((uintptr_t)scratch & 7u) != 0) return SDN_E_BADARG;
-    SealImageArgs a;
-    if (int rc = fill_image_args(a, image)) return rc;
-    if (int rc = sdn_whole_rays_schedule(rays, sigmas, deltas, M, N, T_thresh, max_steps, ray_stop, slot_iter, n_iter, stream)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(scratch, 0, 16 * ((size_t)max_steps + 8), st) != hipSuccess) return sdn_launch_status();
-    hipLaunchKernelGGL(k_seal_rgb_sum_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, (const float *)rgbs, mask, (const int32_t *)slot_iter, M,
-                       (unsigned long long *)scratch);
-    hipLaunchKernelGGL(k_seal_image_apply_iter, dim3(sdn_div_up(M, 256u)), dim3(256), 0, st, rgbs, xyzs, mask, (const int32_t *)slot_iter, M, a,
-                       (const unsigned long long *)scratch);
-    return sdn_launch_status();
+    SealStamp op{xyzs, {}};
+    if (int rc = fill_image_args(op.A, image)) return rc;
+    return seal_recolour_whole_rays(rgbs, mask, rays, sigmas, deltas, M, N, T_thresh, max_steps, op, scratch, ray_stop, slot_iter, n_iter, stream);
 }
 
 int sdn_seal_modify_hsv(float *rgbs, const uint8_t *mask, uint32_t M, float dh, float ds, float dv, void *stream) {
     if (M == 0) return 0;
     if (!rgbs || !mask) return SDN_E_BADARG;
-    hipLaunchKernelGGL(k_seal_hsv, dim3(sdn_div_up(M, 256u)), dim3(256), 0, (hipStream_t)stream, rgbs, mask, M, dh, ds, dv);
+    launch_lanes(k_seal_hsv, M, stream, rgbs, mask, M, dh, ds, dv);
     return sdn_launch_status();
 }
 

@@ -580,8 +580,7 @@ class DeviceLoop:
         """Hooks a SealD seal mapper (`dnerf_amd.seal_mapper.SealBBoxMapper` / `SealAnchorMapper` / `SealBrushMapper`, or None) into every iteration of the
         native loop: samples are mapped back to their origin before the field kernel, colours of the mapped samples re-mapped after it."""
         import ctypes
-        from sdn_backend import SdnSealBox, SdnSealBrush, SEAL_ANCHOR, SEAL_BBOX, SEAL_BRUSH
-        from .seal_mapper import SealAnchorMapper, SealBrushMapper
+        import sdn_backend
         c = self.ctx
         self.mapper = mapper
         if mapper is None:
@@ -590,35 +589,24 @@ class DeviceLoop:
         dev = self.buf["xyzs"].device
         mapper.map_data_conversion(self.buf["xyzs"])
         a = mapper._native_args(dev)
-        anchor, brush = isinstance(mapper, SealAnchorMapper), isinstance(mapper, SealBrushMapper)
-        if self.frames > 1 and (anchor or mapper.redirects_source or "rgb" in mapper.map_data or "image" in mapper.map_data):
+        kind = getattr(sdn_backend, mapper.native_kind)
+        if self.frames > 1 and (kind == sdn_backend.SEAL_ANCHOR or mapper.redirects_source or "rgb" in mapper.map_data or "image" in mapper.map_data):
             # these look at ALL samples of a loop iteration (the mean brightness of the masked ones -- the tint's and the texture stamp's --,
             # "does the call map anything" of mapSource and of the anchor mapper): in a frame group an iteration holds several frames'
             # samples, which the reference never mixes (the brush maps every sample on its own: without a tint or a stamp it runs on frame groups)
             raise NotImplementedError("mapSource / rgb tint / texture stamp / the anchor mapper depend on the set of samples of an iteration: "
                                       "render such edits one frame per loop")
-        box = SdnSealBox()
+        box = sdn_backend.SdnSealBox()
         for k in range(6 * a["n_bounds"]):
             box.bounds[k] = a["bounds"][k]
         box.n_bounds, box.n_tris, box.tris = a["n_bounds"], a["n_tris"], a["tris"].data_ptr()
-        box.kind = SEAL_ANCHOR if anchor else SEAL_BRUSH if brush else SEAL_BBOX
-        rec = None
-        if brush:
-            fields = (("test_dir", 3),)
-            rec = SdnSealBrush()
-            for k in range(3):
-                rec.normal_expand[k], rec.center[k] = a["normal_expand"][k], a["center"][k]
-            rec.attenuation_distance, rec.mode = a["attenuation_distance"], a["mode"]
-            rec.border, rec.n_border = a["border"].data_ptr(), a["n_border"]
-            rec.image = ctypes.addressof(a["image"]) if "image" in a else None      # the texture stamp (`a` is kept alive below)
-        elif anchor:
-            fields = (("test_dir", 3), ("scale", 3), ("v_anchor", 3), ("v_offset", 3), ("v_h", 3))
-            box.len_h, box.radius = a["len_h"], a["radius"]
-        else:
-            fields = (("test_dir", 3), ("tinv", 12), ("rinv", 9), ("scale", 3), ("center", 3))
-        for name, n in fields:
-            for k in range(n):
+        box.kind = kind
+        for name, n in mapper.native_box_fields:
+            if n is None:
+                setattr(box, name, a[name])
+            for k in range(n or 0):
                 getattr(box, name)[k] = a[name][k]
+        rec = mapper._native_brush_record(a)           # (`a`, which it points into, is kept alive below)
         if "hsv" in mapper.map_data:
             h = [float(v) for v in mapper.map_data["hsv"].reshape(-1).tolist()]
             box.hsv[0], box.hsv[1], box.hsv[2], box.modify_hsv = h[0], h[1], h[2], 1

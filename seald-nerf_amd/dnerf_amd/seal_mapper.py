@@ -146,6 +146,14 @@ class SealMapper:
         self.map_triangles = None
         self.map_test_dir = None
 
+    def _read_color_options(self):
+        """The config's colour options (seal_utils.py: the tail of every mapper's constructor) into `map_data`."""
+        if "hsv" in self.config:
+            self.map_data["hsv"] = self.config["hsv"]
+        if "rgb" in self.config:
+            self.map_data["rgb"] = self.config["rgb"]
+            self.map_data["rgb_light_offset"] = self.config.get("rgbLightOffset", 0)
+
     def map_data_conversion(self, T=None, force=False):
         if T is None and not force:
             return
@@ -202,7 +210,18 @@ class SealMapper:
             colors = mask * modified_colors + (1 - mask) * colors
         return colors
 
+    @torch.no_grad()
     def map_to_origin(self, points, dirs=None):
+        """-> (points', dirs', mask): the mapped samples taken back to where their content comes from (each mapper's docstring says how).
+        CUDA fp32 inputs take the HIP kernel (on copies, as the reference returns copies); everything else the mapper's torch
+        restatement `_map_to_origin_torch`."""
+        if self._native_ok(points, dirs):
+            self.map_data_conversion(points)
+            p, d = points.clone(), dirs.clone()
+            return p, d, self.map_to_origin_(p, d)
+        return self._map_to_origin_torch(points, dirs)
+
+    def _map_to_origin_torch(self, points, dirs=None):
         raise NotImplementedError()
 
     @property
@@ -212,8 +231,17 @@ class SealMapper:
         return False
 
     # ---- device fast path: csrc/seal.hip, one lane per sample slot, in place ---------------------------------------------
-    # (shared by the mappers: the box test's arguments and the colour part are the same for all of them; `_native_map_args` adds a
-    #  mapper's own `map_to_origin` constants, `map_to_origin_` is its kernel call)
+    # (shared by the mappers: the box test's arguments, the colour part and the frame of `map_to_origin_` are the same for all of them;
+    #  `_native_map_args` adds a mapper's own `map_to_origin` constants, `_native_map` is its kernel call.  For the device loop's records
+    #  (`DeviceLoop.set_mapper`) a mapper states `native_kind`, the name of its `SdnSealBox.kind` in sdn_backend, and `native_box_fields`,
+    #  the (name, length) array fields -- length None: a scalar -- of `SdnSealBox` it fills from `_native_args`, beside the box test's)
+    native_kind = None
+    native_box_fields = ()
+
+    def _native_brush_record(self, a):
+        """The mapper's `SdnSealBrush` record from `_native_args`: the brush's; None for every other mapper."""
+        return None
+
     def _native_ok(self, points, dirs):
         return (points.is_cuda and dirs is not None and points.dtype == torch.float32 and dirs.dtype == torch.float32
                 and points.is_contiguous() and dirs.is_contiguous())
@@ -268,8 +296,21 @@ class SealMapper:
         rec.light_offset = float(np.float32(md["rgb_light_offset"]))
         return dict(image=rec, image_texels=texels, image_scratch=torch.zeros(16, dtype=torch.uint8, device=device))
 
-    def map_to_origin_(self, points, dirs):
+    def _native_map(self, lib, a, points, dirs, M, mask):
+        """The mapper's one `lib.sdn_seal_*_map` call on the sample buffers -> (the call's name for the error text, its return code)."""
         raise NotImplementedError()
+
+    @torch.no_grad()
+    def map_to_origin_(self, points, dirs):
+        """In-place `map_to_origin` on the sample buffers (CUDA fp32 contiguous) -> bool mask [M]; the mapper's kernel of csrc/seal.hip.
+        Every slot of the buffers is a sample of the call."""
+        from sdn_backend import lib, check
+        a = self._native_args(points.device)
+        M = points.shape[0]
+        mask = torch.empty(M, dtype=torch.uint8, device=points.device)
+        what, rc = self._native_map(lib, a, points, dirs, M, mask)
+        check(rc, what)
+        return mask.view(torch.bool)
 
     @torch.no_grad()
     def map_color_(self, rgbs, mask, whole_rays=None, points=None):
@@ -293,37 +334,34 @@ class SealMapper:
                 raise ValueError(f"map_color_: {points.shape[0]} points for {rgbs.shape[0]} colours")
             native = native and points.is_cuda and points.dtype == torch.float32 and points.is_contiguous()
         if native:
+            import ctypes
             from sdn_backend import lib, check, ptr, stream
             m8 = mask.view(torch.uint8)
+            M, w = rgbs.shape[0], whole_rays
+            if w is not None:      # the whole-ray calls' arguments around the edit's own (target colour or image record, scratch)
+                w_list = (ptr(w.rays, torch.int32, "rays"), ptr(w.sigmas, torch.float32, "sigmas"), ptr(w.deltas, torch.float32, "deltas"), M, w.N, w.T_thresh,
+                          w.max_steps)
+                w_work = (ptr(w.ray_stop, torch.int32, "ray_stop"), ptr(w.slot_iter, torch.int32, "slot_iter"), ptr(w.n_iter, torch.int32, "n_iter"), stream())
             if "hsv" in self.map_data:
                 h = [float(v) for v in self.map_data["hsv"].reshape(-1).tolist()]
-                check(lib.sdn_seal_modify_hsv(ptr(rgbs), ptr(m8), rgbs.shape[0], h[0], h[1], h[2], stream()), "seal_modify_hsv")
+                check(lib.sdn_seal_modify_hsv(ptr(rgbs), ptr(m8), M, h[0], h[1], h[2], stream()), "seal_modify_hsv")
             if "rgb" in self.map_data:
                 a = self._native_args(rgbs.device)
                 c = a["rgb"]
-                if whole_rays is not None:
-                    w = whole_rays
-                    check(lib.sdn_seal_modify_rgb_whole_rays(ptr(rgbs), ptr(m8), ptr(w.rays, torch.int32, "rays"), ptr(w.sigmas, torch.float32, "sigmas"),
-                                                             ptr(w.deltas, torch.float32, "deltas"), rgbs.shape[0], w.N, w.T_thresh, w.max_steps,
-                                                             c[0], c[1], c[2], a["rgb_light_offset"], ptr(w.scratch), ptr(w.ray_stop, torch.int32, "ray_stop"),
-                                                             ptr(w.slot_iter, torch.int32, "slot_iter"), ptr(w.n_iter, torch.int32, "n_iter"), stream()),
+                if w is not None:
+                    check(lib.sdn_seal_modify_rgb_whole_rays(ptr(rgbs), ptr(m8), *w_list, c[0], c[1], c[2], a["rgb_light_offset"], ptr(w.scratch), *w_work),
                           "seal_modify_rgb_whole_rays")
                 else:
-                    check(lib.sdn_seal_modify_rgb(ptr(rgbs), ptr(m8), rgbs.shape[0], c[0], c[1], c[2], a["rgb_light_offset"], ptr(a["scratch"]),
+                    check(lib.sdn_seal_modify_rgb(ptr(rgbs), ptr(m8), M, c[0], c[1], c[2], a["rgb_light_offset"], ptr(a["scratch"]),
                                                   None, None, None, stream()), "seal_modify_rgb")
             if stamp:         # after the tint, on the tinted colours; its sum / count in scratch of its own
-                import ctypes
                 a = self._native_args(rgbs.device)
                 rec = ctypes.addressof(a["image"])
-                if whole_rays is not None:
-                    w = whole_rays
-                    check(lib.sdn_seal_modify_image_whole_rays(ptr(rgbs), ptr(points), ptr(m8), ptr(w.rays, torch.int32, "rays"), ptr(w.sigmas, torch.float32, "sigmas"),
-                                                               ptr(w.deltas, torch.float32, "deltas"), rgbs.shape[0], w.N, w.T_thresh, w.max_steps, rec,
-                                                               ptr(w.image_scratch), ptr(w.ray_stop, torch.int32, "ray_stop"),
-                                                               ptr(w.slot_iter, torch.int32, "slot_iter"), ptr(w.n_iter, torch.int32, "n_iter"), stream()),
+                if w is not None:
+                    check(lib.sdn_seal_modify_image_whole_rays(ptr(rgbs), ptr(points), ptr(m8), *w_list, rec, ptr(w.image_scratch), *w_work),
                           "seal_modify_image_whole_rays")
                 else:
-                    check(lib.sdn_seal_modify_image(ptr(rgbs), ptr(points), ptr(m8), rgbs.shape[0], rec, ptr(a["image_scratch"]), None, None, None, stream()),
+                    check(lib.sdn_seal_modify_image(ptr(rgbs), ptr(points), ptr(m8), M, rec, ptr(a["image_scratch"]), None, None, None, stream()),
                           "seal_modify_image")
         elif whole_rays is not None and ("rgb" in self.map_data or stamp):
             raise NotImplementedError("the whole-ray rgb tint / texture stamp is a device kernel (CUDA fp32 contiguous colours and points)")
@@ -367,11 +405,7 @@ class SealBBoxMapper(SealMapper):
             "scale": 1 / scale,
             "center": from_center,
         }
-        if "hsv" in seal_config:
-            self.map_data["hsv"] = seal_config["hsv"]
-        if "rgb" in seal_config:
-            self.map_data["rgb"] = seal_config["rgb"]
-            self.map_data["rgb_light_offset"] = seal_config.get("rgbLightOffset", 0)
+        self._read_color_options()
         if seal_config.get("mapSource"):
             self.map_data["empty_bound"] = _bounds(from_verts)
             self.map_data["map_source"] = seal_config["mapSource"]
@@ -388,37 +422,24 @@ class SealBBoxMapper(SealMapper):
             a["map_source"] = cfl(f32(md["map_source"].reshape(3)))
         return a
 
-    @torch.no_grad()
-    def map_to_origin_(self, points, dirs):
-        """In-place `map_to_origin` on the sample buffers (CUDA fp32 contiguous) -> bool mask [M]; the HIP kernel of csrc/seal.hip."""
-        from sdn_backend import lib, check, ptr, stream
-        a = self._native_args(points.device)
-        M = points.shape[0]
-        mask = torch.empty(M, dtype=torch.uint8, device=points.device)
+    native_kind = "SEAL_BBOX"
+    native_box_fields = (("test_dir", 3), ("tinv", 12), ("rinv", 9), ("scale", 3), ("center", 3))
+
+    def _native_map(self, lib, a, points, dirs, M, mask):
+        from sdn_backend import ptr, stream
         if "map_source" in a:
             # (`mapSource`, seal_utils.py:269-273: the call's unmapped samples inside the source box move to one point -- if the call maps
             #  any sample at all, :251-252; every slot of the buffers is a sample of the call here)
-            check(lib.sdn_seal_bbox_map_source(ptr(points), ptr(dirs), M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"],
-                                               a["tinv"], a["rinv"], a["scale"], a["center"], a["source_bound"], a["map_source"],
-                                               a["scratch"].data_ptr() + 16, ptr(mask), None, None, None, stream()), "seal_bbox_map_source")
-        else:
-            check(lib.sdn_seal_bbox_map(ptr(points), ptr(dirs), M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"], a["tinv"],
-                                        a["rinv"], a["scale"], a["center"], ptr(mask), stream()), "seal_bbox_map")
-        return mask.view(torch.bool)
-
-    @torch.no_grad()
-    def map_to_origin(self, points, dirs=None):
-        """Samples inside the target box are taken back to where their content comes from: inverse transform, inverse scale
-        about the source centre, directions by the inverse rotation.  -> (points', dirs', mask).  CUDA fp32 inputs take the
-        HIP kernel (on copies, as the reference returns copies); everything else the torch restatement below."""
-        if self._native_ok(points, dirs):
-            self.map_data_conversion(points)
-            p, d = points.clone(), dirs.clone()
-            return p, d, self.map_to_origin_(p, d)
-        return self._map_to_origin_torch(points, dirs)
+            return "seal_bbox_map_source", lib.sdn_seal_bbox_map_source(
+                ptr(points), ptr(dirs), M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"], a["tinv"], a["rinv"], a["scale"],
+                a["center"], a["source_bound"], a["map_source"], a["scratch"].data_ptr() + 16, ptr(mask), None, None, None, stream())
+        return "seal_bbox_map", lib.sdn_seal_bbox_map(ptr(points), ptr(dirs), M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"],
+                                                      a["tinv"], a["rinv"], a["scale"], a["center"], ptr(mask), stream())
 
     @torch.no_grad()
     def _map_to_origin_torch(self, points, dirs=None):
+        """Samples inside the target box are taken back to where their content comes from: inverse transform, inverse scale
+        about the source centre, directions by the inverse rotation."""
         with torch.autocast(points.device.type if points.device.type != "cpu" else "cpu", enabled=False):
             self.map_data_conversion(points)
             has_dirs = dirs is not None
@@ -517,39 +538,22 @@ class SealAnchorMapper(SealMapper):
             "scale": seal_config["scale"],
             "map_source": True,         # the reference's flag for pretraining (:512-513), NOT a bbox `mapSource` redirect: nothing here reads it
         }
-        if "hsv" in seal_config:
-            self.map_data["hsv"] = seal_config["hsv"]
-        if "rgb" in seal_config:
-            self.map_data["rgb"] = seal_config["rgb"]
-            self.map_data["rgb_light_offset"] = seal_config.get("rgbLightOffset", 0)
+        self._read_color_options()
         self.map_data_conversion(force=True)
 
     def _native_map_args(self, md, f32, cfl):
         return dict(v_anchor=cfl(f32(md["v_anchor"])), v_offset=cfl(f32(md["v_offset"])), v_h=cfl(f32(md["v_h"])), scale=cfl(f32(md["scale"])),
                     len_h=float(np.float32(md["len_h"])), radius=float(np.float32(md["radius"])))
 
-    @torch.no_grad()
-    def map_to_origin_(self, points, dirs):
-        """In-place `map_to_origin` on the sample buffers (CUDA fp32 contiguous) -> bool mask [M]; `sdn_seal_anchor_map` of csrc/seal.hip.
-        Every slot of the buffers is a sample of the call.  `dirs` are left as they are, as in the reference."""
-        from sdn_backend import lib, check, ptr, stream
-        a = self._native_args(points.device)
-        M = points.shape[0]
-        mask = torch.empty(M, dtype=torch.uint8, device=points.device)
-        check(lib.sdn_seal_anchor_map(ptr(points), ptr(dirs), M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"], a["v_anchor"],
-                                      a["v_offset"], a["v_h"], a["len_h"], a["radius"], a["scale"], a["scratch"].data_ptr() + 16, ptr(mask),
-                                      None, None, None, stream()), "seal_anchor_map")
-        return mask.view(torch.bool)
+    native_kind = "SEAL_ANCHOR"
+    native_box_fields = (("test_dir", 3), ("scale", 3), ("v_anchor", 3), ("v_offset", 3), ("v_h", 3), ("len_h", None), ("radius", None))
 
-    @torch.no_grad()
-    def map_to_origin(self, points, dirs=None):
-        """-> (points', dirs, mask): the points of the affected cone taken back to the undeformed content.  CUDA fp32 inputs take the
-        HIP kernel (on copies, as the reference returns copies); everything else the torch restatement below."""
-        if self._native_ok(points, dirs):
-            self.map_data_conversion(points)
-            p, d = points.clone(), dirs.clone()
-            return p, d, self.map_to_origin_(p, d)
-        return self._map_to_origin_torch(points, dirs)
+    def _native_map(self, lib, a, points, dirs, M, mask):
+        """`sdn_seal_anchor_map`: `dirs` are left as they are, as in the reference."""
+        from sdn_backend import ptr, stream
+        return "seal_anchor_map", lib.sdn_seal_anchor_map(
+            ptr(points), ptr(dirs), M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"], a["v_anchor"], a["v_offset"], a["v_h"],
+            a["len_h"], a["radius"], a["scale"], a["scratch"].data_ptr() + 16, ptr(mask), None, None, None, stream())
 
     @torch.no_grad()
     def _map_to_origin_torch(self, points, dirs=None):
@@ -781,14 +785,10 @@ class SealBrushMapper(SealMapper):
             "attenuation_distance": seal_config["attenuationDistance"],
             "attenuation_mode": mode,
         }
-        if "hsv" in seal_config:
-            self.map_data["hsv"] = seal_config["hsv"]
-        if "rgb" in seal_config:
-            self.map_data["rgb"] = seal_config["rgb"]
-            self.map_data["rgb_light_offset"] = seal_config.get("rgbLightOffset", 0)
+        self._read_color_options()
         if "imageConfig" in seal_config:               # :389-411
             image_conf = seal_config["imageConfig"]
-            self.map_data["rgb_light_offset"] = seal_config.get("rgbLightOffset", 0)
+            self.map_data["rgb_light_offset"] = seal_config.get("rgbLightOffset", 0)      # (the stamp's, also without an `rgb`)
             image, alpha = load_stamp(image_conf["path"], config_path)
             v_o, v_w, v_h = (np.asarray(image_conf[k], dtype=np.float64).reshape(3) for k in ("o", "w", "h"))
             self.map_data["image"] = image
@@ -808,28 +808,26 @@ class SealBrushMapper(SealMapper):
                     attenuation_distance=float(np.float32(md["attenuation_distance"])), mode=_BRUSH_MODES[self.map_data["attenuation_mode"]],
                     border=torch.from_numpy(border).to(device), n_border=int(border.shape[0]))
 
-    @torch.no_grad()
-    def map_to_origin_(self, points, dirs):
-        """In-place `map_to_origin` on the sample buffers (CUDA fp32 contiguous) -> bool mask [M]; `sdn_seal_brush_map` of csrc/seal.hip.
-        `dirs` are neither read nor written."""
-        from sdn_backend import lib, check, ptr, stream
-        a = self._native_args(points.device)
-        M = points.shape[0]
-        mask = torch.empty(M, dtype=torch.uint8, device=points.device)
-        check(lib.sdn_seal_brush_map(ptr(points), None, M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"], a["normal_expand"],
-                                     a["center"], a["attenuation_distance"], a["mode"], ptr(a["border"]), a["n_border"], ptr(mask), stream()),
-              "seal_brush_map")
-        return mask.view(torch.bool)
+    native_kind = "SEAL_BRUSH"
+    native_box_fields = (("test_dir", 3),)
 
-    @torch.no_grad()
-    def map_to_origin(self, points, dirs=None):
-        """-> (points', dirs, mask): the samples inside the strokes' meshes taken back along the normal.  CUDA fp32 inputs take the HIP
-        kernel (on copies, as the reference returns copies); everything else the torch restatement below."""
-        if self._native_ok(points, dirs):
-            self.map_data_conversion(points)
-            p, d = points.clone(), dirs.clone()
-            return p, d, self.map_to_origin_(p, d)
-        return self._map_to_origin_torch(points, dirs)
+    def _native_brush_record(self, a):
+        import ctypes
+        from sdn_backend import SdnSealBrush
+        rec = SdnSealBrush()
+        for k in range(3):
+            rec.normal_expand[k], rec.center[k] = a["normal_expand"][k], a["center"][k]
+        rec.attenuation_distance, rec.mode = a["attenuation_distance"], a["mode"]
+        rec.border, rec.n_border = a["border"].data_ptr(), a["n_border"]
+        rec.image = ctypes.addressof(a["image"]) if "image" in a else None      # the texture stamp (the caller keeps `a` alive)
+        return rec
+
+    def _native_map(self, lib, a, points, dirs, M, mask):
+        """`sdn_seal_brush_map`: `dirs` are neither read nor written."""
+        from sdn_backend import ptr, stream
+        return "seal_brush_map", lib.sdn_seal_brush_map(
+            ptr(points), None, M, a["bounds"], a["n_bounds"], ptr(a["tris"]), a["n_tris"], a["test_dir"], a["normal_expand"], a["center"],
+            a["attenuation_distance"], a["mode"], ptr(a["border"]), a["n_border"], ptr(mask), stream())
 
     @torch.no_grad()
     def _map_to_origin_torch(self, points, dirs=None):
@@ -861,13 +859,10 @@ class SealBrushMapper(SealMapper):
 
 def get_seal_mapper(seal_config, config_path=None):
     """seal_utils.py:581-592 for the mapper types built here."""
-    if seal_config.get("type") == "bbox":
-        return SealBBoxMapper(seal_config, config_path)
-    if seal_config.get("type") == "anchor":
-        return SealAnchorMapper(seal_config, config_path)
-    if seal_config.get("type") == "brush":
-        return SealBrushMapper(seal_config, config_path)
-    raise NotImplementedError(f"seal mapper type {seal_config.get('type')!r}")
+    mapper = {"bbox": SealBBoxMapper, "anchor": SealAnchorMapper, "brush": SealBrushMapper}.get(seal_config.get("type"))
+    if mapper is None:
+        raise NotImplementedError(f"seal mapper type {seal_config.get('type')!r}")
+    return mapper(seal_config, config_path)
 
 
 @torch.no_grad()
