@@ -524,6 +524,13 @@ typedef struct SdnRenderCtx {
      * grid_table the fp32 embeddings in the reference's layout, grid_offsets the reference's offsets */
     int32_t field_f32;
     int32_t reserved2_;
+    /* optional [N] offsets in [0, 1), indexed by RAY: the perturbed first march of the reference's preview (`run_cuda(perturb=True)`:
+     * `march_rays(..., perturb if step == 0 else False)`).  Ray r starts the march of iteration 0 at
+     * nears[r] + clamp(nears[r] * dt_gamma, dt_min, dt_max) * noises[r]; later iterations are not perturbed.  NULL = no perturbation
+     * (bit for bit the loop without this field).  The culled start certifies its jump from the perturbed start.  Not supported with a
+     * frame group or by sdn_render_frames_pipelined_f16 (both return SDN_E_UNSUPPORTED when it is set).  (The brush record stays the
+     * record's last field.) */
+    const float *noises;
     /* the brush mapper's arguments: required when seal->kind == SDN_SEAL_BRUSH, not read otherwise */
     const struct SdnSealBrush *seal_brush;
 } SdnRenderCtx;
@@ -547,7 +554,9 @@ int sdn_render_time_kernel(int which);
  * device: after enqueuing iteration k it blocks on the (side-stream, pinned-memory) read-back of iteration k-1's survivor
  * count, which bounds the grids of iteration k+1 and ends the loop.  ev_main[4] / ev_copy[4]: hipEvent_t created by the
  * caller; host_snap: 8 ints of pinned host memory; ev_field: NULL or 2 * max_field_events timing events recorded around the
- * fused-field launches (iteration k uses 2k, 2k+1); iterations_out: step calls enqueued (incl. the trailing no-op). */
+ * fused-field launches (iteration k uses 2k, 2k+1); iterations_out: step calls enqueued (incl. the trailing no-op).
+ * image_out and depth_out both NULL: the loop alone, without sdn_render_finish -- the caller finishes the frame from the context's
+ * accumulators itself (sdn_preview_finish). */
 int sdn_render_frame_f16(const SdnRenderCtx *ctx, float bg_color, float *image_out, float *depth_out, void *stream,
                          void *side_stream, void **ev_main, void **ev_copy, int32_t *host_snap, void **ev_field,
                          uint32_t max_field_events, uint32_t *iterations_out);
@@ -680,6 +689,20 @@ void *sdn_host_mailbox_alloc(uint32_t groups);
 int sdn_host_mailbox_free(void *mailbox);
 /* image_out [N,3] = image + (1 - weights_sum) * bg; depth_out [N] = clamp(depth - nears, 0) / (fars - nears). */
 int sdn_render_finish(const SdnRenderCtx *ctx, float bg_color, float *image_out, float *depth_out, void *stream);
+/* The finishing pass of a PREVIEW frame (reference: Trainer.test_gui, SealDNeRF/utils.py:174-240, and the GUI's running mean,
+ * SealDNeRF/gui.py:241-267), run after the loop in place of sdn_render_finish: one launch over the H x W output pixels of a frame
+ * rendered with ctx->N = rH * rW rays (row-major, rW fastest).  Output pixel (y, x) takes the ray s = (sy, sx),
+ * sy = min((int)floorf(y * ((float)rH / H)), rH - 1), sx likewise -- torch's `nearest` rule; the identity for rH == H, rW == W.
+ *   rgb   = image[s] + (1 - weights_sum[s]) * bg, bg = bg_rays[s] (device, [rH * rW, 3]: the background-sphere model) when bg_rays is
+ *           given, else bg_color[0..2] (host, copied by value);
+ *   depth = normalize ? clamp(depth[s] - nears[s], 0) / (fars[s] - nears[s]) : depth[s], then nan_to_num (NaN -> 0, +-inf -> +-FLT_MAX);
+ *   to_srgb: rgb = rgb < 0.0031308 ? 12.92 rgb : 1.055 rgb^0.41666 - 0.055 (nerf/utils.py:44-45);
+ *   pos_out (optional, [H, W, 3]) = rays_o[s] + depth * rays_d[s]; only for rH == H and rW == W (SDN_E_BADARG otherwise);
+ *   accum (optional, [H, W, 3], with spp >= 0) = (accum * spp + rgb) / (spp + 1); spp == 0 overwrites without reading accum.
+ * image_out [H, W, 3] and depth_out [H, W] always receive this frame's rgb and depth.  H * W <= 2^30. */
+int sdn_preview_finish(const SdnRenderCtx *ctx, uint32_t rH, uint32_t rW, uint32_t H, uint32_t W, const float *bg_color,
+                       const float *bg_rays, int normalize, int to_srgb, float *image_out, float *depth_out, float *pos_out,
+                       float *accum, int32_t spp, void *stream);
 
 /* ---------------------------------------------------------------------------
  * native training step of the dynamic field  ("next" row of the hot path: the caller that trains what the render path evaluates)

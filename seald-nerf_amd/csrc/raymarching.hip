@@ -1185,6 +1185,7 @@ __global__ void __launch_bounds__(256) k_march_rays(uint32_t n_alive, uint32_t n
         const uint32_t m0 = n_alive * n_step;
         M_pad = m0 + (128u - m0 % 128u);
         if (!(rec->culled_start && rec->iteration == 0)) jump = nullptr;   // the per-ray jump targets of k_cull_start hold for the first march only
+        if (rec->iteration != 0) noises = nullptr;   // the loop's noises (SdnRenderCtx::noises) perturb the march of iteration 0 only
         if (blockIdx.x * 256u >= n_alive + 128u) return;   // workgroup-uniform: beyond the list and its alignment tail (the host sizes the grid by a bound)
     }
     __shared__ uint4 s_cull4[FAST ? 256 : 1];  // 32^3 bits = 4 KiB
@@ -1200,7 +1201,9 @@ __global__ void __launch_bounds__(256) k_march_rays(uint32_t n_alive, uint32_t n
         ray_in_fetch(ray, index, rays_o, rays_d, fars);
         t_ray = rays_t[index];
         if (jump) t_jump = jump[index];
-        if (noises) noise = noises[n];
+        // drop-in ABI: one offset per list position (the reference's noises[n]); the loop's are per RAY -- iteration 0 of a culled start
+        // runs on the compacted list, where position and ray differ (on the reference's arange(N) list they coincide)
+        if (noises) noise = noises[rec ? (uint32_t)index : n];
     }
     frame_rounds<FAST>(fs, index >= 0, index, grid, cull, s_cull4, s_fine, s_min4,
                        [&](const OccCache &oc, const uint8_t *grid_f, uint32_t frame, bool grouped) __attribute__((always_inline)) {
@@ -1502,7 +1505,8 @@ __device__ __forceinline__ float certified_jump(const MarcherT<true> &m, float t
 __device__ __forceinline__ bool cull_start_ray(uint32_t n, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                                const float *__restrict__ nears, const float *__restrict__ fars, const uint32_t *__restrict__ cull,
                                                const FrameSel &fs, int32_t *__restrict__ alive_a, float *__restrict__ rays_tend, float bound,
-                                               float dt_gamma, uint32_t max_steps, uint32_t C, uint32_t H, float *__restrict__ jump) {
+                                               float dt_gamma, uint32_t max_steps, uint32_t C, uint32_t H, float *__restrict__ jump,
+                                               const float *__restrict__ noises) {
     const uint32_t frame = fs.n_frames > 1 ? n / fs.rays_per_frame : 0u;
     const uint32_t *__restrict__ cull_f = fs.n_frames > 1 ? cull + (size_t)frame * fs.cull_stride : cull;
     const int *meta = reinterpret_cast<const int *>(cull_f + kCullWords);
@@ -1514,10 +1518,19 @@ __device__ __forceinline__ bool cull_start_ray(uint32_t n, const float *__restri
     if (go) {
         MarcherT<true> m;
         m.init(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, bound, dt_gamma, max_steps, C, H, nullptr);
-        float t_safe;
-        go = ray_may_hit(cull_f, m.ox, m.oy, m.oz, m.dx, m.dy, m.dz, t, far, t_end, fx0, fy0, fz0, fnx, fny, fnz, &t_safe);
+        // Perturbed first march (SdnRenderCtx::noises): the chain of iteration 0 starts at t0 = near + step_size(near) * noise -- the very
+        // expression k_march_rays evaluates -- so t0 is the origin of the step lattice certified_jump walks and the `start` of a ray it
+        // certifies nothing for.  The cull scan keeps starting at `near`: it then covers [near, far], a superset of the segment
+        // [t0, far] the march can sample, so "no marked cell", t_end and t_safe hold for the march from t0 as they do for the march from
+        // near (conservative: a ray whose only marked cells lie in [near, t0) stays on the list, marches, emits nothing and dies in
+        // iteration 0 like any other ray without a sample).  No sample changes: both tests only ever REMOVE work that emits nothing.
+        const float t0 = noises ? t + m.step_size(t) * noises[n] : t;
+        start = t0;
+        go = t0 < far;        // a ray perturbed to or past `far` emits nothing (march_ray's own first test)
+        float t_safe = -__FLT_MAX__;
+        if (go) go = ray_may_hit(cull_f, m.ox, m.oy, m.oz, m.dx, m.dy, m.dz, t, far, t_end, fx0, fy0, fz0, fnx, fny, fnz, &t_safe);
         rays_tend[n] = go ? t_end : kTendDead;     // what march_ray would cache on the ray's first march
-        if (go && jump && m.dt_is_const) start = certified_jump(m, t, fminf(t_safe, fminf(far, t_end)));
+        if (go && jump && m.dt_is_const) start = certified_jump(m, t0, fminf(t_safe, fminf(far, t_end)));
     }
     alive_a[n] = go ? (int32_t)n : -1;
     if (jump) jump[n] = start;
@@ -1528,10 +1541,11 @@ __global__ void __launch_bounds__(256) k_cull_start(uint32_t N, const float *__r
                                                     const float *__restrict__ nears, const float *__restrict__ fars,
                                                     const uint32_t *__restrict__ cull, FrameSel fs, int32_t *__restrict__ alive_a,
                                                     float *__restrict__ rays_tend, float bound, float dt_gamma, uint32_t max_steps, uint32_t C,
-                                                    uint32_t H, float *__restrict__ jump, uint32_t *__restrict__ block_totals) {
+                                                    uint32_t H, float *__restrict__ jump, uint32_t *__restrict__ block_totals,
+                                                    const float *__restrict__ noises) {
     const uint32_t n = threadIdx.x + blockIdx.x * blockDim.x;
     bool go = false;
-    if (n < N) go = cull_start_ray(n, rays_o, rays_d, nears, fars, cull, fs, alive_a, rays_tend, bound, dt_gamma, max_steps, C, H, jump);
+    if (n < N) go = cull_start_ray(n, rays_o, rays_d, nears, fars, cull, fs, alive_a, rays_tend, bound, dt_gamma, max_steps, C, H, jump, noises);
     // rays of this 256-ray block that go on: the compaction's scatter sums these (no separate count launch)
     __shared__ uint32_t s_cnt[4];
     const uint32_t c = block_count_256(go, s_cnt);
@@ -1730,7 +1744,7 @@ int loop_cull_start(const SdnRenderCtx &c, hipStream_t st) {
     if (!cull || !c.rays_tend || c.H != 128 || !fast_config(c.bound, c.C, c.H)) return 0;
     uint32_t *block_totals = (uint32_t *)c.block_totals;
     hipLaunchKernelGGL(k_cull_start, dim3(sdn_div_up(c.N, 256u)), dim3(256), 0, st, c.N, c.rays_o, c.rays_d, c.nears, c.fars, cull, frame_sel(c), c.alive_a,
-                       c.rays_tend, c.bound, c.dt_gamma, c.max_steps, c.C, c.H, jump_buffer(c), block_totals);
+                       c.rays_tend, c.bound, c.dt_gamma, c.max_steps, c.C, c.H, jump_buffer(c), block_totals, c.noises);
     const uint32_t nb = sdn_div_up(c.N, kScanBlock);
     hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(kScanBlock), 0, st, (const int32_t *)c.alive_a, c.N, (const uint32_t *)block_totals, c.alive_b,
                        snap_n_out(c), (const int32_t *)nullptr, (const int32_t *)nullptr, (int32_t *)nullptr, 4u);
@@ -1746,6 +1760,7 @@ static int march(const SdnRenderCtx &c, uint32_t bound_alive, const float *jump,
     m.bound = c.bound; m.dt_gamma = c.dt_gamma; m.max_steps = c.max_steps; m.C = c.C; m.H = c.H; m.grid = c.bitfield; m.fars = c.fars;
     m.xyzs = c.xyzs; m.dirs = c.dirs; m.deltas = c.deltas; m.cull = loop_cull(c); m.live_idx = c.live_idx; m.live_count = live_counters(c);
     m.state = c.state; m.fs = frame_sel(c); m.jump = jump;
+    m.noises = c.noises;   // per ray, read by the march of iteration 0 only (k_march_rays)
     return launch_k_march_rays(m, st);
 }
 

@@ -108,6 +108,9 @@ static int launch_field(const SdnRenderCtx &c, uint32_t m_bound, uint32_t expect
                                   st);
 }
 
+// the perturbed first march (ctx->noises, one offset per ray) is built for one frame per loop
+static bool noises_unsupported(const SdnRenderCtx *c) { return c->noises && c->n_group_frames > 1; }
+
 static bool ctx_ok(const SdnRenderCtx *c) {
     if (!(c && c->rays_o && c->rays_d && c->nears && c->fars && c->alive_a && c->alive_b && c->rays_t && c->weights_sum &&
           c->depth && c->image && c->state && c->live_counts && c->cull_bits))
@@ -125,6 +128,7 @@ static bool ctx_ok(const SdnRenderCtx *c) {
 
 int sdn_render_begin(const SdnRenderCtx *c, void *stream) {
     if (!ctx_ok(c)) return SDN_E_BADARG;
+    if (noises_unsupported(c)) return SDN_E_UNSUPPORTED;
     return sdn_int::render_begin(c, nullptr, 0, (hipStream_t)stream);
 }
 
@@ -201,6 +205,7 @@ struct FrameRun {
 
     int begin() {
         if (!ctx_ok(c)) return SDN_E_BADARG;
+        if (c->noises && c->n_group_frames > 1) return SDN_E_UNSUPPORTED;
         bound = c->N; it = 0; steady = false; done = false; last_alive = c->N; recompact = false; list_bound = 0;
         mail_dev = nullptr;
         unsigned int flags = 0;
@@ -330,7 +335,8 @@ extern "C" {
 int sdn_render_frame_f16(const SdnRenderCtx *c, float bg_color, float *image_out, float *depth_out, void *stream, void *side_stream,
                          void **ev_main, void **ev_copy, int32_t *host_snap, void **ev_field, uint32_t max_field_events,
                          uint32_t *iterations_out) {
-    if (!c || !image_out || !depth_out || !side_stream || !ev_main || !ev_copy || !host_snap) return SDN_E_BADARG;
+    const bool finish = image_out || depth_out;   // neither: the loop alone, the caller finishes the frame (sdn_preview_finish)
+    if (!c || (finish && !(image_out && depth_out)) || !side_stream || !ev_main || !ev_copy || !host_snap) return SDN_E_BADARG;
     FrameRun r{c, (hipStream_t)stream, (hipStream_t)side_stream, ev_main, ev_copy, ev_field, host_snap, max_field_events, 0, 0, false, false};
     int rc = r.begin();
     while (!rc && !r.done) {
@@ -339,7 +345,7 @@ int sdn_render_frame_f16(const SdnRenderCtx *c, float bg_color, float *image_out
     }
     if (rc) return rc;
     if (iterations_out) *iterations_out = r.it + 1;
-    return sdn_render_finish(c, bg_color, image_out, depth_out, stream);
+    return finish ? sdn_render_finish(c, bg_color, image_out, depth_out, stream) : 0;
 }
 
 // A stream of frames (camera path / time steps) through n_ctx loop contexts used in turn, each on its own stream: the next frame
@@ -362,6 +368,8 @@ int sdn_render_frames_pipelined_f16(const SdnRenderCtx *const *ctxs, uint32_t n_
         return SDN_E_BADARG;
     for (uint32_t s = 0; s < n_ctx; s++)
         if (!ctxs[s] || !ctxs[s]->aabb || !side_streams[s]) return SDN_E_BADARG;
+    for (uint32_t s = 0; s < n_ctx; s++)
+        if (ctxs[s]->noises) return SDN_E_UNSUPPORTED;   // one noise vector per context cannot follow a stream of frames
     if (n_frames == 0) return 0;
     if (overlap_div == 0) overlap_div = 1;
     SdnRenderCtx local[kMaxCtx];

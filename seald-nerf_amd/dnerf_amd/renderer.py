@@ -395,9 +395,21 @@ class FrameWorkspace:
         self.live_counts = torch.zeros(1024 + 8, dtype=i32, device=device)  # one counter per loop iteration (<= max_steps)
 
 
+def first_march_noises(N, device, perturb=False, noises=None):
+    """The per-ray offsets in [0, 1) of a perturbed first march, or None.  `noises`: an [N] fp32 device tensor, used as it is (what
+    a recorded frame is replayed with).  Otherwise `perturb` truthy draws `torch.rand(N)` on the device -- the draw
+    `raymarching.march_rays(perturb=True)` makes for iteration 0 of the reference-shaped loop, first in the generator's order, so
+    that after `torch.manual_seed(s)` the op-by-op path and the native loops jitter every ray alike."""
+    if noises is None:
+        return torch.rand(N, dtype=torch.float32, device=device) if perturb else None
+    if noises.dtype != torch.float32 or noises.numel() != N:
+        raise ValueError(f"noises must be {N} fp32 offsets, one per ray (got {tuple(noises.shape)} {noises.dtype})")
+    return noises.to(device).contiguous().view(-1)
+
+
 @torch.no_grad()
 def render_frame(model, rays_o, rays_d, time, fp16=False, dt_gamma=0.0, max_steps=1024, T_thresh=1e-2, bg_color=1.0,
-                 workspace=None, field=None, count_samples=True, use_cull=True, mapper=None):
+                 workspace=None, field=None, count_samples=True, use_cull=True, mapper=None, perturb=False, noises=None):
     """One inference frame: rays [N,3] -> {'image' [N,3], 'depth' [N], 'weights_sum' [N], 'n_samples', 'trace'}.
 
     Same schedule as dnerf/renderer.py:340-381 (n_step = clamp(N // n_alive, 1, 8), stop at max_steps),
@@ -414,12 +426,16 @@ def render_frame(model, rays_o, rays_d, time, fp16=False, dt_gamma=0.0, max_step
     `mapper`: an optional SealD seal mapper (`dnerf_amd.seal_mapper`), hooked exactly where `SealDNeRF/renderer.py:245-267` hooks
     it -- sample positions / directions are mapped back to their origin before the field is evaluated, colours of the mapped
     samples are re-mapped after it -- so an edited scene renders through the fused field as well.
+
+    `perturb` / `noises`: the reference's preview (`run_cuda(perturb=True)`) -- the march of iteration 0 starts every ray at
+    near + step * noise (see `first_march_noises`); later iterations are not perturbed.
     """
     from sdn_backend import lib, check, ptr, stream
     device = rays_o.device
     rays_o = rays_o.contiguous().view(-1, 3)
     rays_d = rays_d.contiguous().view(-1, 3)
     N = rays_o.shape[0]
+    noises = first_march_noises(N, device, perturb, noises)
     ws = workspace if workspace is not None and workspace.N == N else FrameWorkspace(N, device)
     nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, model.aabb_infer, model.min_near)
     bitfield = model.density_bitfield[model.time_slice(time)]
@@ -450,8 +466,8 @@ def render_frame(model, rays_o, rays_d, time, fp16=False, dt_gamma=0.0, max_step
         live_count = ws.live_counts[it:it + 1] if use_list else None
         check(lib.sdn_march_rays_ex(n_alive, n_step, ptr(alive), ptr(ws.rays_t), ptr(rays_o), ptr(rays_d), float(model.bound),
                                     float(dt_gamma), int(max_steps), int(model.cascade), int(model.grid_size), ptr(bitfield), ptr(fars),
-                                    ptr(xyzs), ptr(dirs), ptr(deltas), None, M, cull, ptr(ws.live_idx) if use_list else None,
-                                    ptr(live_count), st), "march_rays_ex")
+                                    ptr(xyzs), ptr(dirs), ptr(deltas), ptr(noises) if it == 0 else None, M, cull,
+                                    ptr(ws.live_idx) if use_list else None, ptr(live_count), st), "march_rays_ex")   # (iteration 0 walks arange(N): list position == ray)
         if n_samples is not None:  # ops path: live samples = slots with a non-zero step (bookkeeping, off in the timed loop)
             n_samples += (deltas[:M0, 0] > 0).sum()
         q_xyzs, q_dirs, mapped = xyzs, dirs, None
@@ -740,12 +756,20 @@ class DeviceLoop:
         return out
 
     @torch.no_grad()
-    def render(self, rays_o, rays_d, time, bg_color=1.0, want_stats=True):
+    def render(self, rays_o, rays_d, time, bg_color=1.0, want_stats=True, perturb=False, noises=None, finish=True):
+        """`perturb` / `noises` (see `first_march_noises`): the first march of the reference's preview -- every ray starts iteration 0 at
+        near + step * noises[ray]; with the culled start the jump is certified from that start.  `finish=False` runs the loop alone:
+        the caller finishes the frame from the context's accumulators (`sdn_preview_finish`), `image_out` / `depth_out` are not written."""
         import ctypes
         from sdn_backend import lib, check, ptr, stream
         import sdn_backend
+        if (perturb or noises is not None) and self.frames > 1:
+            raise NotImplementedError("a perturbed first march is built for one frame per loop (frames == 1)")
         nears, fars = self.bind(rays_o, rays_d, time)
-        bg_model = getattr(self.model, "bg_radius", -1) > 0
+        noises = first_march_noises(self.N, self.buf["rays_t"].device, perturb, noises)
+        self.ctx.noises = ptr(noises, torch.float32, "noises")
+        self._frame_refs += (noises,)
+        bg_model = getattr(self.model, "bg_radius", -1) > 0 and finish
         if bg_model:         # the background-sphere colours are mixed in after the loop (the native finish takes one scalar colour)
             bg_color = 0.0
         cur = torch.cuda.current_stream()
@@ -754,7 +778,8 @@ class DeviceLoop:
             ev_field, recs = self._timing_queue.pop()
             n_ev = self.MAX_TIMED
         self.side.wait_stream(cur)
-        check(lib.sdn_render_frame_f16(ctypes.byref(self.ctx), float(bg_color), ptr(self.image_out), ptr(self.depth_out), stream(),
+        check(lib.sdn_render_frame_f16(ctypes.byref(self.ctx), float(bg_color), ptr(self.image_out) if finish else None,
+                                       ptr(self.depth_out) if finish else None, stream(),
                                        self.side.cuda_stream, self._ev_main, self._ev_copy, self.host_state.data_ptr(), ev_field, n_ev,
                                        ctypes.byref(self._iters)), "render_frame_f16")
         if recs is not None:  # keep the pairs of the iterations that ran
@@ -842,7 +867,8 @@ class PipelinedDeviceLoop:
               "render_frames_pipelined_f16")
 
     @torch.no_grad()
-    def render_frames(self, rays_o, rays_d, time, bg_color=1.0, outputs=None, timing=None, exclusive=None, on_done=None):
+    def render_frames(self, rays_o, rays_d, time, bg_color=1.0, outputs=None, timing=None, exclusive=None, on_done=None, perturb=False,
+                      noises=None):
         """rays_o / rays_d: lists of [N,3] tensors, one per frame (entries may repeat).  time: ONE time stamp for the whole stream
         (number or the reference's [1,1] tensor), or a list with one entry per frame -- a D-NeRF test set carries its own time for
         every frame (dnerf/utils.py:151-161); with frame-group contexts (`frames=F`) an entry is itself a list of F times.
@@ -858,6 +884,8 @@ class PipelinedDeviceLoop:
         import time as _t
         _tin = _t.perf_counter()
         from sdn_backend import lib, check, ptr
+        if perturb or noises is not None:
+            raise NotImplementedError("a perturbed first march is not built for pipelined frames: render preview frames with DeviceLoop")
         n = len(rays_o)
         assert n == len(rays_d) and n >= 1
         cur = torch.cuda.current_stream()
@@ -1038,8 +1066,10 @@ class RayBatchRenderer:
                                          slot_iter=torch.full((self.M,), -1, dtype=i32, device=dev), n_iter=torch.zeros(1, dtype=i32, device=dev))
 
     @torch.no_grad()
-    def render(self, rays_o, rays_d, time, bg_color=1.0, check=False):
+    def render(self, rays_o, rays_d, time, bg_color=1.0, check=False, perturb=False, noises=None):
         import sdn_backend as B
+        if perturb or noises is not None:
+            raise NotImplementedError("the one-pass renderer's marcher is unperturbed by design: render preview frames with DeviceLoop")
         m, lib, st = self.model, B.lib, B.stream()
         ro, rd = rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3)
         if ro.shape[0] != self.N:

@@ -47,6 +47,7 @@ PROTOTYPES = {
     "sdn_render_step_f16": [_vp, _u32, _vp],
     "sdn_render_step_f16_ev": [_vp, _u32, _vp, _vp, _vp],
     "sdn_render_finish": [_vp, _f32, _vp, _vp, _vp],
+    "sdn_preview_finish": [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
     "sdn_render_time_kernel": [_i32],
     "sdn_render_frame_f16": [_vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "sdn_render_frames_pipelined_f16": [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp],
@@ -99,7 +100,7 @@ class SdnRenderCtx(ctypes.Structure):
                 + [(n, _f32) for n in ("bound", "dt_gamma", "T_thresh", "density_scale")]
                 + [("zero_deform", ctypes.c_int32), ("aabb", _vp), ("min_near", _f32), ("reserved_", ctypes.c_int32), ("rays_tend", _vp), ("seal", _vp), ("seal_mask", _vp),
                    ("n_group_frames", _u32), ("rays_per_frame", _u32), ("frame_bitfield", _vp * MAX_GROUP_FRAMES), ("slot_frame", _vp),
-                   ("frame_cull", _vp * MAX_GROUP_FRAMES), ("field_f32", _i32), ("reserved2_", _i32), ("seal_brush", _vp)])
+                   ("frame_cull", _vp * MAX_GROUP_FRAMES), ("field_f32", _i32), ("reserved2_", _i32), ("noises", _vp), ("seal_brush", _vp)])
 
 
 # Word indices of `SdnLoopRecord` (include/sdn_hip.h: the 16 ints of `SdnRenderCtx.state`, one name per word, same order)
