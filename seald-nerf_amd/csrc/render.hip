@@ -108,6 +108,27 @@ static int launch_field(const SdnRenderCtx &c, uint32_t m_bound, uint32_t expect
                                   st);
 }
 
+// n_alive * n_step <= N always (n_step <= N / n_alive), and <= 8 * bound_alive: the slots an iteration's marcher can have written
+static uint32_t slot_bound(const SdnRenderCtx &c, uint32_t bound_alive) {
+    const uint64_t m = (uint64_t)bound_alive * 8u;
+    return m > c.N ? c.N : (uint32_t)m;
+}
+// An iteration's one event pair goes to its field launch or to its marcher launch (sdn_render_time_kernel); the other side gets none
+struct IterEvents { void *field0, *field1, *march0, *march1; };
+static IterEvents split_events(void *e0, void *e1) {
+    return g_timed_kernel.load() == 1 ? IterEvents{nullptr, nullptr, e0, e1} : IterEvents{e0, e1, nullptr, nullptr};
+}
+static void record(void *ev, hipStream_t st) { if (ev) (void)hipEventRecord((hipEvent_t)ev, st); }
+// what every iteration does between its march and its compositing: map the samples, the field between its events, recolour
+static int map_field_color(const SdnRenderCtx &c, uint32_t m_slots, uint32_t expect_points, const IterEvents &ev, hipStream_t st) {
+    int rc = seal_map(c, m_slots, st);
+    if (rc) return rc;
+    record(ev.field0, st);
+    rc = launch_field(c, m_slots, expect_points, st);
+    record(ev.field1, st);
+    return rc ? rc : seal_color(c, m_slots, st);
+}
+
 // the perturbed first march (ctx->noises, one offset per ray) is built for one frame per loop
 static bool noises_unsupported(const SdnRenderCtx *c) { return c->noises && c->n_group_frames > 1; }
 
@@ -140,24 +161,12 @@ int sdn_render_step_f16_ev(const SdnRenderCtx *c, uint32_t bound_alive, void *ev
     if (!c || bound_alive == 0) return SDN_E_BADARG;
     if (bound_alive > c->N) bound_alive = c->N;
     hipStream_t st = (hipStream_t)stream;
-    const bool time_march = g_timed_kernel.load() == 1;
-    if (time_march && ev_field_begin) (void)hipEventRecord((hipEvent_t)ev_field_begin, st);
+    const IterEvents ev = split_events(ev_field_begin, ev_field_end);
+    record(ev.march0, st);
     int rc = sdn_int::loop_march(*c, bound_alive, st);
-    if (time_march && ev_field_end) (void)hipEventRecord((hipEvent_t)ev_field_end, st);
-    if (time_march) ev_field_begin = ev_field_end = nullptr;
-    if (rc) return rc;
-    // n_alive * n_step <= N always (n_step <= N / n_alive), and <= 8 * bound_alive
-    uint64_t m_bound = (uint64_t)bound_alive * 8u;
-    if (m_bound > c->N) m_bound = c->N;
-    rc = seal_map(*c, (uint32_t)m_bound, st);
-    if (rc) return rc;
-    if (ev_field_begin) (void)hipEventRecord((hipEvent_t)ev_field_begin, st);
-    rc = launch_field(*c, (uint32_t)m_bound, 0u, st);
-    if (ev_field_end) (void)hipEventRecord((hipEvent_t)ev_field_end, st);
-    if (rc) return rc;
-    rc = seal_color(*c, (uint32_t)m_bound, st);
-    if (rc) return rc;
-    return sdn_int::loop_composite_compact(*c, bound_alive, st);
+    record(ev.march1, st);
+    if (!rc) rc = map_field_color(*c, slot_bound(*c, bound_alive), 0u, ev, st);
+    return rc ? rc : sdn_int::loop_composite_compact(*c, bound_alive, st);
 }
 
 // Whole-frame driver: begin + iterations + finish in one call, so the per-iteration host work is a handful of HIP API
@@ -205,7 +214,7 @@ struct FrameRun {
 
     int begin() {
         if (!ctx_ok(c)) return SDN_E_BADARG;
-        if (c->noises && c->n_group_frames > 1) return SDN_E_UNSUPPORTED;
+        if (noises_unsupported(c)) return SDN_E_UNSUPPORTED;
         bound = c->N; it = 0; steady = false; done = false; last_alive = c->N; recompact = false; list_bound = 0;
         mail_dev = nullptr;
         unsigned int flags = 0;
@@ -229,18 +238,9 @@ struct FrameRun {
         if (!steady) {
             rc = sdn_render_step_f16_ev(c, bound, e0, e1, st);
         } else {
-            uint64_t m_bound = (uint64_t)bound * 8u;
-            if (m_bound > c->N) m_bound = c->N;
-            rc = seal_map(*c, (uint32_t)m_bound, st);
-            if (rc) return rc;
-            const bool time_march = g_timed_kernel.load() == 1;
-            void *m0 = time_march ? e0 : nullptr, *m1 = time_march ? e1 : nullptr;
-            if (time_march) e0 = e1 = nullptr;
-            if (e0) (void)hipEventRecord((hipEvent_t)e0, st);
-            rc = launch_field(*c, (uint32_t)m_bound, last_alive * 8u, st);
-            if (e1) (void)hipEventRecord((hipEvent_t)e1, st);
-            if (!rc) rc = seal_color(*c, (uint32_t)m_bound, st);
-            if (!rc && m0) (void)hipEventRecord((hipEvent_t)m0, st);
+            const IterEvents ev = split_events(e0, e1);
+            rc = map_field_color(*c, slot_bound(*c, bound), last_alive * 8u, ev, st);
+            if (!rc) record(ev.march0, st);
             if (!rc && recompact) {
                 // composite this iteration on the frozen list, compact it, freeze the shorter list and march the next iteration on it
                 rc = sdn_int::loop_composite_compact(*c, bound, st, true);
@@ -250,7 +250,7 @@ struct FrameRun {
                 recompact = false;
             } else if (!rc)
                 rc = sdn_int::loop_composite_march(*c, bound, st);
-            if (!rc && m1) (void)hipEventRecord((hipEvent_t)m1, st);
+            if (!rc) record(ev.march1, st);
         }
         if (rc) return rc;
         if (mail_dev) return 0;

@@ -242,6 +242,34 @@ class SealMapper:
         """The mapper's `SdnSealBrush` record from `_native_args`: the brush's; None for every other mapper."""
         return None
 
+    def _native_box_record(self, a):
+        """The mapper's `SdnSealBox` record from `_native_args`: the box test's bounds and triangles, the mapper's own
+        `native_box_fields`, the hsv / rgb colour edit and the bbox mapper's mapSource.  `scratch` stays empty: the loop that takes the
+        record owns those bytes (and keeps `a`, which the record points into, alive)."""
+        import sdn_backend
+        box = sdn_backend.SdnSealBox()
+        for k in range(6 * a["n_bounds"]):
+            box.bounds[k] = a["bounds"][k]
+        box.n_bounds, box.n_tris, box.tris = a["n_bounds"], a["n_tris"], a["tris"].data_ptr()
+        box.kind = getattr(sdn_backend, self.native_kind)
+        for name, n in self.native_box_fields:
+            if n is None:
+                setattr(box, name, a[name])
+            for k in range(n or 0):
+                getattr(box, name)[k] = a[name][k]
+        if "hsv" in self.map_data:
+            h = [float(v) for v in self.map_data["hsv"].reshape(-1).tolist()]
+            box.hsv[0], box.hsv[1], box.hsv[2], box.modify_hsv = h[0], h[1], h[2], 1
+        if "rgb" in a:
+            box.rgb[0], box.rgb[1], box.rgb[2], box.rgb_light_offset, box.modify_rgb = a["rgb"][0], a["rgb"][1], a["rgb"][2], a["rgb_light_offset"], 1
+        if self.redirects_source:
+            for k in range(6):
+                box.source_bound[k] = a["source_bound"][k]
+            for k in range(3):
+                box.map_source[k] = a["map_source"][k]
+            box.has_map_source = 1
+        return box
+
     def _native_ok(self, points, dirs):
         return (points.is_cuda and dirs is not None and points.dtype == torch.float32 and dirs.dtype == torch.float32
                 and points.is_contiguous() and dirs.is_contiguous())

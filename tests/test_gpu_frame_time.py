@@ -148,6 +148,43 @@ def test_on_done_hands_finished_frames_on_in_order(model_bits):
     assert not torch.equal(copies[0], copies[2])
 
 
+def test_timed_frames_are_the_untimed_frame_and_every_kept_event_pair_was_recorded(model_bits):
+    """The drivers' timed-event path (`sdn_backend.timers` + `prepare_timing`, otherwise bench.py's alone): a frame rendered with one
+    event pair per iteration around the field launch (`sdn_render_time_kernel(0)`) or around the marcher launch (1) is the untimed
+    frame bit for bit -- image, depth, trace --, min(MAX_TIMED, iterations) pairs are kept, and each has an elapsed time (an event
+    the driver never recorded raises there).  The 64 x 64 fixture frame enters iteration 1 with 230 alive rays (CPU oracle), so all but
+    its first iteration run in steady mode (n_alive * 8 <= N), which the trace must show: both branches of the driver's iteration
+    are timed.  A recompacting iteration needs >= 8192 alive rays in a frozen list: that stays with the full-size tests."""
+    import sdn_backend
+    from dnerf_amd.fused import FusedField
+    from dnerf_amd.renderer import DeviceLoop
+    model, _ = model_bits
+    sc = fixture_scene("cuda", model_bits=model_bits)
+    N = sc.rays_o.shape[0]
+    assert N == 64 * 64
+    loop = DeviceLoop(model, FusedField(model, sc.time), N, "cuda")
+    plain = loop.render(sc.rays_o, sc.rays_d, sc.time)
+    image, depth, trace = plain["image"].clone(), plain["depth"].clone(), plain["trace"]
+    assert not trace[0][0] * 8 <= N and any(n_alive * 8 <= N for n_alive, _, _ in trace[1:])      # normal AND steady iterations
+    assert sdn_backend.timers is None
+    try:
+        for which in (0, 1):
+            sdn_backend.timers = sdn_backend.KernelTimers()
+            sdn_backend.check(sdn_backend.lib.sdn_render_time_kernel(which), "render_time_kernel")
+            loop.prepare_timing(1)
+            out = loop.render(sc.rays_o, sc.rays_d, sc.time)
+            torch.cuda.synchronize()
+            assert torch.equal(out["image"], image) and _eq(out["depth"], depth) and out["trace"] == trace, which
+            pairs = sdn_backend.timers.records["field_forward_f16"]
+            iterations = int(loop._iters.value)                    # step calls enqueued, the trailing no-op one included
+            assert iterations >= len(trace) and len(pairs) == min(loop.MAX_TIMED, iterations), (which, len(pairs), iterations)
+            ms = [s.elapsed_time(e) for s, e, _ in pairs]
+            assert all(np.isfinite(v) and v >= 0 for v in ms), (which, ms)
+    finally:
+        sdn_backend.timers = None
+        sdn_backend.lib.sdn_render_time_kernel(0)
+
+
 def test_kept_cull_grids_change_nothing_and_follow_the_bitfield(model_bits):
     """`keep_cull_grids=True`: each occupancy slice's cull grid is derived once and copied into the context afterwards (single
     frames, a stream, a frame group): frames bit-identical to the loops that derive it every time; after the occupancy grid was

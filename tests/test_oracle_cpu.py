@@ -275,6 +275,66 @@ def test_ctypes_records_match_the_c_header(tmp_path):
     assert seen == sum(len(r._fields_) + 1 for r in records.values())
 
 
+def _c_type_class(decl):
+    """Class of one C parameter / return type as ctypes sees it: 'ptr', 'u32', 'i32', 'u64', 'f32', 'f64', 'void'."""
+    decl = re.sub(r"\bconst\b", " ", decl).strip()
+    if "*" in decl or re.search(r"\[[^\]]*\]\s*$", decl):          # `T name[k]` decays to a pointer
+        return "ptr"
+    base = re.match(r"(unsigned int|unsigned|uint32_t|int32_t|uint64_t|int|float|double|void)\b", decl)
+    assert base, decl
+    return {"unsigned int": "u32", "unsigned": "u32", "uint32_t": "u32", "int": "i32", "int32_t": "i32", "uint64_t": "u64", "float": "f32",
+            "double": "f64", "void": "void"}[base.group(1)]
+
+
+def _ctypes_class(t):
+    import ctypes
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, (ctypes._Pointer, ctypes.Array)):
+        return "ptr"
+    return {ctypes.c_uint32: "u32", ctypes.c_int32: "i32", ctypes.c_uint64: "u64", ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
+
+
+def test_ctypes_prototypes_match_the_c_header():
+    """The argument lists sdn_backend sets on `lib` against the declarations of include/sdn_hip.h: per function the argument count, per
+    argument the class (pointer, uint32_t, int / int32_t, uint64_t, float, double), and the class of the return type.  A drifted list
+    hands a kernel a misplaced pointer.  Covers PROTOTYPES, PROTOTYPES_U32, PROTOTYPES_U64 and the four functions set by hand."""
+    import sdn_backend as B
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "sdn_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    header = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", "", header, flags=re.M)
+    decls = re.findall(r"([A-Za-z_][\w \t\*]*?)\b(sdn_\w+)\s*\(([^()]*)\)\s*;", header)
+    by_hand = {"sdn_version", "sdn_host_mailbox_alloc", "sdn_field_select_kernel", "sdn_field_persistent_workgroups"}
+    tabled = set(B.PROTOTYPES) | set(B.PROTOTYPES_U32) | set(B.PROTOTYPES_U64)
+    assert {name for _, name, _ in decls} == tabled | by_hand
+    assert len(decls) == len(tabled | by_hand)        # one declaration each
+    bad = []
+    for ret, name, params in decls:
+        params = [p for p in (q.strip() for q in params.split(",")) if p and p != "void"]
+        want = [_c_type_class(p) for p in params]
+        fn = getattr(B.lib, name)
+        if name == "sdn_version":                      # takes nothing, and sdn_backend sets no argtypes on it
+            assert fn.argtypes is None and not want
+            got = []
+        else:
+            got = [_ctypes_class(t) for t in fn.argtypes]
+        if got != want:
+            bad.append((name, "arguments", got, want))
+        if _ctypes_class(fn.restype) != _c_type_class(ret):
+            bad.append((name, "return type", _ctypes_class(fn.restype), _c_type_class(ret)))
+    assert not bad, bad
+
+
+def test_frame_drivers_are_reexported_by_renderer():
+    """`dnerf_amd.renderer` keeps every name the frame drivers had there: the very objects of `dnerf_amd.frame_loops`."""
+    from dnerf_amd import frame_loops, renderer
+    for name in ("FrameWorkspace", "first_march_noises", "render_frame", "_field_eval", "DeviceLoop", "_context_streams",
+                 "PipelinedDeviceLoop", "loop_schedule", "RayBatchRenderer"):
+        assert getattr(renderer, name) is getattr(frame_loops, name), name
+    assert renderer.NeRFRenderer.__module__ == renderer.sample_pdf.__module__ == "dnerf_amd.renderer"
+
+
 def test_ops_fail_loudly_without_a_device():
     import torch
     if torch.cuda.is_available():
