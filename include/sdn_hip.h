@@ -527,9 +527,13 @@ typedef struct SdnRenderCtx {
     /* optional [N] offsets in [0, 1), indexed by RAY: the perturbed first march of the reference's preview (`run_cuda(perturb=True)`:
      * `march_rays(..., perturb if step == 0 else False)`).  Ray r starts the march of iteration 0 at
      * nears[r] + clamp(nears[r] * dt_gamma, dt_min, dt_max) * noises[r]; later iterations are not perturbed.  NULL = no perturbation
-     * (bit for bit the loop without this field).  The culled start certifies its jump from the perturbed start.  Not supported with a
-     * frame group or by sdn_render_frames_pipelined_f16 (both return SDN_E_UNSUPPORTED when it is set).  (The brush record stays the
-     * record's last field.) */
+     * (bit for bit the loop without this field).  The culled start certifies its jump from the perturbed start.  In a frame group
+     * (n_group_frames > 1) the vector has n_group_frames * rays_per_frame entries indexed by the group's ray id, frame-major like every
+     * other per-ray array; iteration 0 takes one step per ray whatever the culled count is, so every frame of the group is bit for bit
+     * the frame rendered alone with its block of offsets (the jittered samples of one view: sdn_preview_finish_group folds them).  The
+     * whole-frame driver sdn_render_frame_f16 runs such a group; the step-wise entry sdn_render_begin still returns SDN_E_UNSUPPORTED
+     * for it, and so does sdn_render_frames_pipelined_f16 for any context with noises (one vector per context cannot follow a stream
+     * of frames).  (The brush record stays the record's last field.) */
     const float *noises;
     /* the brush mapper's arguments: required when seal->kind == SDN_SEAL_BRUSH, not read otherwise */
     const struct SdnSealBrush *seal_brush;
@@ -703,6 +707,15 @@ int sdn_render_finish(const SdnRenderCtx *ctx, float bg_color, float *image_out,
 int sdn_preview_finish(const SdnRenderCtx *ctx, uint32_t rH, uint32_t rW, uint32_t H, uint32_t W, const float *bg_color,
                        const float *bg_rays, int normalize, int to_srgb, float *image_out, float *depth_out, float *pos_out,
                        float *accum, int32_t spp, void *stream);
+/* The same pass over the first n_fold frames of a FRAME GROUP context (n_group_frames > 1, rays_per_frame = rH * rW: the jittered samples
+ * of one view rendered by one loop), in ONE launch: for f = 0 .. n_fold - 1, in order, exactly what sdn_preview_finish applies to frame
+ * f's block of the per-ray arrays, folded as accum = (accum * (spp + f) + rgb_f) / (spp + f + 1) with the roundings of n_fold successive
+ * calls (spp + f == 0 overwrites without reading accum).  bg_rays, when given, is [n_group_frames * rH * rW, 3], frame-major like the
+ * context's arrays.  image_out, depth_out and pos_out receive the values of frame n_fold - 1, as after the successive calls.
+ * 1 <= n_fold <= n_group_frames (the last group of an accumulation may fold fewer frames than it rendered); accum is required. */
+int sdn_preview_finish_group(const SdnRenderCtx *ctx, uint32_t rH, uint32_t rW, uint32_t H, uint32_t W, const float *bg_color,
+                             const float *bg_rays, int normalize, int to_srgb, float *image_out, float *depth_out, float *pos_out,
+                             float *accum, int32_t spp, uint32_t n_fold, void *stream);
 
 /* ---------------------------------------------------------------------------
  * native training step of the dynamic field  ("next" row of the hot path: the caller that trains what the render path evaluates)

@@ -129,8 +129,10 @@ static int map_field_color(const SdnRenderCtx &c, uint32_t m_slots, uint32_t exp
     return rc ? rc : seal_color(c, m_slots, st);
 }
 
-// the perturbed first march (ctx->noises, one offset per ray) is built for one frame per loop
-static bool noises_unsupported(const SdnRenderCtx *c) { return c->noises && c->n_group_frames > 1; }
+// The perturbed first march (ctx->noises, one offset per ray) in a frame group: the whole-frame driver (sdn_render_frame_f16) runs it --
+// noises are indexed by the group's ray id like every per-ray array, and iteration 0 takes n_step = 1 whatever the culled count is
+// (k_loop_init sets it, k_cull_advance leaves it), as the reference's N // N.  The step-wise entry keeps refusing the combination.
+static bool stepwise_noises_unsupported(const SdnRenderCtx *c) { return c->noises && c->n_group_frames > 1; }
 
 static bool ctx_ok(const SdnRenderCtx *c) {
     if (!(c && c->rays_o && c->rays_d && c->nears && c->fars && c->alive_a && c->alive_b && c->rays_t && c->weights_sum &&
@@ -149,7 +151,7 @@ static bool ctx_ok(const SdnRenderCtx *c) {
 
 int sdn_render_begin(const SdnRenderCtx *c, void *stream) {
     if (!ctx_ok(c)) return SDN_E_BADARG;
-    if (noises_unsupported(c)) return SDN_E_UNSUPPORTED;
+    if (stepwise_noises_unsupported(c)) return SDN_E_UNSUPPORTED;
     return sdn_int::render_begin(c, nullptr, 0, (hipStream_t)stream);
 }
 
@@ -214,7 +216,6 @@ struct FrameRun {
 
     int begin() {
         if (!ctx_ok(c)) return SDN_E_BADARG;
-        if (noises_unsupported(c)) return SDN_E_UNSUPPORTED;
         bound = c->N; it = 0; steady = false; done = false; last_alive = c->N; recompact = false; list_bound = 0;
         mail_dev = nullptr;
         unsigned int flags = 0;

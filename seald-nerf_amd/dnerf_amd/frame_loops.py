@@ -277,6 +277,7 @@ class DeviceLoop:
         self.side = torch.cuda.Stream(device=device)
         self._handles = None
         self._timing_queue = []
+        self._sample_rays = None              # render_samples: the one view's rays, replicated per sample
         c = sdn_backend.SdnRenderCtx()
         for k, v in self.buf.items():
             setattr(c, k, v.data_ptr())
@@ -422,6 +423,40 @@ class DeviceLoop:
             raise NotImplementedError("a perturbed first march is built for one frame per loop (frames == 1)")
         nears, fars = self.bind(rays_o, rays_d, time)
         noises = first_march_noises(self.N, self.buf["rays_t"].device, perturb, noises)
+        return self._run(nears, fars, noises, bg_color, want_stats, finish)
+
+    @torch.no_grad()
+    def render_samples(self, rays_o, rays_d, time, noises, bg_color=1.0, want_stats=True, finish=False):
+        """F jittered samples of ONE frame in one loop, on a loop built with `frames = F` (N = F * n): what a resting preview
+        accumulates.  rays_o / rays_d: the view's [n, 3] rays; time: its one time stamp; noises: [F, n] fp32 offsets in [0, 1), row f
+        the first-march jitter of sample f (see `first_march_noises`).  The rays are replicated into buffers the loop owns, the time
+        stamp is bound to all F frames and the loop runs once: the samples share the chain of dependent launches, and block f of
+        every per-ray result (`buf['image']`, `buf['depth']`, `buf['weights_sum']`, frame-major) is bit for bit what
+        `DeviceLoop(frames=1).render(noises=noises[f])` leaves.  `finish=False` (the default here) leaves the frames to the caller --
+        `sdn_preview_finish_group` folds them into a running mean --, True writes `image_out` / `depth_out` for all F * n rays.
+        Trace and sample count are the group's, not a frame's (see `__init__`)."""
+        F = self.frames
+        if F < 2:
+            raise ValueError("render_samples needs a loop built with frames = F >= 2 (one frame per loop: render(noises=...))")
+        if isinstance(time, (list, tuple)):
+            raise ValueError("render_samples renders one frame: one time stamp")
+        n = self.N // F
+        rays_o, rays_d = flat_rays(rays_o), flat_rays(rays_d)
+        if rays_o.shape[0] != n or rays_d.shape[0] != n:
+            raise ValueError(f"this loop holds {F} samples of {n} rays, got {rays_o.shape[0]} rays")
+        if not torch.is_tensor(noises) or noises.dtype != torch.float32 or tuple(noises.shape) != (F, n):
+            got = (tuple(noises.shape), noises.dtype) if torch.is_tensor(noises) else type(noises).__name__
+            raise ValueError(f"noises must be [{F}, {n}] fp32 offsets, one row per sample (got {got})")
+        device = self.buf["rays_t"].device
+        if self._sample_rays is None:
+            self._sample_rays = (torch.empty(F, n, 3, dtype=torch.float32, device=device), torch.empty(F, n, 3, dtype=torch.float32, device=device))
+        self._sample_rays[0].copy_(rays_o.unsqueeze(0).expand(F, n, 3))
+        self._sample_rays[1].copy_(rays_d.unsqueeze(0).expand(F, n, 3))
+        nears, fars = self.bind(self._sample_rays[0], self._sample_rays[1], time)
+        return self._run(nears, fars, first_march_noises(self.N, device, noises=noises), bg_color, want_stats, finish)
+
+    def _run(self, nears, fars, noises, bg_color, want_stats, finish):
+        """The bound frame (group) through the native whole-frame driver, with `noises` (one per ray of the loop, or None)."""
         self.ctx.noises = ptr(noises, torch.float32, "noises")
         self._frame_refs += (noises,)
         bg_model = getattr(self.model, "bg_radius", -1) > 0 and finish

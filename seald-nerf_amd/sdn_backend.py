@@ -48,6 +48,7 @@ PROTOTYPES = {
     "sdn_render_step_f16_ev": [_vp, _u32, _vp, _vp, _vp],
     "sdn_render_finish": [_vp, _f32, _vp, _vp, _vp],
     "sdn_preview_finish": [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
+    "sdn_preview_finish_group": [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _u32, _vp],
     "sdn_render_time_kernel": [_i32],
     "sdn_render_frame_f16": [_vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "sdn_render_frames_pipelined_f16": [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp],
