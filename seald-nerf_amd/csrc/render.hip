@@ -30,7 +30,7 @@ int render_begin(const SdnRenderCtx *c, void *mailbox, uint32_t frame_tag, hipSt
         for (uint32_t f = 0; f < nf; f++) kept = kept && c->frame_cull[f] != nullptr;
         if (kept) rc = copy_cull(c->frame_cull, nf, (uint32_t *)c->cull_bits, st);
         else rc = c->n_group_frames > 1 ? build_cull_group(frame_sel(*c), (uint32_t *)c->cull_bits, st) : build_cull(c->bitfield, (uint32_t *)c->cull_bits, st);
-        // iteration 0 on the rays that pass the exact cull test (same samples, same trace; raymarching.hip k_cull_start)
+        // iteration 0 on the rays that pass the exact cull test (same samples, same trace; render_loop.hip k_cull_start)
         if (!rc && c->rays_tend) rc = loop_cull_start(*c, st);
     }
     return rc;

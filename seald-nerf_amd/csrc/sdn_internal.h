@@ -28,7 +28,7 @@ inline float *jump_buffer(const SdnRenderCtx &c) { return c.rays_tend ? c.sigmas
 inline bool has_loop_cull(const SdnRenderCtx &c) { return c.H == 128 && c.C == 1; }
 inline const uint32_t *loop_cull(const SdnRenderCtx &c) { return has_loop_cull(c) ? (const uint32_t *)c.cull_bits : nullptr; }
 
-// The steps of the device-driven loop (raymarching.hip) on the buffers of one context; render.hip decides their order.
+// The steps of the device-driven loop (render_loop.hip) on the buffers of one context; render.hip decides their order.
 int loop_begin(const SdnRenderCtx &c, void *mailbox, uint32_t frame_tag, hipStream_t st);
 int loop_cull_start(const SdnRenderCtx &c, hipStream_t st);
 int loop_march(const SdnRenderCtx &c, uint32_t bound_alive, hipStream_t st);

@@ -453,7 +453,7 @@ __global__ void __launch_bounds__(256) k_whole_rays_stop(const float *__restrict
 
 // Phase B, one workgroup: the loop of dnerf/renderer.py:340-381 on the rays' progress alone.  Per iteration: count the alive rays
 // (wave shuffles + LDS, two LDS rows used in turn so that one barrier per iteration is enough), n_step exactly as advance_record
-// (raymarching.hip) and the reference set it, every alive ray stamps the slots the marcher would have filled -- [pos, pos + n_step),
+// (render_loop.hip) and the reference set it, every alive ray stamps the slots the marcher would have filled -- [pos, pos + n_step),
 // cut at its sample count, INCLUDING those behind a kill inside the window: the loop marched, evaluated and averaged them -- and dies
 // when k_composite_rays would have killed it: its stop sample lies in the window (for a ray without one, stop == count: fewer than
 // n_step samples were left).  Ends as the loop does: step >= max_steps, or nobody alive.
