@@ -253,6 +253,19 @@ int sdn_field_forward_f32x3(const float *xyzs, const float *dirs, const uint32_t
                             const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale,
                             int zero_deform, float *sigmas, float *rgbs, float *deform, void *stream);
 
+/* The fused field of the temporal-basis model (reference: dnerf/network_basis.py:123-161 under `-O`; csrc/field_basis.hip): tiled grid
+ * 16x2 (fp16 table) -> 64,64 sigma MLP = 32 density coefficients ++ 32 geo_feat; SH(4) ++ geo_feat -> 64,64,24 colour MLP = 3 x 8
+ * colour coefficients; sigma = density_scale * exp(coefficients . sigma_basis), rgb = sigmoid(coefficients . color_basis), every
+ * product with autocast's fp16 roundings.  weights: sdn_field_basis_weight_blocks() KiB in the fragment order of
+ * dnerf_amd/fused_basis.py.  basis_row [128] f32: the time stamp's basis (the model's basis_net under autocast: fp16 values) --
+ * sigma_basis in entries 0..31, color_basis in 32..39, the rest zero.  table / offsets_host: the PADDED or the QUAD layout of
+ * sdn_field_forward_f16 (the reference's layout: SDN_E_UNSUPPORTED).  Everything else as sdn_field_forward_f16. */
+uint32_t sdn_field_basis_weight_blocks(void);
+int sdn_field_basis_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count,
+                                uint32_t M, const void *weights, const float *basis_row /* [128] */, const void *table,
+                                const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale,
+                                float *sigmas, float *rgbs, void *stream);
+
 /* Which kernel large launches of the fused field network take: 1 = the persistent two-set ("ping-pong") kernel, the default for launches
  * of at least 4 tiles of 256 points per CU on a QUAD table; 0 = one tile per workgroup for every launch; -1 = environment SDN_FIELD_PP or
  * the default.  Both produce the same bits: a switch for tests and A/B measurements, not a tuning knob. */
@@ -521,7 +534,9 @@ typedef struct SdnRenderCtx {
     /* 0: the fp16 fused field (`-O`: field_weights / grid_table / grid_offsets are sdn_field_forward_f16's); 1 / 2: the fp32 fused field
      * on fp32 MFMAs (sdn_field_forward_f32) / on split fp16 operands (sdn_field_forward_f32x3)
      * (the reference without `-O`): field_weights = sdn_field_forward_f32's packed floats, field_bias0 [128] the fp32 bias row,
-     * grid_table the fp32 embeddings in the reference's layout, grid_offsets the reference's offsets */
+     * grid_table the fp32 embeddings in the reference's layout, grid_offsets the reference's offsets;
+     * 3: the temporal-basis model's fp16 fused field (sdn_field_basis_forward_f16): field_weights = its fragments, field_bias0 the
+     * basis row [128] (one row per frame of a frame group), grid_table / grid_offsets a PADDED or QUAD table; zero_deform is ignored */
     int32_t field_f32;
     int32_t reserved2_;
     /* optional [N] offsets in [0, 1), indexed by RAY: the perturbed first march of the reference's preview (`run_cuda(perturb=True)`:

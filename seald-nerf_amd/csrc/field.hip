@@ -109,7 +109,6 @@ __device__ __forceinline__ void stage_wait_and_sync() {
 //                64 gathers per point are as many cycles of that unit as the point's 240 MFMAs are of a matrix pipe), not by bytes:
 //                half the gathers, the same values into the same arithmetic.
 // The network's stages are field_f16_net.h's; what is written here is this kernel's schedule.
-constexpr int kLayoutRef = 0, kLayoutPad = 1, kLayoutQuad = 2;
 template <int OCC, int LA, bool CELLS, int LAYOUT>
 __global__ void __launch_bounds__(64 * kWaves, OCC) k_field_f16(FieldArgs P, TiledLevels lv) {
     constexpr bool PAD = LAYOUT != kLayoutRef;   // (no clamp / wrap bookkeeping in either derived layout)
@@ -416,7 +415,8 @@ static int g_field_pp_wgs = 0;   // workgroups of a persistent launch; 0 = one p
 constexpr uint32_t kPPMinTilesPerCU = 4;   // launches of at least this many 256-point tiles per CU take the persistent kernel
 
 // the kernels' argument records of one call (cell fields zero: field_cells_f16 sets its own)
-static int fill_field_args(FieldArgs &a, TiledLevels &lv, const FieldCall &f) {
+int field_table_layout(const int32_t *offsets_host) { return table_layout(offsets_host); }
+int fill_field_args(FieldArgs &a, TiledLevels &lv, const FieldCall &f) {
     int rc = fill_tiled_levels(lv, f.offsets_host, f.S, f.H);
     if (rc) return rc;
     a.xyzs = f.xyzs; a.dirs = f.dirs; a.live_idx = f.live_idx; a.live_count = f.live_count; a.state = f.state; a.M = f.M;

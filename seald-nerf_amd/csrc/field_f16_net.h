@@ -306,6 +306,9 @@ __device__ __forceinline__ uint32_t quad_corner(const uint4 (&quads)[2], uint32_
     return (idx & 3u) == 0u ? q.x : ((idx & 3u) == 1u ? q.y : ((idx & 3u) == 2u ? q.z : q.w));
 }
 
+// The fp16 table's layouts (field.hip describes them at k_field_f16; the host recognises one from the offsets it comes with).
+constexpr int kLayoutRef = 0, kLayoutPad = 1, kLayoutQuad = 2;
+
 // the lane-half's 8 levels x 2 features (packed pairs) as the sigma net's operand
 __device__ __forceinline__ void grid_operand(const uint32_t (&gfw)[2][4], half8 (&gf)[2]) {
     #pragma unroll
@@ -323,9 +326,10 @@ __device__ __forceinline__ f32x16 sigma_net(const unsigned char *tail, const hal
 // h[0] (lane-half 0, register 0) is the density logit; trunc_exp = exp in fp32 of the fp16 value
 // (v_exp_f32 on h log2(e): 1 ulp of the hardware exponential plus |h| 2^-24 from the product -- the reference's own operators use the
 //  fast intrinsics of their platform here (__expf), and sigma feeds a compositing sum that is compared at 1e-4 / fp16 distance)
-__device__ __forceinline__ float density(const f32x16 &hv, float density_scale) {
-    return density_scale * __builtin_amdgcn_exp2f(round_h(hv[0]) * 1.4426950408889634f);
+__device__ __forceinline__ float density_of_logit(float logit, float density_scale) {   // logit: an fp16 value
+    return density_scale * __builtin_amdgcn_exp2f(logit * 1.4426950408889634f);
 }
+__device__ __forceinline__ float density(const f32x16 &hv, float density_scale) { return density_of_logit(round_h(hv[0]), density_scale); }
 
 // ---------------- colour net: [geo_feat(15) ++ SH(16)] -> 64 -> 64 -> 3 ----------------
 // k-step 0 of its first layer: registers 0..7 of every lane = h[0..15], raw; the column of h[0] is zero in the packed weights
@@ -363,14 +367,22 @@ __device__ __forceinline__ f32x16 colour_out(const unsigned char *tail, const ha
     small_layer<1, 4>(tail, tC2, c2f, &co, lane);
     return co;
 }
-// rows 0..2 of `co` are the colour logits; torch.sigmoid on fp16: fp32 math, fp16 result
+// torch.sigmoid on an fp16 logit: fp32 math, fp16 result
+__device__ __forceinline__ float rgb_of_logit(float logit) {
+    return round_h(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(logit * -1.4426950408889634f)));
+}
+// rows 0..2 of `co` are the colour logits
 __device__ __forceinline__ void store_sigma_rgb(const FieldArgs &P, uint32_t p, float sigma, const f32x16 &co) {
     P.sigmas[p] = sigma;
     #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float logit = round_h(co[c]);
-        P.rgbs[(size_t)p * 3 + c] = round_h(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(logit * -1.4426950408889634f)));
-    }
+    for (int c = 0; c < 3; c++) P.rgbs[(size_t)p * 3 + c] = rgb_of_logit(round_h(co[c]));
 }
 
 }  // namespace sdn_f16
+
+// Host side, shared by the launchers of the kernels built from these stages (defined in field.hip): the kernels' argument records of
+// one call (cell fields zero), and the layout (kLayout*) a table's offsets announce.
+namespace sdn_int {
+int fill_field_args(sdn_f16::FieldArgs &a, sdn_f16::TiledLevels &lv, const FieldCall &f);
+int field_table_layout(const int32_t *offsets_host);
+}  // namespace sdn_int

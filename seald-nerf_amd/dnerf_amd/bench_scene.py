@@ -99,3 +99,31 @@ def camera_path(sc, n_frames, device=None, elevation=30.0):
         rds.append(torch.from_numpy(rd).to(device))
         times.append(float(f) / max(n_frames - 1, 1))
     return ros, rds, times
+
+
+@torch.no_grad()
+def build_basis_scene(H=800, W=800, device="cuda", seed=0, kind="jumpingjacks", time=0.5, azimuth=30.0, elevation=30.0):
+    """The same scene for the temporal-basis model (`network_basis.NeRFNetwork`, the reference's --basis): seeded weights, embeddings
+    x 1e3, and the 32 density-coefficient rows of the last sigma layer scaled by one factor so that the median of log sigma on the
+    probe set at `time` is log(MEDIAN_SIGMA_DT / dt) (log sigma is linear in those rows; the factor may be negative)."""
+    from .network_basis import NeRFNetwork as BasisNetwork
+    torch.manual_seed(seed)
+    model = BasisNetwork(bound=1, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=-1)
+    model.encoder.embeddings.mul_(1e3)
+    model = model.to(device).eval()
+    t_idx = int(min(max(math.floor(time * model.time_size), 0), model.time_size - 1))
+    bits = scene.density_bitfield_cascades(model.time_size, model.grid_size, model.cascade, 1.0, kind)
+    model.density_bitfield.copy_(torch.from_numpy(bits))
+    time_t = torch.tensor([[time]], dtype=torch.float32, device=device)
+    pts = torch.from_numpy(_probe_points(bits[t_idx][: model.grid_size ** 3 // 8], 8192, seed)).to(device)
+    keep = model.__dict__.get("fused_inference")
+    model.fused_inference = False
+    med = float(torch.log(model.density(pts, time_t)["sigma"]).median())
+    if keep is None:
+        del model.fused_inference
+    assert med != 0
+    model.sigma_net[-1].weight[:32].mul_(math.log(MEDIAN_SIGMA_DT / (2 * math.sqrt(3) / 1024)) / med)
+    pose = scene.look_at_pose(azimuth, elevation)
+    ro, rd = scene.get_rays(pose, scene.intrinsics(H, W), H, W)
+    return SimpleNamespace(model=model, rays_o=torch.from_numpy(ro).to(device), rays_d=torch.from_numpy(rd).to(device), time=time_t,
+                           H=H, W=W, kind=kind, t_idx=t_idx, bitfield=bits[t_idx], bitfields=bits, pose=pose)

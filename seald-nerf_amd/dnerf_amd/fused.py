@@ -115,9 +115,10 @@ def time_slice_index(t, T):
 
 class FusedFieldBase:
     """What the fp16 field (`FusedField`) and the fp32 one (`fused_f32.FusedFieldF32`) share: the constants of a time stamp cached by
-    VALUE, the output buffers, the geometry.  A subclass supplies its rounding rule (`_bias0`, `time_bias`), its packed weights
-    (`_packed`), its table (`_bind_table`, `load_table`), its launches (`__call__`, `query_cells`) and `ctx_kind`, the value of
-    `SdnRenderCtx.field_f32` that selects its kernel in the native loops."""
+    VALUE, the output buffers, the geometry.  A subclass supplies the constants of a time stamp (`_time_row`: the deformation model's
+    fields through `DeformTimeRow` and their rounding rule `_bias0`, `time_bias`), its packed weights (`_packed`), its table
+    (`_bind_table`, `load_table`: the fp16 kernels' through `Fp16Table`), its launches (`__call__`, `query_cells`) and `ctx_kind`, the
+    value of `SdnRenderCtx.field_f32` that selects its kernel in the native loops."""
 
     def __init__(self, model, time, max_points=None):
         enc = model.encoder
@@ -142,16 +143,13 @@ class FusedFieldBase:
         return float(np.float32(v))
 
     def time_constants(self, time):
-        """The constants one time stamp contributes to a frame, cached by VALUE: (bias0 [128] f32 -- the time encoding's
-        contribution W0[:,63:76] . freq(t, 6) to the first deform layer, in the subclass's precision --, zero_deform flag (t == 0: the
-        canonical frame, dnerf/network.py:139-141), index of the occupancy-grid time slice)."""
+        """The constants one time stamp contributes to a frame, cached by VALUE: (the frame's constants row [128] f32 and its flag
+        bit, both the subclass's (`_time_row`), index of the occupancy-grid time slice)."""
         t = self.time_value(time)
         hit = self._time_cache.get(t)
         if hit is None:
-            with torch.no_grad(), torch.autocast("cuda", enabled=False):
-                enc_t = freq_encode(torch.tensor([[t]], dtype=torch.float32, device=self.weights.device), 6, 13).reshape(13)
-                bias0 = self._bias0(self.model.deform_net[0].weight.detach(), enc_t)
-            hit = (bias0, int(t == 0.0), time_slice_index(t, self.model.time_size))
+            row, flag = self._time_row(t)
+            hit = (row, flag, time_slice_index(t, self.model.time_size))
             if len(self._time_cache) >= 4096:
                 self._time_cache.clear()
             self._time_cache[t] = hit
@@ -214,22 +212,25 @@ class FusedFieldBase:
         return self._buf[0][:M], self._buf[1][:M]
 
 
-class FusedField(FusedFieldBase):
-    """Callable (xyzs [M,3], dirs [M,3]) -> (sigmas [M] f32, rgbs [M,3] f32) with the reference's -O numerics."""
+class DeformTimeRow:
+    """The constants row of the deformation model's fields (dnerf/network.py): bias0 [128] f32 -- the time encoding's contribution
+    W0[:,63:76] . freq(t, 6) to the first deform layer, in the field's precision (`_bias0`) -- and the zero_deform flag (t == 0: the
+    canonical frame, dnerf/network.py:139-141)."""
 
-    ctx_kind = 0
+    def _time_row(self, t):
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            enc_t = freq_encode(torch.tensor([[t]], dtype=torch.float32, device=self.weights.device), 6, 13).reshape(13)
+            bias0 = self._bias0(self.model.deform_net[0].weight.detach(), enc_t)
+        return bias0, int(t == 0.0)
 
-    def __init__(self, model, time, fp16=True, max_points=None, table_layout=None):
-        if not fp16:
-            raise NotImplementedError("the fused field kernel implements the -O (fp16) configuration; use the op-by-op network for fp32")
-        if not available():
-            raise sdn_backend.SdnError("libsdn_hip was built without the fused field kernel")
+
+class Fp16Table:
+    """Table binding of the fp16 fused kernels (csrc/field.hip, csrc/field_basis.hip): an fp16 copy of the model's embeddings in a layout
+    of the kernels' own, "quad" (default; SDN_FIELD_TABLE in the environment overrides it) or "pad"."""
+
+    def _choose_layout(self, table_layout):
         self.layout = table_layout or os.environ.get("SDN_FIELD_TABLE", "quad")
         assert self.layout in ("quad", "pad"), self.layout
-        super().__init__(model, time, max_points)
-
-    def _packed(self):
-        return torch.from_numpy(pack_weights(self.model))
 
     def _bind_table(self, enc):
         # fp16 copy of the table (grid.py:43-44 under autocast) in a layout of the kernel's own (csrc/field.hip, kLayout*):
@@ -268,6 +269,23 @@ class FusedField(FusedFieldBase):
             dst = int(self.offsets_host[l])
             self.table[dst:dst + (b - a)].copy_(embeddings[a:b])
             self.table[dst + (b - a)].copy_(embeddings[a])
+
+
+class FusedField(DeformTimeRow, Fp16Table, FusedFieldBase):
+    """Callable (xyzs [M,3], dirs [M,3]) -> (sigmas [M] f32, rgbs [M,3] f32) with the reference's -O numerics."""
+
+    ctx_kind = 0
+
+    def __init__(self, model, time, fp16=True, max_points=None, table_layout=None):
+        if not fp16:
+            raise NotImplementedError("the fused field kernel implements the -O (fp16) configuration; use the op-by-op network for fp32")
+        if not available():
+            raise sdn_backend.SdnError("libsdn_hip was built without the fused field kernel")
+        self._choose_layout(table_layout)
+        super().__init__(model, time, max_points)
+
+    def _packed(self):
+        return torch.from_numpy(pack_weights(self.model))
 
     # bias0 in -O numerics: fp16-rounded operands, fp32 sum -- for one time stamp, and for the T slices of a density update at once
     # (two matrix expressions whose fp32 summation order may differ: kept side by side, not derived from one another)
@@ -323,6 +341,8 @@ class DensityGridUpdater:
                 field = FusedFieldF32(model, t0, variant="mfma32")
             else:
                 field = FusedField(model, t0, fp16=True)
+        if field.ctx_kind not in (0, 1, 2):
+            raise NotImplementedError("this field has no density query (CELLS kernel): keep its grid with the op-by-op update_extra_state")
         self.field = field
         self.fp32 = field.ctx_kind != 0
         n = model.grid_size ** 3

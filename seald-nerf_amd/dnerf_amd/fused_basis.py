@@ -1,0 +1,112 @@
+"""MI355X-native fused field of the temporal-basis model (`network_basis.NeRFNetwork`, the reference's `--basis`): host side of
+csrc/field_basis.hip.  Packs the five Linear layers of the sigma and colour nets into MFMA fragment order (30 blocks of 1 KiB, all
+resident in LDS), computes the basis row of a time stamp with the model's own `basis_net`, and launches the kernel through the C ABI.
+
+Fragment order: that of dnerf_amd/fused.py (`_pack_layer`).  The k-maps:
+  * first sigma layer: lane-half h owns grid levels 8h..8h+7 (`fused._s0_kmap`);
+  * hidden layers: the accumulator-as-operand order (`fused._acc_kmap`);
+  * first colour layer: k-step 0 = SH coefficient 8h + j, k-steps 1 and 2 = geo_feat -- output tile 1 of the sigma net, raw -- in
+    accumulator order, behind the 16 SH columns (the colour input is [SH(16), geo_feat(32)], network_basis.py:151-152).
+The constants row of a frame is [128] f32: sigma_basis in 0..31, color_basis in 32..39, zeros behind -- the fp16 values autocast's
+basis_net returns, which are exactly what the reference contracts with.
+"""
+import numpy as np
+import torch
+
+import sdn_backend
+from sdn_backend import check, ptr, stream
+
+from . import fused as F16
+
+SHAPES = {"sigma_net": [(64, 32), (64, 64)], "color_net": [(64, 48), (64, 64), (24, 64)]}
+ROW = 128
+
+
+def available():
+    return hasattr(sdn_backend.lib, "sdn_field_basis_forward_f16")
+
+
+def shapes_ok(model):
+    """The architecture the kernel is built for: the defaults of dnerf/network_basis.py on the default tiled grid."""
+    enc = model.encoder
+    nets_ok = all([tuple(l.weight.shape) for l in getattr(model, name)] == shapes for name, shapes in SHAPES.items())
+    return bool(nets_ok and model.sigma_basis_dim == 32 and model.color_basis_dim == 8 and enc.gridtype == "tiled" and not enc.align_corners
+                and enc.interpolation == "linear" and enc.num_levels == 16 and enc.level_dim == 2)
+
+
+def _c0_kmap(s):
+    h = np.arange(2)[:, None]
+    j = np.arange(8)[None, :]
+    if s == 0:
+        return 8 * h + j                           # SH coefficient
+    return 16 + F16._acc_kmap(0, s - 1)            # geo_feat[i] = sigma-net output 32 + i, i in accumulator order
+
+
+def layer_plan(weights):
+    """(W [out, in] float32, m-tile count, k-maps) of the five Linear layers in the kernel's block order S0 S1 C0 C1 C2; `weights`: their
+    arrays in that order."""
+    s0, s1, c0, c1, c2 = weights
+    hidden64 = [F16._acc_kmap(t, s) for t in range(2) for s in range(2)]
+    yield s0, 2, [F16._s0_kmap(s) for s in range(2)]
+    yield s1, 2, hidden64
+    yield c0, 2, [_c0_kmap(s) for s in range(3)]
+    yield c1, 2, hidden64
+    yield c2, 1, hidden64
+
+
+def pack_weights(model):
+    """[30, 64, 8] float16."""
+    g = lambda m: m.weight.detach().float().cpu().numpy()  # noqa: E731
+    ws = [g(l) for l in model.sigma_net] + [g(l) for l in model.color_net]
+    assert [w.shape for w in ws] == SHAPES["sigma_net"] + SHAPES["color_net"], "the fused kernel is built for the basis network's default shape"
+    packed = np.concatenate([F16._pack_layer(*layer) for layer in layer_plan(ws)], axis=0)
+    assert packed.shape[0] == int(sdn_backend.lib.sdn_field_basis_weight_blocks()), packed.shape
+    return packed
+
+
+class FusedBasisField(F16.Fp16Table, F16.FusedFieldBase):
+    """Callable (xyzs [M,3], dirs [M,3]) -> (sigmas [M] f32, rgbs [M,3] f32) with the reference's -O numerics, for the frame drivers of
+    dnerf_amd/frame_loops.py through `ctx_kind`.  `bias0` is the basis row of the selected time stamp (the name the drivers read);
+    `zero_deform` is always 0: the model deforms nothing."""
+
+    ctx_kind = 3
+
+    def __init__(self, model, time, fp16=True, max_points=None, table_layout=None):
+        if not fp16:
+            raise NotImplementedError("the fused basis field implements the -O (fp16) configuration; use the op-by-op network for fp32")
+        if not available():
+            raise sdn_backend.SdnError("libsdn_hip was built without the fused basis field kernel")
+        self._choose_layout(table_layout)
+        super().__init__(model, time, max_points)
+
+    def _packed(self):
+        return torch.from_numpy(pack_weights(self.model))
+
+    def _time_row(self, t):
+        """The basis of time stamp `t` from the model's own encoder_time and basis_net under fp16 autocast -> (row [128] f32, 0)."""
+        m = self.model
+        dev = self.weights.device
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+            sigma_basis, color_basis = m.basis(torch.tensor([[t]], dtype=torch.float32, device=dev))
+        row = torch.zeros(ROW, dtype=torch.float32, device=dev)
+        row[:32], row[32:40] = sigma_basis.float(), color_basis.float()
+        return row, 0
+
+    def invalidate_time_cache(self):
+        """Call after basis_net's weights changed: cached rows were computed from the old weights."""
+        self._time_cache.clear()
+        self._group_cache.clear()
+
+    def query_cells(self, *args, **kwargs):
+        raise NotImplementedError("the basis model has no density query (CELLS kernel): keep its grid with the op-by-op update_extra_state")
+
+    def __call__(self, xyzs, dirs, live_idx=None, live_count=None):
+        M = xyzs.shape[0]
+        sigmas, rgbs = self._outputs(M)
+        with sdn_backend.timed("field_basis_forward_f16", M):
+            check(sdn_backend.lib.sdn_field_basis_forward_f16(ptr(xyzs, torch.float32, "xyzs"), ptr(dirs, torch.float32, "dirs"),
+                                                              ptr(live_idx), ptr(live_count), M, ptr(self.weights), ptr(self.bias0),
+                                                              ptr(self.table), self.offsets_host.ctypes.data, self.S, self.H, self.bound,
+                                                              self.density_scale, ptr(sigmas), ptr(rgbs), stream()),
+                  "field_basis_forward_f16")
+        return sigmas, rgbs

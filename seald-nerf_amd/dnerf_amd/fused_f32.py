@@ -95,7 +95,7 @@ def pack_weights_f32_split(model):
     return flat
 
 
-class FusedFieldF32(F16.FusedFieldBase):
+class FusedFieldF32(F16.DeformTimeRow, F16.FusedFieldBase):
     """Callable (xyzs [M,3], dirs [M,3]) -> (sigmas [M] f32, rgbs [M,3] f32): the fp32 network (dnerf/network.py:123-169 without
     autocast) in one launch.  Same interface as `fused.FusedField` (time constants per value, live lists)."""
 
