@@ -266,6 +266,21 @@ int sdn_field_basis_forward_f16(const float *xyzs, const float *dirs, const uint
                                 const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale,
                                 float *sigmas, float *rgbs, void *stream);
 
+/* The fused field of the ambient-dimension model (reference: dnerf/network_hyper.py:121-161 under `-O`; csrc/field_hyper.hip): a 4-D
+ * tiled grid 16x2 (fp16 table) over (x, y, z, ambient) -> 64,33 sigma MLP = the density logit ++ 32 geo_feat; SH(4) ++ geo_feat ->
+ * 64,64,3 colour MLP; sigma = density_scale * exp(logit), rgb = sigmoid(logits), with autocast's fp16 roundings.  weights:
+ * sdn_field_hyper_weight_blocks() KiB in the fragment order of dnerf_amd/fused_hyper.py.  ambient_row [128] f32: entry 0 = the time
+ * stamp's ambient coordinate in [-bound, bound] (the model's ambient_net under autocast: an fp16 value), the rest zero; the kernel
+ * normalises it as it normalises x, y, z, and a coordinate outside the grid zeroes the features of every point.  table /
+ * offsets_host: the PADDED or the QUAD layout (sdn_field_build_quad_table_nd with input_dim 4) of the model's 4-D embeddings (the
+ * reference's layout: SDN_E_UNSUPPORTED).  Everything else as sdn_field_forward_f16.  There is no fp32 configuration, no density
+ * query and no persistent form of this kernel. */
+uint32_t sdn_field_hyper_weight_blocks(void);
+int sdn_field_hyper_forward_f16(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count,
+                                uint32_t M, const void *weights, const float *ambient_row /* [128] */, const void *table,
+                                const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale,
+                                float *sigmas, float *rgbs, void *stream);
+
 /* Which kernel large launches of the fused field network take: 1 = the persistent two-set ("ping-pong") kernel, the default for launches
  * of at least 4 tiles of 256 points per CU on a QUAD table; 0 = one tile per workgroup for every launch; -1 = environment SDN_FIELD_PP or
  * the default.  Both produce the same bits: a switch for tests and A/B measurements, not a tuning knob. */
@@ -281,6 +296,10 @@ void sdn_field_persistent_workgroups(int n);
  * dimension is dropped) as fp16 pairs.  Pass offsets_host[l] = ref_offsets_host[l] + 2 l to the field entry points. */
 int sdn_field_build_quad_table(const void *embeddings, int dtype, const int32_t *ref_offsets_host, float S, uint32_t H, void *out,
                                void *stream);
+/* The same for a tiled grid of input_dim 3 (identical to the above, byte for byte) or 4 (the ambient-dimension model's): a block is
+ * the four (x, y) corners whatever lies above them; the dimension decides which levels count as dense. */
+int sdn_field_build_quad_table_nd(const void *embeddings, int dtype, uint32_t input_dim, const int32_t *ref_offsets_host, float S,
+                                  uint32_t H, void *out, void *stream);
 
 /* ---------------------------------------------------------------------------
  * density-grid maintenance  (reference: NeRFRenderer.update_extra_state, dnerf/renderer.py:453-555; the network queries of
@@ -536,7 +555,10 @@ typedef struct SdnRenderCtx {
      * (the reference without `-O`): field_weights = sdn_field_forward_f32's packed floats, field_bias0 [128] the fp32 bias row,
      * grid_table the fp32 embeddings in the reference's layout, grid_offsets the reference's offsets;
      * 3: the temporal-basis model's fp16 fused field (sdn_field_basis_forward_f16): field_weights = its fragments, field_bias0 the
-     * basis row [128] (one row per frame of a frame group), grid_table / grid_offsets a PADDED or QUAD table; zero_deform is ignored */
+     * basis row [128] (one row per frame of a frame group), grid_table / grid_offsets a PADDED or QUAD table; zero_deform is ignored;
+     * 4: the ambient-dimension model's fp16 fused field (sdn_field_hyper_forward_f16): field_weights = its fragments, field_bias0 the
+     * ambient row [128] (entry 0 = the frame's ambient coordinate; one row per frame of a frame group), grid_table / grid_offsets a
+     * PADDED or QUAD copy of the 4-D table; zero_deform is ignored */
     int32_t field_f32;
     int32_t reserved2_;
     /* optional [N] offsets in [0, 1), indexed by RAY: the perturbed first march of the reference's preview (`run_cuda(perturb=True)`:

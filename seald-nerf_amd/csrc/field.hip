@@ -357,27 +357,35 @@ float exact_reciprocal(float v) {
     return 1.0f / v;
 }
 
-int fill_tiled_levels(TiledLevels &lv, const int32_t *offsets_host, float S, uint32_t H) {
+// D = 3 (the deformation and temporal-basis models' grid) or 4 (the ambient-dimension model's: s3 [16] receives the fourth stride)
+int fill_tiled_levels(TiledLevels &lv, const int32_t *offsets_host, float S, uint32_t H, uint32_t D = 3, uint32_t *s3 = nullptr) {
+    if (D != 3 && !(D == 4 && s3)) return SDN_E_BADARG;
     const int layout = table_layout(offsets_host);
     for (uint32_t l = 0; l < 16; l++) {
         const uint32_t hsize = (uint32_t)(offsets_host[l + 1] - offsets_host[l]) - (layout == kLayoutPad ? 1u : (layout == kLayoutQuad ? 2u : 0u));
         if (hsize == 0 || (uint32_t)offsets_host[16] >= (1u << 28)) return SDN_E_BADARG;   // (32-bit byte offsets into the table)
         const float scale = exp2f((float)l * S) * (float)H - 1.0f;  // gridencoder.cu:138
         const uint32_t res = (uint32_t)ceil((double)scale) + 1;      // gridencoder.cu:139
-        // get_grid_index (gridencoder.cu:66-84) for D = 3, align_corners = false, gridtype = tiled:
+        // get_grid_index (gridencoder.cu:66-84) for align_corners = false, gridtype = tiled:
         //   stride = 1; for d: if (stride <= hsize) { index += pos[d] * stride; stride *= res + 1; }
-        uint32_t stride = 1, s[3] = {0, 0, 0};
-        for (int d = 0; d < 3; d++) {
-            if (stride <= hsize) { s[d] = stride; stride *= (res + 1); }
+        // (64-bit here: a stride that no longer fits is never used -- the loop has stopped by then)
+        uint64_t stride = 1;
+        uint32_t s[4] = {0, 0, 0, 0};
+        for (uint32_t d = 0; d < D && stride <= hsize; d++) {
+            s[d] = (uint32_t)stride;
+            stride *= (res + 1);
         }
         if (s[0] != 1) return SDN_E_BADARG;
+        // (the 4-D kernel forms cell x stride with 24-bit multiplies, as level_cell does: strides never exceed the level's size)
+        if (D == 4 && hsize > (1u << 24)) return SDN_E_UNSUPPORTED;
+        if (s3) s3[l] = s[3];
         lv.offset[l] = (uint32_t)offsets_host[l];
         lv.s1[l] = s[1];
         lv.s2[l] = s[2];
         lv.hsize[l] = hsize;
         const bool pow2 = (hsize & (hsize - 1)) == 0;
         // a non-power-of-two level must be dense (every corner has its own row), otherwise the AND/min form would be wrong
-        if (!pow2 && (s[1] == 0 || s[2] == 0 || (uint64_t)(res + 1) * (res + 1) * (res + 1) > hsize)) return SDN_E_UNSUPPORTED;
+        if (!pow2 && (s[D - 1] == 0 || stride > hsize)) return SDN_E_UNSUPPORTED;
         lv.mask[l] = pow2 ? hsize - 1 : 0xFFFFFFFFu;
         lv.scale[l] = scale;
     }
@@ -416,9 +424,16 @@ constexpr uint32_t kPPMinTilesPerCU = 4;   // launches of at least this many 256
 
 // the kernels' argument records of one call (cell fields zero: field_cells_f16 sets its own)
 int field_table_layout(const int32_t *offsets_host) { return table_layout(offsets_host); }
+int fill_tiled_levels_nd(TiledLevels &lv, uint32_t (*s3)[16], uint32_t D, const int32_t *offsets_host, float S, uint32_t H) {
+    return fill_tiled_levels(lv, offsets_host, S, H, D, s3 ? *s3 : nullptr);
+}
 int fill_field_args(FieldArgs &a, TiledLevels &lv, const FieldCall &f) {
     int rc = fill_tiled_levels(lv, f.offsets_host, f.S, f.H);
     if (rc) return rc;
+    fill_field_record(a, f);
+    return 0;
+}
+void fill_field_record(FieldArgs &a, const FieldCall &f) {
     a.xyzs = f.xyzs; a.dirs = f.dirs; a.live_idx = f.live_idx; a.live_count = f.live_count; a.state = f.state; a.M = f.M;
     a.weights = (const unsigned char *)f.weights; a.bias0 = f.bias0; a.table = (const __half *)f.table;
     a.sigmas = f.sigmas; a.rgbs = f.rgbs; a.bound = f.bound; a.density_scale = f.density_scale; a.zero_deform = f.zero_deform;
@@ -426,7 +441,6 @@ int fill_field_args(FieldArgs &a, TiledLevels &lv, const FieldCall &f) {
     a.slot_frame = f.slot_frame; a.n_frames = field_n_frames(f);
     a.cell_noise = nullptr; a.cell_seed = 0; a.cell_inv = a.cell_span = a.cell_half = 0;
     a.pp_soft = 0;
-    return 0;
 }
 
 // One-tile-per-workgroup launch: the table layout x the variant (small: the latency variant, at most one workgroup per CU).  A
@@ -532,9 +546,16 @@ void sdn_field_persistent_workgroups(int n) { sdn_int::g_field_pp_wgs = n > 0 ? 
 //   out: (ref_offsets_host[16] + 32) blocks of 16 bytes -- level l starts at block ref_offsets_host[l] + 2 l (pass those 17 values as
 //   `offsets_host` to the field entry points: level sizes == 2 mod 8 announce the layout).
 int sdn_field_build_quad_table(const void *embeddings, int dtype, const int32_t *ref_offsets_host, float S, uint32_t H, void *out, void *stream) {
+    return sdn_field_build_quad_table_nd(embeddings, dtype, 3, ref_offsets_host, S, H, out, stream);
+}
+// The same for a grid of input_dim 3 or 4: a QUAD block is the four (x, y) corners whatever lies above them, so only the levels'
+// validation depends on the dimension; the blocks of a 3-D table are what sdn_field_build_quad_table writes.
+int sdn_field_build_quad_table_nd(const void *embeddings, int dtype, uint32_t input_dim, const int32_t *ref_offsets_host, float S, uint32_t H, void *out,
+                                  void *stream) {
     if (!embeddings || !ref_offsets_host || !out || ((uintptr_t)out & 15u) != 0) return SDN_E_BADARG;
     TiledLevels lv;
-    int rc = fill_tiled_levels(lv, ref_offsets_host, S, H);   // (reference offsets: level sizes are multiples of 8)
+    uint32_t s3[16];
+    int rc = fill_tiled_levels(lv, ref_offsets_host, S, H, input_dim, s3);   // (reference offsets: level sizes are multiples of 8)
     if (rc) return rc;
     QuadLevels q;
     for (int l = 0; l < 17; l++) q.src[l] = (uint32_t)ref_offsets_host[l];

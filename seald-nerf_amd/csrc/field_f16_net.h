@@ -381,8 +381,12 @@ __device__ __forceinline__ void store_sigma_rgb(const FieldArgs &P, uint32_t p, 
 }  // namespace sdn_f16
 
 // Host side, shared by the launchers of the kernels built from these stages (defined in field.hip): the kernels' argument records of
-// one call (cell fields zero), and the layout (kLayout*) a table's offsets announce.
+// one call (cell fields zero), and the layout (kLayout*) a table's offsets announce.  For a kernel with a grid of its own dimension
+// (field_hyper.hip: D = 4): the argument record without the levels, and the levels of a D-dimensional tiled grid -- the 3-D record plus
+// the fourth coordinate's stride s3 [16] (0 where a level's index drops it).
 namespace sdn_int {
 int fill_field_args(sdn_f16::FieldArgs &a, sdn_f16::TiledLevels &lv, const FieldCall &f);
+void fill_field_record(sdn_f16::FieldArgs &a, const FieldCall &f);
+int fill_tiled_levels_nd(sdn_f16::TiledLevels &lv, uint32_t (*s3)[16], uint32_t D, const int32_t *offsets_host, float S, uint32_t H);
 int field_table_layout(const int32_t *offsets_host);
 }  // namespace sdn_int

@@ -127,3 +127,29 @@ def build_basis_scene(H=800, W=800, device="cuda", seed=0, kind="jumpingjacks", 
     ro, rd = scene.get_rays(pose, scene.intrinsics(H, W), H, W)
     return SimpleNamespace(model=model, rays_o=torch.from_numpy(ro).to(device), rays_d=torch.from_numpy(rd).to(device), time=time_t,
                            H=H, W=W, kind=kind, t_idx=t_idx, bitfield=bits[t_idx], bitfields=bits, pose=pose)
+
+
+@torch.no_grad()
+def build_hyper_scene(H=800, W=800, device="cuda", seed=0, kind="jumpingjacks", time=0.5, azimuth=30.0, elevation=30.0, ambient_gain=256.0):
+    """The same scene for the ambient-dimension model (`network_hyper.NeRFNetwork`, the reference's --hyper): seeded weights, embeddings
+    x 1e3, the last ambient layer times `ambient_gain` (the seeded ambient_net moves the coordinate by a few 1e-3 over the whole
+    sequence: with the gain it crosses cells of the coarse levels) and row 0 of the last sigma layer -- the density logit -- scaled by
+    one factor so that the median of log sigma on the probe set at `time` is log(MEDIAN_SIGMA_DT / dt)."""
+    from .network_hyper import NeRFNetwork as HyperNetwork
+    torch.manual_seed(seed)
+    model = HyperNetwork(bound=1, cuda_ray=True, density_scale=1, min_near=0.2, density_thresh=10, bg_radius=-1)
+    model.encoder.embeddings.mul_(1e3)
+    model.ambient_net[-1].weight.mul_(ambient_gain)
+    model = model.to(device).eval()
+    t_idx = int(min(max(math.floor(time * model.time_size), 0), model.time_size - 1))
+    bits = scene.density_bitfield_cascades(model.time_size, model.grid_size, model.cascade, 1.0, kind)
+    model.density_bitfield.copy_(torch.from_numpy(bits))
+    time_t = torch.tensor([[time]], dtype=torch.float32, device=device)
+    pts = torch.from_numpy(_probe_points(bits[t_idx][: model.grid_size ** 3 // 8], 8192, seed)).to(device)
+    med = float(torch.log(model.density(pts, time_t)["sigma"]).median())      # (with gradients off and no autocast: the op-by-op path)
+    assert med != 0
+    model.sigma_net[-1].weight[0].mul_(math.log(MEDIAN_SIGMA_DT / (2 * math.sqrt(3) / 1024)) / med)
+    pose = scene.look_at_pose(azimuth, elevation)
+    ro, rd = scene.get_rays(pose, scene.intrinsics(H, W), H, W)
+    return SimpleNamespace(model=model, rays_o=torch.from_numpy(ro).to(device), rays_d=torch.from_numpy(rd).to(device), time=time_t,
+                           H=H, W=W, kind=kind, t_idx=t_idx, bitfield=bits[t_idx], bitfields=bits, pose=pose)

@@ -225,7 +225,7 @@ class DeformTimeRow:
 
 
 class Fp16Table:
-    """Table binding of the fp16 fused kernels (csrc/field.hip, csrc/field_basis.hip): an fp16 copy of the model's embeddings in a layout
+    """Table binding of the fp16 fused kernels (csrc/field.hip, csrc/field_basis.hip, csrc/field_hyper.hip): an fp16 copy of the model's embeddings in a layout
     of the kernels' own, "quad" (default; SDN_FIELD_TABLE in the environment overrides it) or "pad"."""
 
     def _choose_layout(self, table_layout):
@@ -241,7 +241,10 @@ class Fp16Table:
         #       every gather is two consecutive rows even when x is the level's last row (`(index + 1) % hashmap_size` == 0,
         #       gridencoder.cu:66-84): four 8-byte gathers per level, no clamp / wrap bookkeeping.
         # Either is recognised by the kernel from the offsets that come with it (level sizes == 2 / 1 mod 8).
+        # The encoder's input_dim (3, or 4 for fused_hyper) changes nothing here: a QUAD block is the four (x, y) corners and a PAD pair
+        # the (x, x+1) rows whatever lies above them; the library validates the levels for that dimension.
         dev = enc.embeddings.device
+        self._input_dim = int(enc.input_dim)
         off = enc.offsets.cpu().numpy().astype(np.int64)
         self._ref_offsets = np.ascontiguousarray(off.astype(np.int32))
         self._level_rows = [(int(off[l]), int(off[l + 1])) for l in range(16)]
@@ -262,8 +265,9 @@ class Fp16Table:
             if emb.dtype not in (torch.float32, torch.float16):
                 emb = emb.float()
             emb = emb.contiguous()
-            check(sdn_backend.lib.sdn_field_build_quad_table(ptr(emb), sdn_backend.dtype_id(emb.dtype), self._ref_offsets.ctypes.data,
-                                                             self.S, self.H, ptr(self.table), stream()), "field_build_quad_table")
+            check(sdn_backend.lib.sdn_field_build_quad_table_nd(ptr(emb), sdn_backend.dtype_id(emb.dtype), self._input_dim,
+                                                                self._ref_offsets.ctypes.data, self.S, self.H, ptr(self.table), stream()),
+                  "field_build_quad_table")
             return
         for l, (a, b) in enumerate(self._level_rows):
             dst = int(self.offsets_host[l])
@@ -341,7 +345,7 @@ class DensityGridUpdater:
                 field = FusedFieldF32(model, t0, variant="mfma32")
             else:
                 field = FusedField(model, t0, fp16=True)
-        if field.ctx_kind not in (0, 1, 2):
+        if field.ctx_kind not in (0, 1, 2):      # (3: the temporal-basis field, 4: the ambient-dimension field)
             raise NotImplementedError("this field has no density query (CELLS kernel): keep its grid with the op-by-op update_extra_state")
         self.field = field
         self.fp32 = field.ctx_kind != 0

@@ -58,6 +58,8 @@ class NativeTrainStep:
         grad_sync: a `dnerf_amd.dist.GradSync` for data-parallel training -- every rank runs forward + backward on its own batch, the
         fp16 gradient buffers of the step (24 MB table gradient + one 250 KB block with every MLP's) are all-reduced over RCCL, and
         the optimizer pass divides by the world size on top of the loss scale."""
+        if getattr(model, "ambient_net", None) is not None:
+            raise NotImplementedError("NativeTrainStep: the ambient-dimension model (network_hyper) has no native step; train it op by op")
         if not getattr(model, "cuda_ray", False) or model.mean_count <= 0:
             raise ValueError("NativeTrainStep needs the occupancy-grid path with a known point budget (model.mean_count > 0)")
         if getattr(model, "bg_radius", 0) > 0:

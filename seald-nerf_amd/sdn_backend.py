@@ -68,7 +68,9 @@ PROTOTYPES = {
     "sdn_field_forward_f32": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
     "sdn_field_forward_f32x3": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
     "sdn_field_basis_forward_f16": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _vp, _vp, _vp],
+    "sdn_field_hyper_forward_f16": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _vp, _vp, _vp],
     "sdn_field_build_quad_table": [_vp, _i32, _vp, _f32, _u32, _vp, _vp],
+    "sdn_field_build_quad_table_nd": [_vp, _i32, _u32, _vp, _f32, _u32, _vp, _vp],
     "sdn_grid_encode_forward_quad_f16": [_vp, _vp, _vp, _vp, _u32, _f32, _u32, _vp],
     "sdn_density_query_cells_f16": [_vp, _vp, _u32, _vp, _u32, _u32, _f32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp],
     "sdn_debug_shader_clock": [_vp, _u32, _vp],
@@ -190,6 +192,7 @@ PROTOTYPES.update({
 PROTOTYPES_U32 = {
     "sdn_field_weight_blocks": [],
     "sdn_field_basis_weight_blocks": [],
+    "sdn_field_hyper_weight_blocks": [],
     "sdn_field_weight_floats_f32": [],
     "sdn_cull_grid_bytes": [],
     "sdn_whole_rays_schedule_max_rays": [],
