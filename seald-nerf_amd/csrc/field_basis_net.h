@@ -66,12 +66,14 @@ __device__ __forceinline__ void grid_encode(const uint4 (&s_lv)[16][2], const un
 }
 
 // ---------------- sigma net: 32 -> 64 (ReLU) -> 64, no bias; hv[0] = the density coefficients, hv[1] = geo_feat ----------------
+// GEO = false (the density-grid query, which has no consumer for geo_feat): output tile 1 of the last layer is not computed
+template <bool GEO = true>
 __device__ __forceinline__ void sigma_net(const unsigned char *w, const half8 (&gf)[2], uint32_t lane, f32x16 (&hv)[2]) {
     f32x16 s0[2];
     small_layer<2, 2>(w, kBlkS0, gf, s0, lane);
     half8 sf[4];
     relu_frags(s0, sf);
-    small_layer<2, 4>(w, kBlkS1, sf, hv, lane);
+    small_layer<GEO ? 2 : 1, 4>(w, kBlkS1, sf, hv, lane);
 }
 
 // `h[:, lo : lo + 8 n] @ basis` as autocast runs it: an fp16 matrix-vector product -- fp16 operands (the Linear's output rounded to

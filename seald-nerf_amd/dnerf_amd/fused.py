@@ -335,20 +335,30 @@ class DensityGridUpdater:
 
     def __init__(self, model, field=None, fp32=False):
         """fp32: the update of a model trained WITHOUT -O -- the queries go through the fp32 fused kernel (csrc/field_f32.hip, CELLS
-        variant: `sdn_density_query_cells_f32`, within 1e-4 of the op-by-op fp32 network) on the model's fp32 table in place."""
+        variant: `sdn_density_query_cells_f32`, within 1e-4 of the op-by-op fp32 network) on the model's fp32 table in place.
+        A temporal-basis model (network_basis.py), or a `FusedBasisField` as `field`: the queries go through the CELLS variant of
+        csrc/field_basis.hip with one basis row per slice (`FusedBasisField.time_bias`); `-O` only, fp32=True raises."""
         self.model = model
         dev = model.density_grid.device
+        # the temporal-basis model (network_basis.py) or its field: queried through csrc/field_basis.hip, `-O` numerics only
+        basis = field.ctx_kind == 3 if field is not None else (not hasattr(model, "deform_net") and hasattr(model, "sigma_basis_dim"))
+        if basis and fp32:
+            raise NotImplementedError("the temporal-basis model has no fp32 density query: keep the grid of a model trained without -O "
+                                      "with the op-by-op update_extra_state")
         if field is None:
             t0 = model.times[0].reshape(1, 1).to(dev)
-            if fp32:
+            if basis:
+                from .fused_basis import FusedBasisField
+                field = FusedBasisField(model, t0, fp16=True)
+            elif fp32:
                 from .fused_f32 import FusedFieldF32
                 field = FusedFieldF32(model, t0, variant="mfma32")
             else:
                 field = FusedField(model, t0, fp16=True)
-        if field.ctx_kind not in (0, 1, 2):      # (3: the temporal-basis field, 4: the ambient-dimension field)
+        if field.ctx_kind not in (0, 1, 2, 3):   # (4: the ambient-dimension field)
             raise NotImplementedError("this field has no density query (CELLS kernel): keep its grid with the op-by-op update_extra_state")
         self.field = field
-        self.fp32 = field.ctx_kind != 0
+        self.fp32 = field.ctx_kind in (1, 2)
         n = model.grid_size ** 3
         self.tmp = torch.empty(n, dtype=torch.float32, device=dev)
         self.sum = torch.zeros(1, dtype=torch.float64, device=dev)

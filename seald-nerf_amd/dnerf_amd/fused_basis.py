@@ -9,6 +9,8 @@ Fragment order: that of dnerf_amd/fused.py (`_pack_layer`).  The k-maps:
     accumulator order, behind the 16 SH columns (the colour input is [SH(16), geo_feat(32)], network_basis.py:151-152).
 The constants row of a frame is [128] f32: sigma_basis in 0..31, color_basis in 32..39, zeros behind -- the fp16 values autocast's
 basis_net returns, which are exactly what the reference contracts with.
+The density-grid query (`query_cells`, `time_bias`: the CELLS variant of the kernel behind `fused.DensityGridUpdater`) takes the same
+packed weights and one such row per time slice.
 """
 import numpy as np
 import torch
@@ -97,8 +99,25 @@ class FusedBasisField(F16.Fp16Table, F16.FusedFieldBase):
         self._time_cache.clear()
         self._group_cache.clear()
 
-    def query_cells(self, *args, **kwargs):
-        raise NotImplementedError("the basis model has no density query (CELLS kernel): keep its grid with the op-by-op update_extra_state")
+    def time_bias(self, times):
+        """[K] (perturbed) times -> basis rows [K,128] for the slices of a density update; row k is `_time_row(times[k])[0]` bit for bit.
+        One `basis()` call per stamp, as `density(cas_xyzs, time_perturb)` makes it: a batched fp16 GEMM of K rows need not accumulate in
+        the order of the one-row product.  (`_time_row` opens its own autocast region: the trainer calls update_extra_state under one.)"""
+        return torch.stack([self._time_row(self.time_value(t))[0] for t in times.reshape(-1).tolist()]).contiguous()
+
+    def query_cells(self, out, bias0, zero_deform, cas_bound, cells=None, cell_count=None, n=None, noise=None, seed=0):
+        """out[cell] = density_scale * sigma for the listed (or the first n) cells of one occupancy slice (CELLS variant of the kernel);
+        bias0: the basis row of the slice's time.  zero_deform is accepted for the updater's sake and ignored: nothing deforms."""
+        if cells is not None:
+            n = cells.shape[0]
+        with sdn_backend.timed("density_query_cells_basis_f16", n):
+            check(sdn_backend.lib.sdn_density_query_cells_basis_f16(ptr(cells, torch.int32, "cells"), ptr(cell_count), n, ptr(noise, torch.float32, "noise"),
+                                                                    int(seed) & 0xFFFFFFFF, self.model.grid_size, float(cas_bound), ptr(self.weights),
+                                                                    ptr(bias0, torch.float32, "bias0"), ptr(self.table, torch.float16, "embeddings"),
+                                                                    self.offsets_host.ctypes.data, self.S, self.H, self.bound, self.density_scale,
+                                                                    ptr(out, torch.float32, "out"), stream()),
+                  "density_query_cells_basis_f16")
+        return out
 
     def __call__(self, xyzs, dirs, live_idx=None, live_count=None):
         M = xyzs.shape[0]

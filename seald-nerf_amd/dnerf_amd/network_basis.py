@@ -120,6 +120,20 @@ class NeRFNetwork(NeRFRenderer):
         field._buf = None              # fresh output tensors per call: the caller owns them, as on the op-by-op path
         return field(x.contiguous(), d.contiguous())
 
+    def use_native_density_update(self, field=None, fp32=False):
+        """Route update_extra_state through the CELLS variant of csrc/field_basis.hip + csrc/density.hip (`-O` numerics;
+        `fused.DensityGridUpdater`).  Opt-in: the op-by-op update stays the default.  The configurations the fused field refuses are
+        refused here."""
+        from . import fused_basis
+        if self.bg_radius > 0:
+            raise NotImplementedError("native density update of the temporal-basis model: bg_radius > 0 (the background sphere) is not "
+                                      "served by the fused basis field; keep the op-by-op update_extra_state")
+        if not fused_basis.shapes_ok(self):
+            raise NotImplementedError("native density update of the temporal-basis model: the fused basis field is built for the default "
+                                      "architecture of dnerf/network_basis.py (sigma net 32-64-64, colour net 48-64-64-24, basis 32 + 8, "
+                                      "16 x 2 tiled grid); keep the op-by-op update_extra_state")
+        return super().use_native_density_update(field, fp32=fp32)
+
     def forward(self, x, d, t):
         """x [M,3] in [-bound,bound], d [M,3] unit, t [1,1] -> sigma [M], rgb [M,3], None  (network_basis.py:123-161)."""
         if self._fused_inference_ok(x, d):
