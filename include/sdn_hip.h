@@ -334,6 +334,15 @@ int sdn_density_query_cells_basis_f16(const int32_t *cells, const uint32_t *cell
                                       uint32_t grid_size, float cas_bound, const void *weights, const float *basis_row, const void *table,
                                       const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale,
                                       float *tmp_slice, void *stream);
+/* The same query for the ambient-dimension model (dnerf/network_hyper.py under `-O`): the network of sdn_field_hyper_forward_f16 (weights
+ * = its 30 packed blocks, table in one of the two derived layouts; a reference-layout table is SDN_E_UNSUPPORTED, as there), ambient_row
+ * [128] with the ambient coordinate of the slice's -- perturbed -- time stamp in entry 0 where the deformation model's query takes
+ * bias0.  Nothing deforms: no zero_deform.  The range test covers all four coordinates, normalised by `bound`.  tmp_slice[cell] =
+ * density_scale * exp(fp16 logit), bit for bit the sigma sdn_field_hyper_forward_f16 returns for the same point. */
+int sdn_density_query_cells_hyper_f16(const int32_t *cells, const uint32_t *cell_count, uint32_t n, const float *noise, uint32_t seed,
+                                      uint32_t grid_size, float cas_bound, const void *weights, const float *ambient_row, const void *table,
+                                      const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale,
+                                      float *tmp_slice, void *stream);
 /* :536-538  density = max(density * decay, tmp) where density >= 0 and tmp >= 0, over n cells (n % 4 == 0, 16-byte aligned);
  * *sum (device, fp64, zeroed by the caller before the first slice) += sum of clamp(density, 0) after the update. */
 int sdn_density_grid_ema(float *density_grid, const float *tmp_grid, uint64_t n, float decay, double *sum, void *stream);

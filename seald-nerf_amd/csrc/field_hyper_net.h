@@ -17,6 +17,9 @@ constexpr int kBlkC0 = kBlkS1 + 8;     // [SH(16) ++ geo_feat(32)] -> 64: 2 Mt x
 constexpr int kBlkC1 = kBlkC0 + 6;     // 64 -> 64: 2 Mt x 4 ks
 constexpr int kBlkC2 = kBlkC1 + 8;     // 64 -> 3 (rows 3..31 of the tile are zero): 1 Mt x 4 ks
 constexpr int kBlkTotal = kBlkC2 + 4;  // 30
+// the density-grid query's LDS copy holds S0 and, right behind it, the logit tile of S1 (source blocks kBlkS1 + 4 .. kBlkS1 + 7)
+constexpr int kBlkS1Logit = kBlkS0 + 4;
+constexpr int kBlkCellsTotal = kBlkS1Logit + 4;  // 8
 
 // tiled-grid level constants for D = 4: the 3-D kernels' record (their view of it is unchanged) and the row stride of +1 along the
 // fourth coordinate (0 if the level's index drops it: gridencoder.cu:72)
@@ -150,12 +153,16 @@ __device__ __forceinline__ void grid_encode(const uint4 (&s_lv)[16][2], const ui
 }
 
 // ---------------- sigma net: 32 -> 64 (ReLU) -> 33, no bias; hv[0] = geo_feat, row 0 of hv[1] = the density logit ----------------
+// GEO = false (the density-grid query, which has no consumer for geo_feat): output tile 0 of the last layer is not computed, hv[0] is
+// left unset, and `w` is the query's short copy, where the logit tile's fragments start at kBlkS1Logit
+template <bool GEO = true>
 __device__ __forceinline__ void sigma_net(const unsigned char *w, const half8 (&gf)[2], uint32_t lane, f32x16 (&hv)[2]) {
     f32x16 s0[2];
     small_layer<2, 2>(w, kBlkS0, gf, s0, lane);
     half8 sf[4];
     relu_frags(s0, sf);
-    small_layer<2, 4>(w, kBlkS1, sf, hv, lane);
+    if constexpr (GEO) small_layer<2, 4>(w, kBlkS1, sf, hv, lane);
+    else small_layer<1, 4>(w, kBlkS1Logit, sf, &hv[1], lane);
 }
 
 // ---------------- colour net: [SH(16) ++ geo_feat(32)] -> 64 -> 64 -> 3, no bias ----------------

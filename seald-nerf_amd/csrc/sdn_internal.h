@@ -81,8 +81,8 @@ inline uint32_t field_n_frames(const FieldCall &f) {
 
 // one launcher per kernel; field_forward / field_cells pick by SdnRenderCtx::field_f32 (0: fp16, 1: fp32 MFMAs, 2: split fp16 operands,
 // 3: the temporal-basis model's fp16 field, whose bias0 rows are its basis rows -- its density query takes the one row of the slice's
-// time --, 4: the ambient-dimension model's fp16 field, whose bias0 rows hold the ambient coordinate in entry 0 and which has no
-// density query)
+// time --, 4: the ambient-dimension model's fp16 field, whose bias0 rows hold the ambient coordinate in entry 0 -- its density query
+// takes the one row of the slice's time too)
 int field_forward_f16(const FieldCall &f, hipStream_t st);
 int field_forward_f32(const FieldCall &f, hipStream_t st);
 int field_forward_f32x3(const FieldCall &f, hipStream_t st);
@@ -91,6 +91,7 @@ int field_forward_hyper(const FieldCall &f, hipStream_t st);
 int field_cells_f16(const FieldCells &q, hipStream_t st);
 int field_cells_f32(const FieldCells &q, hipStream_t st);
 int field_cells_basis(const FieldCells &q, hipStream_t st);
+int field_cells_hyper(const FieldCells &q, hipStream_t st);
 inline int field_forward(int kind, const FieldCall &f, hipStream_t st) {
     if (kind == 3) return field_forward_basis(f, st);
     if (kind == 4) return field_forward_hyper(f, st);
@@ -109,13 +110,13 @@ inline int field_forward_checked(int kind, const FieldCall &f, void *stream) {
     return field_forward(kind, f, (hipStream_t)stream);
 }
 inline int field_cells_checked(int kind, const FieldCells &q, void *stream) {
-    if (kind == 4) return SDN_E_UNSUPPORTED;
     if (q.f.M == 0) return 0;
     if (!field_buffers_ok(q.f)) return SDN_E_BADARG;
     if (q.grid_size < 2 || q.grid_size > 1024 || !(q.cas_bound > 0)) return SDN_E_BADARG;
     // without a list, slot p IS the Morton index: n may not exceed the grid
     if (!q.f.live_idx && (uint64_t)q.f.M > (uint64_t)q.grid_size * q.grid_size * q.grid_size) return SDN_E_BADARG;
     if (kind == 3) return field_cells_basis(q, (hipStream_t)stream);
+    if (kind == 4) return field_cells_hyper(q, (hipStream_t)stream);
     return kind ? field_cells_f32(q, (hipStream_t)stream) : field_cells_f16(q, (hipStream_t)stream);
 }
 

@@ -331,31 +331,44 @@ class DensityGridUpdater:
     The partial update (`iter_density` 16..99) draws the same two populations as the reference -- N = H^3 / 4 uniformly random cells
     plus N uniformly random *occupied* cells, with repetition -- but picks the occupied ones by rank (cumsum + searchsorted) instead
     of `torch.nonzero`, which would synchronise once per slice, and hands the kernel the union sorted by Morton index.
+
+    Serves the three models the reference trains with `--cuda_ray`: the deformation model (fp16 or fp32 field), the temporal-basis
+    model and the ambient-dimension model (both `-O` only), each through the CELLS variant of its own fused field kernel; the field
+    supplies `time_bias` (the constants row of every slice's perturbed time) and `query_cells`, everything else here is shared.
     """
 
     def __init__(self, model, field=None, fp32=False):
         """fp32: the update of a model trained WITHOUT -O -- the queries go through the fp32 fused kernel (csrc/field_f32.hip, CELLS
         variant: `sdn_density_query_cells_f32`, within 1e-4 of the op-by-op fp32 network) on the model's fp32 table in place.
         A temporal-basis model (network_basis.py), or a `FusedBasisField` as `field`: the queries go through the CELLS variant of
-        csrc/field_basis.hip with one basis row per slice (`FusedBasisField.time_bias`); `-O` only, fp32=True raises."""
+        csrc/field_basis.hip with one basis row per slice (`FusedBasisField.time_bias`); `-O` only, fp32=True raises.
+        An ambient-dimension model (network_hyper.py), or a `FusedHyperField` built with `density_query=True` as `field`: the CELLS
+        variant of csrc/field_hyper.hip with one ambient row per slice (`FusedHyperField.time_bias`); `-O` only, fp32=True raises.  A
+        hyper field built without `density_query=True` has no density query and is refused."""
         self.model = model
         dev = model.density_grid.device
         # the temporal-basis model (network_basis.py) or its field: queried through csrc/field_basis.hip, `-O` numerics only
         basis = field.ctx_kind == 3 if field is not None else (not hasattr(model, "deform_net") and hasattr(model, "sigma_basis_dim"))
-        if basis and fp32:
-            raise NotImplementedError("the temporal-basis model has no fp32 density query: keep the grid of a model trained without -O "
-                                      "with the op-by-op update_extra_state")
+        # the ambient-dimension model (network_hyper.py) or its field: csrc/field_hyper.hip, `-O` numerics only
+        hyper = field.ctx_kind == 4 if field is not None else (not hasattr(model, "deform_net") and hasattr(model, "ambient_net"))
+        if (basis or hyper) and fp32:
+            raise NotImplementedError(f"the {'temporal-basis' if basis else 'ambient-dimension'} model has no fp32 density query: keep "
+                                      "the grid of a model trained without -O with the op-by-op update_extra_state")
         if field is None:
             t0 = model.times[0].reshape(1, 1).to(dev)
             if basis:
                 from .fused_basis import FusedBasisField
                 field = FusedBasisField(model, t0, fp16=True)
+            elif hyper:
+                from .fused_hyper import FusedHyperField
+                field = FusedHyperField(model, t0, fp16=True, density_query=True)
             elif fp32:
                 from .fused_f32 import FusedFieldF32
                 field = FusedFieldF32(model, t0, variant="mfma32")
             else:
                 field = FusedField(model, t0, fp16=True)
-        if field.ctx_kind not in (0, 1, 2, 3):   # (4: the ambient-dimension field)
+        # (4: the ambient-dimension field, which offers the query only when it was built with density_query=True)
+        if field.ctx_kind not in (0, 1, 2, 3, 4) or (field.ctx_kind == 4 and not getattr(field, "has_density_query", False)):
             raise NotImplementedError("this field has no density query (CELLS kernel): keep its grid with the op-by-op update_extra_state")
         self.field = field
         self.fp32 = field.ctx_kind in (1, 2)

@@ -13,6 +13,8 @@ PERMUTED: geo_feat in tile 0 (rows 0..31), the logit in row 0 of tile 1, the res
 The constants row of a frame is [128] f32: entry 0 = the ambient coordinate in [-bound, bound], zeros behind.  Under autocast the
 reference's `tanh(ambient_net(.)) * bound` is an fp16 tensor and `torch.cat([x, ambient.repeat(..)])` promotes it to x's float32: the
 encoder receives the fp16 value as float32, and that is the value stored.
+The density-grid query (`query_cells`, `time_bias`: the CELLS variant of the kernel behind `fused.DensityGridUpdater`) takes the same
+packed weights and one such row per time slice; a field offers it when it is built with `density_query=True`.
 """
 import numpy as np
 import torch
@@ -24,6 +26,8 @@ from . import fused as F16
 
 SHAPES = {"sigma_net": [(64, 32), (33, 64)], "color_net": [(64, 48), (64, 64), (3, 64)]}
 ROW = 128
+_NO_QUERY = ("this hyper field was built without density_query=True and has no density query (CELLS kernel): keep its grid with the "
+             "op-by-op update_extra_state")
 
 
 def available():
@@ -72,8 +76,11 @@ class FusedHyperField(F16.Fp16Table, F16.FusedFieldBase):
     `zero_deform` is always 0: the model deforms nothing."""
 
     ctx_kind = 4
+    has_density_query = False    # an instance built with density_query=True sets it: `fused.DensityGridUpdater` reads it
 
-    def __init__(self, model, time, fp16=True, max_points=None, table_layout=None, persistent=False):
+    def __init__(self, model, time, fp16=True, max_points=None, table_layout=None, persistent=False, density_query=False):
+        """density_query: also offer `time_bias` / `query_cells`, the density-grid query behind `fused.DensityGridUpdater` (the CELLS
+        variant of the kernel, on the same packed weights and table).  Without it both raise NotImplementedError."""
         if not fp16:
             raise NotImplementedError("the fused hyper field implements the -O (fp16) configuration; use the op-by-op network for fp32")
         if persistent:
@@ -84,6 +91,7 @@ class FusedHyperField(F16.Fp16Table, F16.FusedFieldBase):
             raise NotImplementedError("the fused hyper field does not serve the native drivers with a background model (bg_radius > 0)")
         if not available():
             raise sdn_backend.SdnError("libsdn_hip was built without the fused hyper field kernel")
+        self.has_density_query = bool(density_query)
         self._choose_layout(table_layout)
         super().__init__(model, time, max_points)
 
@@ -105,8 +113,31 @@ class FusedHyperField(F16.Fp16Table, F16.FusedFieldBase):
         self._time_cache.clear()
         self._group_cache.clear()
 
-    def query_cells(self, *args, **kwargs):
-        raise NotImplementedError("the hyper model has no density query (CELLS kernel): keep its grid with the op-by-op update_extra_state")
+    def time_bias(self, times):
+        """[K] (perturbed) times -> ambient rows [K,128] for the slices of a density update; row k is `_time_row(times[k])[0]` bit for
+        bit.  One `ambient()` call per stamp, as `density(cas_xyzs, time_perturb)` makes it: a batched fp16 GEMM of K rows need not
+        accumulate in the order of the one-row product.  Nothing is cached: perturbed times never repeat.  (`_time_row` opens its own
+        autocast region: the trainer calls update_extra_state under one.)"""
+        if not self.has_density_query:
+            raise NotImplementedError(_NO_QUERY)
+        return torch.stack([self._time_row(self.time_value(t))[0] for t in times.reshape(-1).tolist()]).contiguous()
+
+    def query_cells(self, out, bias0, zero_deform, cas_bound, cells=None, cell_count=None, n=None, noise=None, seed=0):
+        """out[cell] = density_scale * sigma for the listed (or the first n) cells of one occupancy slice (CELLS variant of the kernel);
+        bias0: the ambient row of the slice's time.  zero_deform is accepted for the updater's sake and ignored: nothing deforms.
+        Only a field built with `density_query=True` offers it."""
+        if not self.has_density_query:
+            raise NotImplementedError(_NO_QUERY)
+        if cells is not None:
+            n = cells.shape[0]
+        with sdn_backend.timed("density_query_cells_hyper_f16", n):
+            check(sdn_backend.lib.sdn_density_query_cells_hyper_f16(ptr(cells, torch.int32, "cells"), ptr(cell_count), n, ptr(noise, torch.float32, "noise"),
+                                                                    int(seed) & 0xFFFFFFFF, self.model.grid_size, float(cas_bound), ptr(self.weights),
+                                                                    ptr(bias0, torch.float32, "bias0"), ptr(self.table, torch.float16, "embeddings"),
+                                                                    self.offsets_host.ctypes.data, self.S, self.H, self.bound, self.density_scale,
+                                                                    ptr(out, torch.float32, "out"), stream()),
+                  "density_query_cells_hyper_f16")
+        return out
 
     def __call__(self, xyzs, dirs, live_idx=None, live_count=None):
         M = xyzs.shape[0]

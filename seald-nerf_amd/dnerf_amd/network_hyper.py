@@ -118,6 +118,23 @@ class NeRFNetwork(NeRFRenderer):
         field._buf = None              # fresh output tensors per call: the caller owns them, as on the op-by-op path
         return field(x.contiguous(), d.contiguous())
 
+    def use_native_density_update(self, field=None, fp32=False):
+        """Route update_extra_state through the CELLS variant of csrc/field_hyper.hip + csrc/density.hip (`-O` numerics;
+        `fused.DensityGridUpdater`).  Opt-in: the op-by-op update stays the default.  The configurations the fused field refuses are
+        refused here."""
+        from . import fused_hyper
+        if self.bg_radius > 0:
+            raise NotImplementedError("native density update of the ambient-dimension model: bg_radius > 0 (the background sphere) is "
+                                      "not served by the fused hyper field; keep the op-by-op update_extra_state")
+        if self.ambient_dim != 1:
+            raise NotImplementedError("native density update of the ambient-dimension model: the fused hyper field is built for "
+                                      "ambient_dim == 1 (a 4-D grid); keep the op-by-op update_extra_state")
+        if not fused_hyper.shapes_ok(self):
+            raise NotImplementedError("native density update of the ambient-dimension model: the fused hyper field is built for the "
+                                      "default architecture of dnerf/network_hyper.py (sigma net 32-64-33, colour net 48-64-64-3, "
+                                      "16 x 2 tiled grid over 4 coordinates); keep the op-by-op update_extra_state")
+        return super().use_native_density_update(field, fp32=fp32)
+
     def forward(self, x, d, t):
         """x [M,3] in [-bound,bound], d [M,3] unit, t [1,1] -> sigma [M], rgb [M,3], None  (network_hyper.py:121-161)."""
         if self._fused_inference_ok(x, d):
