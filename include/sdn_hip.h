@@ -266,6 +266,18 @@ int sdn_field_basis_forward_f16(const float *xyzs, const float *dirs, const uint
                                 const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale,
                                 float *sigmas, float *rgbs, void *stream);
 
+/* The same model in fp32 (the reference without `-O`; csrc/field_basis_f32.hip: v_mfma_f32_32x32x2_f32, fp32 encoders, both
+ * contractions accumulated in fp32): weights = sdn_field_basis_weight_floats_f32() floats in the order of
+ * dnerf_amd/fused_basis.py:pack_weights_f32, basis_row [128] f32 = the model's basis_net without autocast (sigma_basis in 0..31,
+ * color_basis in 32..39, the rest zero), table = the model's fp32 embeddings [offsets_host[16], 2] in the reference's layout (read in
+ * place), offsets_host [17] the reference's level offsets (a PADDED or QUAD table: SDN_E_UNSUPPORTED).  Everything else as
+ * sdn_field_basis_forward_f16. */
+uint32_t sdn_field_basis_weight_floats_f32(void);
+int sdn_field_basis_forward_f32(const float *xyzs, const float *dirs, const uint32_t *live_idx, const uint32_t *live_count,
+                                uint32_t M, const float *weights, const float *basis_row /* [128] */, const float *table,
+                                const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale,
+                                float *sigmas, float *rgbs, void *stream);
+
 /* The fused field of the ambient-dimension model (reference: dnerf/network_hyper.py:121-161 under `-O`; csrc/field_hyper.hip): a 4-D
  * tiled grid 16x2 (fp16 table) over (x, y, z, ambient) -> 64,33 sigma MLP = the density logit ++ 32 geo_feat; SH(4) ++ geo_feat ->
  * 64,64,3 colour MLP; sigma = density_scale * exp(logit), rgb = sigmoid(logits), with autocast's fp16 roundings.  weights:
@@ -334,6 +346,14 @@ int sdn_density_query_cells_basis_f16(const int32_t *cells, const uint32_t *cell
                                       uint32_t grid_size, float cas_bound, const void *weights, const float *basis_row, const void *table,
                                       const int32_t *offsets_host, float S, uint32_t H, float bound, float density_scale,
                                       float *tmp_slice, void *stream);
+/* The same query for a temporal-basis model trained WITHOUT `-O`: the fp32 network of sdn_field_basis_forward_f32 (weights = its
+ * packed floats, basis_row the fp32 basis of the slice's -- perturbed -- time stamp, table = the model's fp32 embeddings in the
+ * reference layout with the reference's offsets).  tmp_slice[cell] = density_scale * exp(coefficients . sigma_basis), bit for bit the
+ * sigma sdn_field_basis_forward_f32 returns for the same point and row. */
+int sdn_density_query_cells_basis_f32(const int32_t *cells, const uint32_t *cell_count, uint32_t n, const float *noise, uint32_t seed,
+                                      uint32_t grid_size, float cas_bound, const float *weights, const float *basis_row,
+                                      const float *table, const int32_t *offsets_host, float S, uint32_t H, float bound,
+                                      float density_scale, float *tmp_slice, void *stream);
 /* The same query for the ambient-dimension model (dnerf/network_hyper.py under `-O`): the network of sdn_field_hyper_forward_f16 (weights
  * = its 30 packed blocks, table in one of the two derived layouts; a reference-layout table is SDN_E_UNSUPPORTED, as there), ambient_row
  * [128] with the ambient coordinate of the slice's -- perturbed -- time stamp in entry 0 where the deformation model's query takes
@@ -576,7 +596,10 @@ typedef struct SdnRenderCtx {
      * basis row [128] (one row per frame of a frame group), grid_table / grid_offsets a PADDED or QUAD table; zero_deform is ignored;
      * 4: the ambient-dimension model's fp16 fused field (sdn_field_hyper_forward_f16): field_weights = its fragments, field_bias0 the
      * ambient row [128] (entry 0 = the frame's ambient coordinate; one row per frame of a frame group), grid_table / grid_offsets a
-     * PADDED or QUAD copy of the 4-D table; zero_deform is ignored */
+     * PADDED or QUAD copy of the 4-D table; zero_deform is ignored;
+     * 5: the temporal-basis model's fp32 fused field (sdn_field_basis_forward_f32): field_weights = its packed floats, field_bias0 the
+     * fp32 basis row [128] (one row per frame of a frame group), grid_table / grid_offsets the fp32 embeddings and offsets in the
+     * reference's layout; zero_deform is ignored */
     int32_t field_f32;
     int32_t reserved2_;
     /* optional [N] offsets in [0, 1), indexed by RAY: the perturbed first march of the reference's preview (`run_cuda(perturb=True)`:

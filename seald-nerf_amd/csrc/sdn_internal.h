@@ -82,19 +82,23 @@ inline uint32_t field_n_frames(const FieldCall &f) {
 // one launcher per kernel; field_forward / field_cells pick by SdnRenderCtx::field_f32 (0: fp16, 1: fp32 MFMAs, 2: split fp16 operands,
 // 3: the temporal-basis model's fp16 field, whose bias0 rows are its basis rows -- its density query takes the one row of the slice's
 // time --, 4: the ambient-dimension model's fp16 field, whose bias0 rows hold the ambient coordinate in entry 0 -- its density query
-// takes the one row of the slice's time too)
+// takes the one row of the slice's time too, 5: the temporal-basis model's fp32 field (field_basis_f32.hip): basis rows as kind 3 in
+// fp32, the packed floats and the fp32 table in the reference layout as kind 1)
 int field_forward_f16(const FieldCall &f, hipStream_t st);
 int field_forward_f32(const FieldCall &f, hipStream_t st);
 int field_forward_f32x3(const FieldCall &f, hipStream_t st);
 int field_forward_basis(const FieldCall &f, hipStream_t st);
 int field_forward_hyper(const FieldCall &f, hipStream_t st);
+int field_forward_basis_f32(const FieldCall &f, hipStream_t st);
 int field_cells_f16(const FieldCells &q, hipStream_t st);
 int field_cells_f32(const FieldCells &q, hipStream_t st);
 int field_cells_basis(const FieldCells &q, hipStream_t st);
 int field_cells_hyper(const FieldCells &q, hipStream_t st);
+int field_cells_basis_f32(const FieldCells &q, hipStream_t st);
 inline int field_forward(int kind, const FieldCall &f, hipStream_t st) {
     if (kind == 3) return field_forward_basis(f, st);
     if (kind == 4) return field_forward_hyper(f, st);
+    if (kind == 5) return field_forward_basis_f32(f, st);
     return kind == 2 ? field_forward_f32x3(f, st) : (kind ? field_forward_f32(f, st) : field_forward_f16(f, st));
 }
 
@@ -117,6 +121,7 @@ inline int field_cells_checked(int kind, const FieldCells &q, void *stream) {
     if (!q.f.live_idx && (uint64_t)q.f.M > (uint64_t)q.grid_size * q.grid_size * q.grid_size) return SDN_E_BADARG;
     if (kind == 3) return field_cells_basis(q, (hipStream_t)stream);
     if (kind == 4) return field_cells_hyper(q, (hipStream_t)stream);
+    if (kind == 5) return field_cells_basis_f32(q, (hipStream_t)stream);
     return kind ? field_cells_f32(q, (hipStream_t)stream) : field_cells_f16(q, (hipStream_t)stream);
 }
 

@@ -333,7 +333,7 @@ class DensityGridUpdater:
     of `torch.nonzero`, which would synchronise once per slice, and hands the kernel the union sorted by Morton index.
 
     Serves the three models the reference trains with `--cuda_ray`: the deformation model (fp16 or fp32 field), the temporal-basis
-    model and the ambient-dimension model (both `-O` only), each through the CELLS variant of its own fused field kernel; the field
+    model (fp16 field, or the fp32 one handed over as `field`) and the ambient-dimension model (`-O` only), each through the CELLS variant of its own fused field kernel; the field
     supplies `time_bias` (the constants row of every slice's perturbed time) and `query_cells`, everything else here is shared.
     """
 
@@ -341,7 +341,9 @@ class DensityGridUpdater:
         """fp32: the update of a model trained WITHOUT -O -- the queries go through the fp32 fused kernel (csrc/field_f32.hip, CELLS
         variant: `sdn_density_query_cells_f32`, within 1e-4 of the op-by-op fp32 network) on the model's fp32 table in place.
         A temporal-basis model (network_basis.py), or a `FusedBasisField` as `field`: the queries go through the CELLS variant of
-        csrc/field_basis.hip with one basis row per slice (`FusedBasisField.time_bias`); `-O` only, fp32=True raises.
+        csrc/field_basis.hip with one basis row per slice (`FusedBasisField.time_bias`); `-O` numerics, fp32=True raises.  A
+        temporal-basis model trained WITHOUT -O: hand over `field=fused_basis.FusedBasisFieldF32(model, t0)` -- the CELLS variant of
+        csrc/field_basis_f32.hip on the model's fp32 table in place, within 1e-4 of the op-by-op fp32 network.
         An ambient-dimension model (network_hyper.py), or a `FusedHyperField` built with `density_query=True` as `field`: the CELLS
         variant of csrc/field_hyper.hip with one ambient row per slice (`FusedHyperField.time_bias`); `-O` only, fp32=True raises.  A
         hyper field built without `density_query=True` has no density query and is refused."""
@@ -351,8 +353,12 @@ class DensityGridUpdater:
         basis = field.ctx_kind == 3 if field is not None else (not hasattr(model, "deform_net") and hasattr(model, "sigma_basis_dim"))
         # the ambient-dimension model (network_hyper.py) or its field: csrc/field_hyper.hip, `-O` numerics only
         hyper = field.ctx_kind == 4 if field is not None else (not hasattr(model, "deform_net") and hasattr(model, "ambient_net"))
-        if (basis or hyper) and fp32:
-            raise NotImplementedError(f"the {'temporal-basis' if basis else 'ambient-dimension'} model has no fp32 density query: keep "
+        if basis and fp32:
+            raise NotImplementedError("the temporal-basis model has no fp32 density query behind `fp32=True`: hand over the fp32 field "
+                                      "(`field=fused_basis.FusedBasisFieldF32(model, t0)`), or keep the grid of a model trained without "
+                                      "-O with the op-by-op update_extra_state")
+        if hyper and fp32:
+            raise NotImplementedError("the ambient-dimension model has no fp32 density query: keep "
                                       "the grid of a model trained without -O with the op-by-op update_extra_state")
         if field is None:
             t0 = model.times[0].reshape(1, 1).to(dev)
@@ -367,11 +373,12 @@ class DensityGridUpdater:
                 field = FusedFieldF32(model, t0, variant="mfma32")
             else:
                 field = FusedField(model, t0, fp16=True)
-        # (4: the ambient-dimension field, which offers the query only when it was built with density_query=True)
-        if field.ctx_kind not in (0, 1, 2, 3, 4) or (field.ctx_kind == 4 and not getattr(field, "has_density_query", False)):
+        # (4: the ambient-dimension field, which offers the query only when it was built with density_query=True; 5: the temporal-basis
+        #  model's fp32 field)
+        if field.ctx_kind not in (0, 1, 2, 3, 4, 5) or (field.ctx_kind == 4 and not getattr(field, "has_density_query", False)):
             raise NotImplementedError("this field has no density query (CELLS kernel): keep its grid with the op-by-op update_extra_state")
         self.field = field
-        self.fp32 = field.ctx_kind in (1, 2)
+        self.fp32 = field.ctx_kind in (1, 2, 5)
         n = model.grid_size ** 3
         self.tmp = torch.empty(n, dtype=torch.float32, device=dev)
         self.sum = torch.zeros(1, dtype=torch.float64, device=dev)

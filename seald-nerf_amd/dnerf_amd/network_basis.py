@@ -11,10 +11,13 @@ Two evaluation paths, as in dnerf_amd/network.py:
   * `forward` / `density` / `background` / `color` -- the reference's op sequence on the drop-in operators; differentiable.
   * the fused dispatch inside `forward`: in eval mode, without autograd, under fp16 autocast (the reference's `-O`) and with the
     default geometry the whole network is ONE launch of csrc/field_basis.hip (`sdn_field_basis_forward_f16`) behind
-    `fused_basis.FusedBasisField`; `model.fused_inference = False` switches it off.  There is no fused fp32 configuration.
+    `fused_basis.FusedBasisField`; `model.fused_inference = False` switches it off.  Without autocast (the reference without `-O`)
+    `forward` stays op by op unless `model.fused_inference_f32 = True`: then it is one launch of csrc/field_basis_f32.hip
+    (`sdn_field_basis_forward_f32`) behind `fused_basis.FusedBasisFieldF32`, within 1e-4 of the op-by-op fp32 network.
 """
 import torch
 
+import sdn_backend
 from freqencoder import FreqEncoder
 from gridencoder import GridEncoder
 from shencoder import SHEncoder
@@ -79,19 +82,38 @@ class NeRFNetwork(NeRFRenderer):
     # -- fused inference dispatch -----------------------------------------------------------------
     fused_inference = True       # class default; set False on a model to keep `forward` on the op-by-op path in every mode
 
+    fused_inference_f32 = False  # opt-in: without autocast (the reference without -O) dispatch to the fp32 fused kernel as well
+
     def _fused_inference_ok(self, x, d):
+        """False, or the mode of the fused dispatch: 16 (-O: csrc/field_basis.hip) or 32 (no autocast, opt-in: csrc/field_basis_f32.hip)."""
         if not self.fused_inference or self.training or torch.is_grad_enabled() or not x.is_cuda or x.dim() != 2 or x.shape[0] == 0:
             return False
         if x.dtype != torch.float32 or d.dtype != torch.float32:
             return False
-        if not torch.is_autocast_enabled("cuda") or torch.get_autocast_dtype("cuda") != torch.float16:
-            return False       # without -O the model stays op by op: there is no fused fp32 configuration of it
+        if not torch.is_autocast_enabled("cuda"):
+            if not self.fused_inference_f32:
+                return False   # the default without -O stays the op-by-op network, what the fp32 fixture pins
+            mode = 32
+        elif torch.get_autocast_dtype("cuda") == torch.float16:
+            mode = 16
+        else:
+            return False
         ok = self.__dict__.get("_fused_arch_ok")
         if ok is None:         # the architecture does not change after construction
             from . import fused_basis
             ok = bool(fused_basis.available() and fused_basis.shapes_ok(self))
             self.__dict__["_fused_arch_ok"] = ok
-        return ok
+        if not ok:
+            return False
+        if mode == 32:
+            ok32 = self.__dict__.get("_fused_f32_ok")
+            if ok32 is None:
+                from . import fused_basis
+                ok32 = bool(fused_basis.available_f32() and not self.bg_radius > 0)
+                self.__dict__["_fused_f32_ok"] = ok32
+            if not ok32 or any(p.dtype != torch.float32 for p in (self.encoder.embeddings, self.sigma_net[0].weight, self.basis_net[0].weight)):
+                return False
+        return mode
 
     def _parameter_epoch(self):
         ps = self.__dict__.get("_fused_params")
@@ -102,19 +124,30 @@ class NeRFNetwork(NeRFRenderer):
 
     _fused_time_value = _DeformNetwork._fused_time_value
 
-    def _forward_fused(self, x, d, t):
-        """The whole network in one launch: sigma [M] f32 (density_scale NOT applied: the caller multiplies), rgb [M,3] (the fp16 values
-        of torch.sigmoid on the half logits, held in f32)."""
+    def _forward_fused(self, x, d, t, mode=16):
+        """The whole network in one launch: sigma [M] f32 (density_scale NOT applied: the caller multiplies), rgb [M,3].  mode 16 (-O):
+        rgb holds the fp16 values of torch.sigmoid on the half logits in f32; mode 32: float32 throughout, within 1e-4 of the op-by-op
+        evaluation (tests/test_gpu_basis_f32.py).  Each mode keeps its own field, built once per parameter version."""
         epoch = self._parameter_epoch()
-        cache = self.__dict__.get("_fused_cache")
-        if cache is None or cache[0] != epoch[1:]:
-            from . import fused_basis
-            field = fused_basis.FusedBasisField(self, t, fp16=True)
-            field.density_scale = 1.0
-            cache = self.__dict__["_fused_cache"] = (epoch[1:], field, epoch[0])
-        elif cache[2] != epoch[0]:      # only the embeddings moved
-            cache[1].load_table(self.encoder.embeddings.detach())
-            cache = self.__dict__["_fused_cache"] = (cache[0], cache[1], epoch[0])
+        if mode == 16:
+            cache = self.__dict__.get("_fused_cache")
+            if cache is None or cache[0] != epoch[1:]:
+                from . import fused_basis
+                field = fused_basis.FusedBasisField(self, t, fp16=True)
+                field.density_scale = 1.0
+                cache = self.__dict__["_fused_cache"] = (epoch[1:], field, epoch[0])
+            elif cache[2] != epoch[0]:      # only the embeddings moved
+                cache[1].load_table(self.encoder.embeddings.detach())
+                cache = self.__dict__["_fused_cache"] = (cache[0], cache[1], epoch[0])
+        else:
+            sdn_backend.await_pending_write(self.encoder.embeddings)     # (read in place below: a table pass still running elsewhere)
+            cache = self.__dict__.get("_fused_cache32")
+            if cache is None or cache[0] != epoch[1:] or cache[2][0] != epoch[0][0]:
+                from . import fused_basis
+                # (the table is read where it is: its in-place updates need nothing, only another tensor does)
+                field = fused_basis.FusedBasisFieldF32(self, t)
+                field.density_scale = 1.0
+                cache = self.__dict__["_fused_cache32"] = (epoch[1:], field, epoch[0])
         field = cache[1]
         field.set_time_if_changed(self._fused_time_value(field, t))
         field._buf = None              # fresh output tensors per call: the caller owns them, as on the op-by-op path
@@ -123,7 +156,8 @@ class NeRFNetwork(NeRFRenderer):
     def use_native_density_update(self, field=None, fp32=False):
         """Route update_extra_state through the CELLS variant of csrc/field_basis.hip + csrc/density.hip (`-O` numerics;
         `fused.DensityGridUpdater`).  Opt-in: the op-by-op update stays the default.  The configurations the fused field refuses are
-        refused here."""
+        refused here.  A model trained without -O: `field=fused_basis.FusedBasisFieldF32(model, t0)` (the CELLS variant of
+        csrc/field_basis_f32.hip); `fp32=True` without a field stays refused."""
         from . import fused_basis
         if self.bg_radius > 0:
             raise NotImplementedError("native density update of the temporal-basis model: bg_radius > 0 (the background sphere) is not "
@@ -136,8 +170,9 @@ class NeRFNetwork(NeRFRenderer):
 
     def forward(self, x, d, t):
         """x [M,3] in [-bound,bound], d [M,3] unit, t [1,1] -> sigma [M], rgb [M,3], None  (network_basis.py:123-161)."""
-        if self._fused_inference_ok(x, d):
-            sigma, rgb = self._forward_fused(x, d, t)
+        mode = self._fused_inference_ok(x, d)
+        if mode:
+            sigma, rgb = self._forward_fused(x, d, t, mode)
             return sigma, rgb, None
         sigma_basis, color_basis = self.basis(t)
         sigma, geo_feat = self._sigma(x, sigma_basis)

@@ -68,6 +68,8 @@ PROTOTYPES = {
     "sdn_field_forward_f32": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
     "sdn_field_forward_f32x3": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
     "sdn_field_basis_forward_f16": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _vp, _vp, _vp],
+    "sdn_field_basis_forward_f32": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _vp, _vp, _vp],
+    "sdn_density_query_cells_basis_f32": [_vp, _vp, _u32, _vp, _u32, _u32, _f32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _vp, _vp],
     "sdn_field_hyper_forward_f16": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _f32, _u32, _f32, _f32, _vp, _vp, _vp],
     "sdn_field_build_quad_table": [_vp, _i32, _vp, _f32, _u32, _vp, _vp],
     "sdn_field_build_quad_table_nd": [_vp, _i32, _u32, _vp, _f32, _u32, _vp, _vp],
@@ -196,6 +198,7 @@ PROTOTYPES_U32 = {
     "sdn_field_basis_weight_blocks": [],
     "sdn_field_hyper_weight_blocks": [],
     "sdn_field_weight_floats_f32": [],
+    "sdn_field_basis_weight_floats_f32": [],
     "sdn_cull_grid_bytes": [],
     "sdn_whole_rays_schedule_max_rays": [],
 }
