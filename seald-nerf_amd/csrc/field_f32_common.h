@@ -57,6 +57,14 @@ __device__ __forceinline__ float relu1(float x) {
     const int b = __builtin_bit_cast(int, x);
     return __builtin_bit_cast(float, b > 0 ? b : 0);
 }
+// ReLU that keeps a NaN of EITHER sign, for a kernel whose operands can overflow (field_f32x3.hip): an activation above the fp16 range
+// splits into +inf and -inf, the MFMA's 0 * inf and inf - inf are NaNs with the sign bit set, and relu1 would turn those into a
+// plausible 0.  As signed integers the negative NaNs are the negative numbers closest to zero (0xff800001 .. 0xffffffff), above -inf
+// (0xff800000) and every negative float: one compare against -inf's bits and a select.
+__device__ __forceinline__ float relu1_keep_nan(float x) {
+    const int b = __builtin_bit_cast(int, x);
+    return __builtin_bit_cast(float, b > (int)0xff800000 ? b : 0);
+}
 
 // The point of this lane: lane half h = lane / 32 of point n = lane % 32 of the wave's 32 (both halves hold the same point).
 struct Point {

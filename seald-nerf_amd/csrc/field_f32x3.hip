@@ -13,6 +13,9 @@
 // every weight below 0.25 would lose its lo part (measured: 2e-4 relative errors).  Activations travel as 2^6 x and weights as 2^8 w
 // (exact scalings), accumulators hold 2^14 times the layer's output and are brought back by the 2^-8 of the next split / the 2^-14 of an
 // output: lo parts stay normal down to |x| = 4e-3 and |w| = 1e-3, the hi parts fit fp16 up to |x| = 1023 and |w| = 255.
+// Above that the kernel is LOUD, not wrong: the packer refuses |w| > 255.875 (fused_f32.py), and an activation from 1023.75 on converts
+// to hi = +inf, lo = -inf, every product with it is NaN, the ReLU keeps NaNs (relu1_keep_nan) and the point's sigma or rgb comes out
+// NaN (tests/test_gpu_field_ranges.py); the other points of the launch are untouched.
 #include "field_f32_net.h"
 
 namespace {
@@ -82,7 +85,7 @@ struct SplitF16 {
             for (int sh = 0; sh < 2; sh++) {
                 float x[8];
                 #pragma unroll
-                for (int j = 0; j < 8; j++) x[j] = relu1(acc[t][8 * sh + j]);
+                for (int j = 0; j < 8; j++) x[j] = relu1_keep_nan(acc[t][8 * sh + j]);      // (an overflow upstream stays NaN)
                 b[2 * t + sh] = split8(x, kAccToX);       // accumulators hold kXS kWS y: the next operand is kXS y
             }
     }

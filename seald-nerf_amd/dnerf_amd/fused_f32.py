@@ -77,11 +77,22 @@ def pack_weights_f32(model):
     return flat
 
 
+LAYER_NAMES = ("D0", "D1", "D2", "D3", "D4", "D5", "D6", "D7", "S0", "S1", "C0", "C1", "C2")      # the kernels' stage order
+SPLIT_F16_MAX = 65504.0                      # the largest finite fp16 value
+SPLIT_WEIGHT_MAX = SPLIT_F16_MAX / 256.0     # 255.875: the largest |w| whose 2^8 w is a finite fp16 value
+
+
 def pack_weights_f32_split(model):
     """The same weights for csrc/field_f32x3.hip: every fp32 weight as hi + lo (two fp16 values), in the fp16 kernel's operand order
-    (fused.py kmaps), per layer [k-step][lane][m-tile][hi | lo][8 halves]; flat uint16, stage order D0 | D1..D6 | D7 S0 S1 C0 C1 C2."""
-    def layer(W, n_mt, kmaps):
+    (fused.py kmaps), per layer [k-step][lane][m-tile][hi | lo][8 halves]; flat uint16, stage order D0 | D1..D6 | D7 S0 S1 C0 C1 C2.
+    A weight whose 2^8 w does not fit fp16 (|w| > 255.875) is refused with `SdnError` naming its layer: it would be packed as an
+    infinity and every output would be NaN."""
+    def layer(name, W, n_mt, kmaps):
         W = np.asarray(W, dtype=np.float32) * np.float32(256.0)     # kWS of the kernel: keeps the lo parts out of the fp16 subnormals the MFMA flushes
+        top = float(np.abs(W).max()) if W.size else 0.0
+        if not top <= SPLIT_F16_MAX:       # (also a NaN or an infinity in the weights themselves)
+            raise sdn_backend.SdnError(f"split fp32 field: layer {name} has a weight of magnitude {top / 256.0:g}; 2^8 w must fit fp16 "
+                                       f"(|w| <= {SPLIT_WEIGHT_MAX:g}): use FusedFieldF32(variant='mfma32') for this model")
         hi = W.astype(np.float16)
         lo = (W - hi.astype(np.float32)).astype(np.float16)
         out = []
@@ -90,14 +101,19 @@ def pack_weights_f32_split(model):
             out.append(blk.transpose(1, 2, 0, 3))                       # [ks, lane, mt, 8]
         return np.ascontiguousarray(np.stack(out, axis=3)).reshape(-1)   # [ks, lane, mt, 2, 8]
 
-    flat = np.concatenate([layer(*l) for l in F16.layer_plan(model)]).view(np.uint16)
+    flat = np.concatenate([layer(name, *l) for name, l in zip(LAYER_NAMES, F16.layer_plan(model))]).view(np.uint16)
     assert flat.shape[0] * 2 == 4 * int(sdn_backend.lib.sdn_field_weight_floats_f32()), flat.shape
     return flat
 
 
 class FusedFieldF32(F16.DeformTimeRow, F16.FusedFieldBase):
     """Callable (xyzs [M,3], dirs [M,3]) -> (sigmas [M] f32, rgbs [M,3] f32): the fp32 network (dnerf/network.py:123-169 without
-    autocast) in one launch.  Same interface as `fused.FusedField` (time constants per value, live lists)."""
+    autocast) in one launch.  Same interface as `fused.FusedField` (time constants per value, live lists).
+
+    The "mfma32" variant has no operand envelope.  The "split" variant carries activations as 2^6 x and weights as 2^8 w in fp16 pairs:
+    it keeps its accuracy for activations of magnitude 2^-8 .. 1023 and weights of 2^-10 .. 255 (below, a term loses its lo part: 2^-11
+    of it at worst).  Above, it is loud: a weight beyond 255.875 is refused when the weights are packed (`SdnError` naming the layer),
+    and a point with a hidden activation from 1023.75 on returns a non-finite sigma or rgb, never a plausible finite one."""
 
     def __init__(self, model, time, max_points=None, variant=None):
         """variant: "mfma32" (default; csrc/field_f32.hip: v_mfma_f32_32x32x2_f32, 1e-4 from the fp32 network) or "split"
