@@ -47,9 +47,9 @@ def _linear(x16, w16):
 def activation_forward(act, z16):
     """utils.h:425-470 on the fp16 layer output."""
     x = z16.astype(np.float32)
-    with np.errstate(over="ignore"):
-        if act == 0:
-            return np.where(z16 > 0, z16, np.float16(0))
+    with np.errstate(over="ignore", invalid="ignore"):
+        if act == 0:       # a product with the compare result, not a select (utils.h:430): NaN -> NaN, -inf -> NaN, x < 0 -> -0
+            return z16 * (z16 > 0).astype(np.float16)
         if act == 1:
             return _h(np.exp(x))
         if act == 2:
@@ -57,8 +57,9 @@ def activation_forward(act, z16):
         if act == 3:
             return _h(np.float32(1) / (np.float32(1) + np.exp(-x)))
         if act == 4:
-            s = x * K_ACT
-            return _h(np.float32(0.5) * (s + np.sqrt(s * s + np.float32(4))) / K_ACT)
+            s = x * K_ACT                      # for s < 0 as 2 / (sqrt(s^2 + 4) - s): the reference's sum cancels to nothing there
+            r = np.sqrt(s * s + np.float32(4))
+            return _h(np.where(s < 0, np.float32(2) / (r - s), np.float32(0.5) * (s + r)) / K_ACT)
         if act == 5:
             return _h(np.log(np.exp(x * K_ACT) + np.float32(1)) / K_ACT)
     return z16
@@ -67,8 +68,9 @@ def activation_forward(act, z16):
 def activation_backward(act, g16, f16):
     """utils.h:538-583: gradient w.r.t. the pre-activation from the stored post-activation f."""
     f = f16.astype(np.float32)
-    if act == 0:
-        return np.where(f16 > 0, g16, np.float16(0))
+    if act == 0:           # utils.h:543, a product too: an infinite or NaN gradient behind a closed gate is NaN; a NaN f gives g * 0
+        with np.errstate(invalid="ignore"):
+            return g16 * (f16 > 0).astype(np.float16)
     if act == 1:
         return g16 * f16
     if act == 2:

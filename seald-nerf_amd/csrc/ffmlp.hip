@@ -421,6 +421,7 @@ int sdn_ffmlp_backward(const void *grad, const void *inputs, const void *weights
     if (calc_grad_inputs && !grad_inputs) return SDN_E_BADARG;
     if (!dims_ok(in, output_dim, W, L) || activation > ACT_NONE || activation == ACT_SINE || output_activation != ACT_NONE) return SDN_E_UNSUPPORTED;
     if ((uintptr_t)scratch & 15u) return SDN_E_BADARG;
+    if (L + 1 > (uint32_t)kMaxDw) return SDN_E_UNSUPPORTED;      // before anything is launched: a refused call writes nothing
 
     // 1. pre-activation gradients of every hidden layer (+ grad_inputs): one fused launch
     int rc = pack(weights, scratch, in, W, L, 1, calc_grad_inputs ? 1 : 0, st);
@@ -439,7 +440,6 @@ int sdn_ffmlp_backward(const void *grad, const void *inputs, const void *weights
     const size_t BW = (size_t)B * W;
     sdn_ffh::DwJob jobs[kMaxDw];
     uint32_t n = 0;
-    if (L + 1 > (uint32_t)kMaxDw) return SDN_E_UNSUPPORTED;
     // output layer: dW_out [16, W] = grad^T X_L                                   (ffmlp.cu:800-811)
     jobs[n++] = {grad, 16, 16, fwd + (L - 1) * BW, W, W, gw + (size_t)W * in + (size_t)(L - 1) * W * W};
     // hidden layers: dW_j [W, W] = G_j^T X_j, G_j = backward_buffer[L - 1 - j]   (ffmlp.cu:845-863)

@@ -48,6 +48,13 @@ __device__ __forceinline__ PairRuns row16_to_pair(uint4 v) {
     return PairRuns{__builtin_bit_cast(half4, a), __builtin_bit_cast(half4, b)};
 }
 
+// ReLU with the values of the reference's formula, a PRODUCT with the compare result (utils.h:430, :543: x * (x > 0), g * (f > 0)):
+// NaN stays NaN, -inf and an infinite or NaN gradient behind a closed gate become NaN (x * 0), so that an overflow upstream reaches
+// the loss and the GradScaler skips the step -- `x > 0 ? x : 0` turns all of them into a plausible 0 (a dead neuron whose weight row
+// never gets a gradient again).  The open side passes x itself (x * 1 without the multiply).
+__device__ __forceinline__ _Float16 relu16(_Float16 x) { return x > (_Float16)0 ? x : x * (_Float16)0; }
+__device__ __forceinline__ _Float16 relu16_gate(_Float16 g, _Float16 f) { return f > (_Float16)0 ? g : g * (_Float16)0; }
+
 // Activations act on one accumulator tile's 16 values per lane at a time, with the dispatch outside the element loops
 // (ARELU = true: compiled for ReLU only -- the hot case; false: run-time dispatch over the other six).
 // utils.h:425-470 (forward) on the fp16-rounded layer output.  The transcendental ones use the hardware
@@ -57,13 +64,13 @@ template <bool ARELU>
 __device__ __forceinline__ void act_forward16(uint32_t act, _Float16 (&v)[16]) {
     if (ARELU) {
         #pragma unroll
-        for (int i = 0; i < 16; i++) v[i] = v[i] > (_Float16)0 ? v[i] : (_Float16)0;
+        for (int i = 0; i < 16; i++) v[i] = relu16(v[i]);
         return;
     }
     switch (act) {
         case ACT_RELU:
             #pragma unroll
-            for (int i = 0; i < 16; i++) v[i] = v[i] > (_Float16)0 ? v[i] : (_Float16)0;
+            for (int i = 0; i < 16; i++) v[i] = relu16(v[i]);
             break;
         case ACT_EXP:
             #pragma unroll
@@ -79,7 +86,10 @@ __device__ __forceinline__ void act_forward16(uint32_t act, _Float16 (&v)[16]) {
             break;
         case ACT_SQUAREPLUS:
             #pragma unroll
-            for (int i = 0; i < 16; i++) { const float x = (float)v[i] * kAct; v[i] = (_Float16)(0.5f * (x + __fsqrt_rn(x * x + 4.0f)) / kAct); }
+            for (int i = 0; i < 16; i++) {     // 0.5 (x + sqrt(x^2 + 4)); for x < 0 as 2 / (sqrt(x^2 + 4) - x): the sum cancels to nothing there
+                const float x = (float)v[i] * kAct, r = __fsqrt_rn(x * x + 4.0f);
+                v[i] = (_Float16)((x < 0.0f ? __fdividef(2.0f, r - x) : 0.5f * (x + r)) / kAct);
+            }
             break;
         case ACT_SOFTPLUS:
             #pragma unroll
@@ -94,13 +104,13 @@ template <bool ARELU>
 __device__ __forceinline__ void act_backward16(uint32_t act, _Float16 (&g)[16], const _Float16 (&f)[16]) {
     if (ARELU) {
         #pragma unroll
-        for (int i = 0; i < 16; i++) g[i] = f[i] > (_Float16)0 ? g[i] : (_Float16)0;
+        for (int i = 0; i < 16; i++) g[i] = relu16_gate(g[i], f[i]);
         return;
     }
     switch (act) {
         case ACT_RELU:
             #pragma unroll
-            for (int i = 0; i < 16; i++) g[i] = f[i] > (_Float16)0 ? g[i] : (_Float16)0;
+            for (int i = 0; i < 16; i++) g[i] = relu16_gate(g[i], f[i]);
             break;
         case ACT_EXP:
             #pragma unroll

@@ -302,7 +302,7 @@ __global__ void __launch_bounds__(64) k_train_sigma_fwd(SigmaFwd P) {
         for (uint32_t s = 0; s < 2; s++) acc = mfma16(a_frag(P.w1, kSigIn, kSigW, 32 * Mt + n, s, h), B1[s], acc);
         _Float16 v[16];
         #pragma unroll
-        for (int i = 0; i < 16; i++) { const _Float16 x = (_Float16)acc[i]; v[i] = x > (_Float16)0 ? x : (_Float16)0; }
+        for (int i = 0; i < 16; i++) { const _Float16 x = (_Float16)acc[i]; v[i] = x > (_Float16)0 ? x : x * (_Float16)0; }   // x * (x > 0): keeps NaN (ffmlp_kernels.h relu16)
         #pragma unroll
         for (uint32_t p = 0; p < 2; p++) {
             const h4 g0{v[8 * p], v[8 * p + 1], v[8 * p + 2], v[8 * p + 3]}, g1{v[8 * p + 4], v[8 * p + 5], v[8 * p + 6], v[8 * p + 7]};
@@ -564,8 +564,9 @@ __global__ void __launch_bounds__(64) k_train_sigma_bwd(SigmaBwd P) {
             h4 g0, g1;
             #pragma unroll
             for (int e = 0; e < 4; e++) {
-                g0[e] = f0[e] > (_Float16)0 ? (_Float16)acc[8 * p + e] : (_Float16)0;
-                g1[e] = f1[e] > (_Float16)0 ? (_Float16)acc[8 * p + 4 + e] : (_Float16)0;
+                const _Float16 a0 = (_Float16)acc[8 * p + e], a1 = (_Float16)acc[8 * p + 4 + e];      // g * (f > 0): a non-finite g stays visible
+                g0[e] = f0[e] > (_Float16)0 ? a0 : a0 * (_Float16)0;
+                g1[e] = f1[e] > (_Float16)0 ? a1 : a1 * (_Float16)0;
             }
             B2[2 * Mt + p] = join(g0, g1);
             const uint4 row16 = runs_to_row16(g0, g1);

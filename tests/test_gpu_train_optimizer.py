@@ -350,3 +350,43 @@ def test_the_masked_column_and_the_largest_finite_gradients_do_not_skip():
     c.scaler._growth_tracker.zero_()
     found, st = _pass(c, 0.5, g, what="+-65504 everywhere")
     assert not found and (st.scale, st.tracker) == (1024.0, 1)
+
+
+def _bits(t):
+    return t.detach().contiguous().view(torch.int32)
+
+
+def test_a_nan_hidden_weight_of_the_deformation_mlp_skips_the_step():
+    """One weight of a hidden row of deform_net is NaN: that neuron's pre-activation is NaN on every sample, and the ReLU of the MLP
+    chains (csrc/ffmlp_kernels.h, the reference's x * (x > 0)) keeps it, so the loss is non-finite, the step is skipped, the scaler
+    backs off and no parameter, moment or fp16 copy changes.  (A select-ReLU turned the NaN into a dead neuron: a finite loss, a
+    normal update, and a zero gradient for the offending row for good.)  The step's own gradients are used: nothing is injected."""
+    from dnerf_amd.bench_scene import build_scene
+    c = _settled()
+    c.inject.grads, c.inject.world, c.inject.single_process = {}, 1, True
+    # 64 rays through the middle of the 32 x 32 image (the fixture's own first 64 are a corner of it and sample nothing)
+    sc = build_scene(H=32, W=32, device="cuda", seed=0)
+    idx = (torch.arange(14, 18)[:, None] * 32 + torch.arange(8, 24)[None, :]).reshape(-1).cuda()
+    rays_o, rays_d = sc.rays_o[idx].contiguous(), sc.rays_d[idx].contiguous()
+    clean = float(c.step(rays_o, rays_d, c.target, 0.5, grads_only=True))
+    assert np.isfinite(clean) and bool(c.step.view("g_deform", F16, c.shapes["g_deform"]).any()), "the rays sample nothing"
+    p = c.step.params[2]                                  # deform_net.1.weight [128, 128]
+    assert tuple(p.shape) == (S.DEF_W, S.DEF_W)
+    old = float(p.data[5, 7])
+    try:
+        p.data[5, 7] = float("nan")
+        c.step.refresh()
+        before = _state(c)
+        loss = float(c.step(rays_o, rays_d, c.target, 0.5))
+        after = _state(c)
+        assert not np.isfinite(loss), loss
+        assert after.steps == before.steps and (after.scale, after.tracker) == (before.scale * 0.5, 0)
+        for i in range(14):
+            assert torch.equal(_bits(after.p[i]), _bits(before.p[i])) and torch.equal(after.m[i], before.m[i]) and torch.equal(after.v[i], before.v[i]), i
+        assert all(torch.equal(after.w[k].view(torch.int16), before.w[k].view(torch.int16)) for k in before.w)
+        assert not after.g_table.any()
+    finally:
+        p.data[5, 7] = old
+        c.step.refresh()
+        c.scaler._scale.fill_(1024.0)
+        c.scaler._growth_tracker.zero_()
